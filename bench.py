@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of the batched safety-gridworld step path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,20 +10,23 @@ island_navigation_ex envs (level 9, default flags) PER GPU, synthetic uniform ac
 Philox-4x32-10 keyed by the global env id.  One bench "step" = one pass of the hot path over the
 batch = ONE sgw_step kernel launch advancing all 65 536 envs by one env.step() (auto-reset
 included), writing board + reward vector + step_type + term_reason + safety + frame.  The
-action batches are resident in HBM before the timed region starts; the K launches of a batch are
-issued back to back by sgw_step_n (host loop in C).  A K-step batch at this size lasts K x ~9 us, so
-the timed region REPEATS the K-step batch R times (R chosen after warmup so that the region lasts
->= --min-seconds, default 2 s; "repeats" / "timed_steps" in the JSON line; --min-seconds 0 times
-exactly K steps): with the driver's `--steps 20` alone the region would be 0.2 ms of event / sync
-overhead and clock ramp.  value = envs x K x R x N_gpus / max-over-ranks time.
+action batches are resident in HBM before the timed region starts; the launches are issued back
+to back by sgw_step_n (host loop in C, at most 2000 steps per call, replayed as captured hipGraphs).
+The timed region is exactly K steps ("timed_steps"); --min-seconds S repeats the K-step pass R
+times until the region lasts >= S ("repeats").  ms_per_step = time of the region / timed steps,
+value = envs x timed steps x N_gpus / max-over-ranks time.  With the same arguments (and no
+--min-seconds) the timed steps start from the same state with the same actions in every run, and
+--dump-outputs DIR writes what the last of them returned (output arrays + episodic returns, .npy).
 Envs are sharded by contiguous global-id ranges; the only collective is one all-reduce (RCCL)
 of the episodic-return accumulators after the batch ("scaling": "weak").
 
-Also reported (same JSON line): the fused-rollout mode (512 steps in ONE launch, state in
-registers, outputs written every step), the roofline of the step kernel, and a CPU baseline =
-the C oracle (oracle/, "port" of the reference semantics, bit-identical outputs) on a bounded
-sample of the same workload on this box's host cores, with the reference's own CPython rate
-(measured in the build container, profiles/reference_cpython.json) beside it.
+The JSON line also carries the roofline of the step kernel from the same timed region.  --full
+adds legs of their own after the headline: the fused-rollout mode (512 steps in ONE launch,
+state in registers, outputs written every step), the agents' windows from the round launch,
+every observation of env.step() (sgw_step_full), the mixed suite as one launch per step, and a
+CPU baseline = the C oracle (oracle/, "port" of the reference semantics, bit-identical outputs)
+on a bounded sample of the same workload on the host cores, with the reference's own CPython
+rate (profiles/reference_cpython.json) beside it.
 """
 import argparse
 import json
@@ -52,6 +55,8 @@ VALU_PEAK_GINST = 256 * 4 * 2.4 / 2.0
 # families whose round kernel is bound by instruction issue, not by HBM: SQ_INSTS_VALU per launch comes from this round's PMC pass
 VALU_BOUND = {"firemaker_ex_ma": ("r03_pmc_firemaker_ex_ma.json", "r02_pmc_firemaker_ex_ma.json"),
               "aintelope_savanna": ("r03_pmc_aintelope_savanna.json", "r02_pmc_aintelope_savanna.json")}     # newest first
+MAX_CALL_STEPS = 2000            # steps per sgw_step_n call at most (one captured hipGraph each)
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: bytes written at most
 # algorithmic bytes per env-step, island_navigation_ex L9 (step-per-launch mode):
 # action 1 + state 80 read + 80 write + board 48 + reward 80 + done 1 + term 1 + safety/hidden 8
 # (per-workload figures live in WORKLOADS below; fused rollout: the two state terms drop out)
@@ -190,6 +195,18 @@ def fill_action_batches(engines, K, R, step0=0, max_steps=4096):
   return n_distinct
 
 
+def step_engines(engines, spans, accumulate, group=None):
+  """One sgw_step_n call per engine on its stream (or one sgw_group_step_n over the group) for the action spans given, one per
+  engine; e["out"] = what the call hands back, the last step's output arrays."""
+  if group is not None:
+    for e, o in zip(engines, group.step_n(spans, accumulate=accumulate)):
+      e["out"] = o
+  else:
+    for e, span in zip(engines, spans):
+      with torch.cuda.stream(e["stream"]):
+        e["out"] = e["eng"].step_n(span, accumulate=accumulate)
+
+
 def run_batches(engines, K, first, count, accumulate, group=None):
   """`count` batches of exactly K sgw_step launches per engine (sgw_step_n: the host loop is in C), one stream per
   engine; batch j uses action batch j modulo the number resident.  `group` (an EngineGroup over the same engines): K
@@ -201,14 +218,44 @@ def run_batches(engines, K, first, count, accumulate, group=None):
   while j < end:                               # batch-major: every family's stream is fed in turn (a mixed suite runs concurrently)
     nd = min(e["acts"].shape[0] // K for e in engines)
     b = j % nd
-    g = max(1, min(end - j, nd - b, 2000 // max(K, 1)))
-    if group is not None:
-      group.step_n([e["acts"][b * K:(b + g) * K] for e in engines], accumulate=accumulate)
-    else:
-      for e in engines:
-        with torch.cuda.stream(e["stream"]):
-          e["eng"].step_n(e["acts"][b * K:(b + g) * K], accumulate=accumulate)
+    g = max(1, min(end - j, nd - b, MAX_CALL_STEPS // max(K, 1)))
+    step_engines(engines, [e["acts"][b * K:(b + g) * K] for e in engines], accumulate, group)
     j += g
+
+
+def run_steps(engines, n_steps, B, accumulate, group=None):
+  """Exactly n_steps launches per engine: n_steps // B batches of B steps (run_batches), then the remaining n_steps % B steps
+  from the head of action batch 0."""
+  run_batches(engines, B, 0, n_steps // B, accumulate, group)
+  r = n_steps % B
+  if r:
+    step_engines(engines, [e["acts"][:r] for e in engines], accumulate, group)
+
+
+def dump_outputs(path, engines, returns, budget=DUMP_BYTES):
+  """--dump-outputs: the last timed step's output arrays of every engine on this rank (what sgw_step_n hands its caller) and the
+  all-reduced episodic returns, as DIR/<name>.npy: float64 outputs as they are, the integer ones as float32 (exact: bytes, small
+  counters).  Beyond `budget` bytes in all, the same fixed, seeded sample of env rows of every engine (DIR/[<family>_]env_index.npy)."""
+  os.makedirs(path, exist_ok=True)
+  arrays = {}
+  for fam, (spec, acc) in returns.items():
+    arrays["returns" if len(returns) == 1 else "returns_" + fam] = acc.astype(np.float64)
+  per_engine = []
+  for e in engines:
+    prefix = "" if len(engines) == 1 else e["fam"] + "_"
+    outs = {prefix + k: v.cpu().numpy() for k, v in e["out"].items()}
+    per_engine.append((prefix, e["n"], {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in outs.items()}))
+  total, room = sum(v.nbytes for _, _, outs in per_engine for v in outs.values()), budget - (1 << 20)   # 1 MB: returns, headers
+  frac = 1.0 if total <= room else room / float(total + 8 * sum(n for _, n, _ in per_engine))          # 8 B per env: its index
+  for prefix, n, outs in per_engine:
+    if frac < 1.0:
+      idx = np.sort(np.random.default_rng(SEED).choice(n, max(1, int(n * frac)), replace=False))
+      outs = {k: v[idx] for k, v in outs.items()}
+      outs[prefix + "env_index"] = idx.astype(np.float64)
+    arrays.update(outs)
+  for name, v in arrays.items():
+    np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v))
+  return sorted(arrays)
 
 
 def main():
@@ -218,15 +265,24 @@ def main():
   ap.add_argument("--warmup", type=int, default=200)
   ap.add_argument("--workload", default="island_navigation_ex", choices=sorted(WORKLOADS) + ["mixed"])
   ap.add_argument("--envs", type=int, default=0, help="envs per GPU (default: the workload's BASELINE size)")
-  ap.add_argument("--min-seconds", type=float, default=2.0,
-                  help="the timed region repeats the K-step batch until it lasts at least this long (0: exactly K steps)")
+  ap.add_argument("--min-seconds", type=float, default=None,
+                  help="repeat the K-step pass until the timed region lasts at least this long (default: exactly K timed steps; "
+                       "0: exactly K and no clock-ramp batches); --full sizes its other legs by it (default 2 s)")
+  ap.add_argument("--full", action="store_true",
+                  help="also measure the fused rollout, the agents' windows, every observation of env.step(), the mixed suite as "
+                       "one launch and the CPU baseline (legs of their own after the headline)")
+  ap.add_argument("--dump-outputs", metavar="DIR",
+                  help="write the last timed step's output arrays and the episodic returns to DIR/<name>.npy (rank 0)")
   ap.add_argument("--cpu-seconds", type=float, default=12.0)
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--no-fused", action="store_true")
   ap.add_argument("--mixed-group", action="store_true",
                   help="mixed suite: time ONE heterogeneous launch per step (sgw_group_step_n) as the headline instead of one launch "
-                       "per family on three streams; the default run reports it beside the headline as 'group_launch'")
+                       "per family on three streams; --full reports it beside the headline as 'group_launch'")
   a = ap.parse_args()
+  if a.steps < 1 or a.warmup < 0:
+    sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
+  side_seconds = 2.0 if a.min_seconds is None else a.min_seconds      # the --full legs' timed regions
 
   rank, local_rank, world = parallel.world()
   if world != a.gpus:
@@ -254,34 +310,42 @@ def main():
       dist.barrier()                                    # nccl: on this rank's device; gloo (rehearsal): host
     torch.cuda.synchronize(device)
 
-  # ---- warmup (untimed): W steps as asked, then K-step batches until the clocks have ramped (>= 0.25 s of launches);
-  # the same batches calibrate how many repeats R of the K-step batch make a timed region of >= --min-seconds
-  # (the driver's `--steps 20` alone would be a 0.2 ms region: event / sync overhead and the clock ramp, not the kernel)
-  warm_acts = [e["eng"].fill_actions(max(W, 1), SEED) for e in engines]
-  torch.cuda.synchronize(device)
+  # ---- warmup (untimed): W steps as asked, then B-step batches until the clocks have ramped (>= 0.25 s of launches); the same
+  # batches calibrate how many repeats R of the K-step pass make a timed region of >= --min-seconds when that is asked for.
+  # A K-step pass = K // B batches of B <= MAX_CALL_STEPS steps and a remainder, so any --steps stays a bounded set of graphs.
+  # How many ramp batches run depends on the clock: the state after the W steps is put back after them, so that with the same
+  # arguments the timed steps compute the same outputs from run to run (R = 1 unless --min-seconds > 0)
+  B = min(K, MAX_CALL_STEPS)
   if W > 0:
-    if group is not None:
-      group.step_n([wa[:W] for wa in warm_acts], accumulate=False)
-    else:
-      for e, wa in zip(engines, warm_acts):
-        with torch.cuda.stream(e["stream"]):
-          e["eng"].step_n(wa[:W], accumulate=False)
-  del warm_acts
-  fill_action_batches(engines, K, 1, step0=W)
+    warm_acts = [e["eng"].fill_actions(min(W, MAX_CALL_STEPS), SEED) for e in engines]
+    torch.cuda.synchronize(device)
+    for s in range(0, W, MAX_CALL_STEPS):
+      step_engines(engines, [wa[:min(MAX_CALL_STEPS, W - s)] for wa in warm_acts], False, group)
+    del warm_acts
+  torch.cuda.synchronize(device)
+  saved = [e["eng"].get_state() for e in engines]
+  fill_action_batches(engines, B, 1, step0=W)
   torch.cuda.synchronize(device)
   c0, nb = time.perf_counter(), 0
   while True:
-    run_batches(engines, K, 0, 1, False, group)
+    run_batches(engines, B, 0, 1, False, group)
     torch.cuda.synchronize(device)
     nb += 1
-    if time.perf_counter() - c0 >= (0.25 if a.min_seconds > 0 else 0.0) or nb >= 20000:
+    if time.perf_counter() - c0 >= (0.0 if a.min_seconds == 0 else 0.25) or nb >= 20000:
       break
   t_batch = parallel.max_over_ranks((time.perf_counter() - c0) / nb, device, dist)
-  R = 1 if a.min_seconds <= 0 else int(min(200000, max(1, -(-a.min_seconds // t_batch))))
-  n_distinct = fill_action_batches(engines, K, R, step0=W)      # action batches resident in HBM before the timed region
-  # untimed: two passes over the resident batches -- sgw_step_n captures a call's launches as a hipGraph the second time it sees
-  # the same buffers and replays it from then on; the timed region below is all replays (accumulate=True as timed, then cleared)
-  run_batches(engines, K, 0, 2 * n_distinct, True, group)
+  R = 1 if not a.min_seconds else int(min(200000, max(1, -(-a.min_seconds // (t_batch * K / B)))))
+  KR = K * R
+  for e, st in zip(engines, saved):
+    e["eng"].set_state(st)
+  del saved
+  n_distinct = fill_action_batches(engines, B, KR // B, step0=W)      # action batches resident in HBM before the timed region
+  # untimed: every distinct sgw_step_n call of the timed region twice -- sgw_step_n captures a call's launches as a hipGraph the
+  # second time it sees the same buffers and replays it from then on; the timed region below is all replays (accumulate=True as
+  # timed, then cleared)
+  run_batches(engines, B, 0, 2 * n_distinct, True, group)
+  for _ in range(2 if KR % B else 0):
+    step_engines(engines, [e["acts"][:KR % B] for e in engines], True, group)
   for e in engines:
     with torch.cuda.stream(e["stream"]):
       e["eng"].read_returns(clear=True)
@@ -290,12 +354,11 @@ def main():
   barrier()
   t0 = time.perf_counter()
   ev0.record(engines[0]["stream"])
-  run_batches(engines, K, 0, R, True, group)                     # R x exactly K steps, launches issued from C
+  run_steps(engines, KR, B, True, group)                         # exactly K x R steps, launches issued from C
   ev1.record(engines[0]["stream"])
   torch.cuda.synchronize(device)
   elapsed = time.perf_counter() - t0
   barrier()
-  KR = K * R
   kernel_ms = ev0.elapsed_time(ev1) / KR                # avg launch-to-launch time of the first family's kernel, HIP events on ITS stream
   elapsed = parallel.max_over_ranks(elapsed, device, dist)
   returns = {}
@@ -307,30 +370,34 @@ def main():
         acc += e["eng"].read_returns()
     parallel.allreduce_returns(acc, dist)              # the one collective: episodic returns, end of batch
     returns[fam] = (spec, acc.cpu().numpy())
+  if a.dump_outputs and rank == 0:
+    dump_outputs(a.dump_outputs, engines, returns)
 
+  # ---- --full: the legs beside the headline, each on fresh engines after it, regions sized by --min-seconds (default 2 s)
   fused = None
   group_launch = None
-  if a.workload == "mixed" and not grouped:
+  if a.full and a.workload == "mixed" and not grouped:
     # the same suite stepped by ONE heterogeneous launch per step (sgw_group_step_n), on fresh engines, after the headline
     engs3 = build_engines(parts, device, streams=False)
     for e3, e in zip(engs3, engines):
       e3["acts"] = e["acts"]
     g3 = EngineGroup([e["eng"] for e in engs3])
-    nb3 = int(max(3, min(R, -(-0.4 * max(a.min_seconds, 0.05) // max(t_batch, 1e-6)))))
-    run_batches(engs3, K, 0, 2 * n_distinct, True, g3)         # first sighting + capture of every resident batch
+    R_side = 1 if side_seconds <= 0 else int(min(200000, max(1, -(-side_seconds // (t_batch * K / B)))))
+    nb3 = int(max(3, min(R_side * K // B, -(-0.4 * max(side_seconds, 0.05) // max(t_batch, 1e-6)))))
+    run_batches(engs3, B, 0, 2 * n_distinct, True, g3)         # first sighting + capture of every resident batch
     torch.cuda.synchronize(device)
     g0 = time.perf_counter()
-    run_batches(engs3, K, 0, nb3, True, g3)
+    run_batches(engs3, B, 0, nb3, True, g3)
     torch.cuda.synchronize(device)
-    gdt = parallel.max_over_ranks(time.perf_counter() - g0, device, dist) / (K * nb3)
+    gdt = parallel.max_over_ranks(time.perf_counter() - g0, device, dist) / (B * nb3)
     group_launch = {"value": world * sum(e["n"] for e in engs3) / gdt, "unit": "env-steps/s", "us_per_step": gdt * 1e6, "launches_per_step": 1,
-                    "timed_steps": K * nb3, "kernel": "sgw::k_engine_group<K_STEP>",
+                    "timed_steps": B * nb3, "kernel": "sgw::k_engine_group<K_STEP>",
                     "note": "one launch = every member's envs; its time is the slowest member's single-wave latency plus the member "
                             "dispatch, three concurrent per-family launches overlap theirs"}
     g3.close()
     for e3 in engs3:
       e3["eng"].close()
-  if not a.no_fused and a.workload == "mixed":
+  if a.full and not a.no_fused and a.workload == "mixed":
     # the mixed suite's fused leg: ONE launch advances every member 512 steps (sgw_group_rollout)
     engs2 = [prepare_engine(e["fam"], e["spec"], e["n"], e["base"], device, e["wl"]["outputs"]) for e in engines]
     g2 = EngineGroup(engs2)
@@ -341,7 +408,7 @@ def main():
     g2.rollout(Tf, SEED, step0=Tf, write_every=True)
     torch.cuda.synchronize(device)
     t_launch = parallel.max_over_ranks(time.perf_counter() - c0, device, dist)
-    Rf = 1 if a.min_seconds <= 0 else int(min(10000, max(1, -(-0.6 * a.min_seconds // t_launch))))
+    Rf = 1 if side_seconds <= 0 else int(min(10000, max(1, -(-0.6 * side_seconds // t_launch))))
     barrier()
     f0 = time.perf_counter()
     ev0.record()
@@ -362,7 +429,7 @@ def main():
     g2.close()
     for e2 in engs2:
       e2.close()
-  elif not a.no_fused and a.workload != "mixed":
+  elif a.full and not a.no_fused and a.workload != "mixed":
     e = engines[0]
     eng2 = prepare_engine(e["fam"], e["spec"], e["n"], rank * e["n"], device, e["wl"]["outputs"])
     Tf = 512 if e["fam"] != "firemaker_ex_ma" else 128      # steps per launch: a property of the mode, not of --steps
@@ -372,7 +439,7 @@ def main():
     eng2.rollout(Tf, SEED, step0=Tf, write_every=True)
     torch.cuda.synchronize(device)
     t_launch = parallel.max_over_ranks(time.perf_counter() - c0, device, dist)
-    Rf = 1 if a.min_seconds <= 0 else int(min(10000, max(1, -(-0.6 * a.min_seconds // t_launch))))
+    Rf = 1 if side_seconds <= 0 else int(min(10000, max(1, -(-0.6 * side_seconds // t_launch))))
     barrier()
     f0 = time.perf_counter()
     ev0.record()
@@ -395,12 +462,16 @@ def main():
   # multi-agent families (BASELINE config 4, "via Zoo parallel API"): the same round loop with the agent-centric windows --
   # what the Zoo wrapper hands to the agents as observations -- written by the SAME launch (sgw_out.views: the
   # round kernel assembles them from the board rows it holds in LDS); after the main measurement so that it cannot disturb it
+  side_acts = None
+  if a.full and a.workload != "mixed" and world == 1:
+    side_acts = engines[0]["eng"].fill_actions(500, SEED, step0=W)      # resident actions of the two legs below
+    torch.cuda.synchronize(device)
   with_views = None
-  if a.workload != "mixed" and world == 1 and fused_views(engines[0]["spec"]):
+  if side_acts is not None and fused_views(engines[0]["spec"]):
     e = engines[0]
     engv = prepare_engine(e["fam"], e["spec"], e["n"], rank * e["n"], device, tuple(e["wl"]["outputs"]) + ("views",))
     vb = int(engv._lib.sgw_view_bytes(engv._h))
-    acts = e["acts"]
+    acts = side_acts
     nv = int(min(acts.shape[0], 500))
     for _ in range(3):                                   # first sighting, graph capture, first replay
       engv.step_n(acts[:nv], accumulate=True)
@@ -408,7 +479,7 @@ def main():
     c0 = time.perf_counter()
     engv.step_n(acts[:nv], accumulate=True)
     torch.cuda.synchronize(device)
-    reps = 1 if a.min_seconds <= 0 else int(max(1, min(1000, -(-0.5 * a.min_seconds // (time.perf_counter() - c0)))))
+    reps = 1 if side_seconds <= 0 else int(max(1, min(1000, -(-0.5 * side_seconds // (time.perf_counter() - c0)))))
     v0 = time.perf_counter()
     ev0.record()
     for _ in range(reps):
@@ -428,12 +499,12 @@ def main():
   # hipGraph, sgw_extras.replay, costs ~5 us of host time per step instead of ~25 but ~5 us more GPU time -- 44 instead of 39 us),
   # actions refilled in place in a persistent buffer as an RL loop does
   full_obs = None
-  if a.workload != "mixed" and world == 1 and engines[0]["spec"].A == 1:
+  if side_acts is not None and engines[0]["spec"].A == 1:
     from ai_safety_gridworlds_amd.helpers.gridworld_gym_env import GridworldVectorEnv
     e = engines[0]
     engf = prepare_engine(e["fam"], e["spec"], e["n"], rank * e["n"], device,
                           tuple(dict.fromkeys(tuple(e["wl"]["outputs"]) + GridworldVectorEnv.FULL_OUTPUTS)))
-    acts = e["acts"]
+    acts = side_acts
     nf = int(min(acts.shape[0], 400))
     buf = torch.empty_like(acts[0])
     # (the original scalar envs observe OCCLUDED layers, safety_game.py: no unoccluded layer tables in their specs)
@@ -501,8 +572,9 @@ def main():
         "config": {"workload": "%s, %d envs/GPU, one sgw_step launch per family per step, uniform Philox actions "
                                "resident in HBM" % (desc, n_rank),
                    "envs_per_gpu": n_rank, "outputs": list(e0["wl"]["outputs"]), "sharding": "env-id ranges, dp%d" % world,
-                   "timed_region": "%d repeats of the %d-step batch (>= %.2f s; warmup = %d steps + clock-ramp batches), "
-                                   "%d distinct action batches resident in HBM" % (R, K, a.min_seconds, W, n_distinct)},
+                   "timed_region": "%d repeat(s) of the %d-step pass (%s; warmup = %d steps + clock-ramp batches), "
+                                   "%d distinct %d-step action batches resident in HBM"
+                                   % (R, K, ">= %.2f s" % a.min_seconds if a.min_seconds else "exactly --steps", W, n_distinct, B)},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                      "kernel": ("sgw::k_engine_group<K_STEP>" if grouped else
@@ -544,7 +616,7 @@ def main():
       line["group_launch"] = group_launch
     if fused is not None:
       line["fused_rollout"] = fused
-    if world == 1 and not a.no_cpu_baseline and a.workload == "island_navigation_ex":
+    if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "island_navigation_ex":
       threads = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
       threads = max(1, min(threads, 64))
       line["cpu_baseline"] = cpu_baseline(n, a.cpu_seconds, threads)

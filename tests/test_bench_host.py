@@ -2,6 +2,7 @@
 j modulo the number resident, whatever grouping run_batches uses to hand contiguous batches to sgw_step_n in one call; and the
 mixed suite's parts must cover the global env-id ranges exactly once over the ranks."""
 import contextlib
+import os
 
 import numpy as np
 import pytest
@@ -58,3 +59,54 @@ def test_mixed_parts_cover_the_global_ranges_once(world):
       assert a1 <= b0                                            # no env id belongs to two ranks
     total += sum(hi - lo for lo, hi in spans)
   assert total == world * per_gpu and set(seen) == set(B.MIXED)
+
+
+@pytest.mark.parametrize("n_steps,batch,nd", [(20, 20, 1), (4567, 2000, 2), (2000, 2000, 1), (1, 1, 1), (6001, 2000, 2)])
+def test_run_steps_times_exactly_the_asked_steps(n_steps, batch, nd, monkeypatch):
+  """bench.py --steps N: the timed region is N launches per engine whatever N is -- batches of B <= MAX_CALL_STEPS steps and a
+  remainder from the head of action batch 0 -- and every call's outputs are kept as the engine's "out"."""
+  monkeypatch.setattr(torch.cuda, "stream", lambda s: contextlib.nullcontext())
+
+  class Acts(FakeActs):
+    def __getitem__(self, sl):
+      return (sl.start or 0, sl.stop)
+
+  class Eng(FakeEngine):
+    def step_n(self, span, accumulate=False):
+      self.calls.append(span)
+      return {"last": span}
+  engines = [dict(eng=Eng(), acts=Acts(batch * nd), stream=None) for _ in range(2)]
+  B.run_steps(engines, n_steps, batch, True)
+  for e in engines:
+    assert sum(hi - lo for lo, hi in e["eng"].calls) == n_steps
+    assert all(hi - lo <= B.MAX_CALL_STEPS for lo, hi in e["eng"].calls)
+    assert e["out"] == {"last": e["eng"].calls[-1]}
+
+
+def test_dump_outputs_float_files_within_budget(tmp_path):
+  """--dump-outputs: float32 / float64 .npy files only, at most the budget in all (a seeded sample of env rows beyond it, with
+  the rows' env ids), the same files from the same arrays."""
+  n = 4096
+  g = torch.Generator().manual_seed(3)
+  out = {"board": torch.randint(0, 9, (n, 6, 8), generator=g, dtype=torch.uint8),
+         "reward": torch.randn(n, 10, generator=g, dtype=torch.float64),
+         "frame": torch.randint(0, 100, (n,), generator=g, dtype=torch.int32)}
+  engines = [dict(fam="island_navigation_ex", n=n, out=out)]
+  returns = {"island_navigation_ex": (None, np.arange(11, dtype=np.float64))}
+  full = B.dump_outputs(str(tmp_path / "all"), engines, returns, budget=64 * 10 ** 6)
+  assert full == ["board", "frame", "returns", "reward"]
+  a = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in full}
+  assert a["board"].dtype == np.float32 and a["reward"].dtype == np.float64 and a["frame"].dtype == np.float32
+  assert np.array_equal(a["board"], out["board"].numpy()) and np.array_equal(a["reward"], out["reward"].numpy())
+  budget = (1 << 20) + 100000                                  # room for ~1/4 of the 4096 rows
+  names = B.dump_outputs(str(tmp_path / "s1"), engines, returns, budget=budget)
+  B.dump_outputs(str(tmp_path / "s2"), engines, returns, budget=budget)
+  assert "env_index" in names
+  assert sum(os.path.getsize(str(tmp_path / "s1" / (k + ".npy"))) for k in names) <= budget
+  idx = np.load(str(tmp_path / "s1" / "env_index.npy")).astype(np.int64)
+  assert 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+  for k in names:
+    s1, s2 = np.load(str(tmp_path / "s1" / (k + ".npy"))), np.load(str(tmp_path / "s2" / (k + ".npy")))
+    assert s1.dtype in (np.float32, np.float64) and np.array_equal(s1, s2)
+    if k in ("board", "reward", "frame"):
+      assert np.array_equal(s1, a[k][idx])
