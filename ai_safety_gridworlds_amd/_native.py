@@ -90,6 +90,7 @@ def lib():
     getattr(L, f).restype = C.c_int64
     getattr(L, f).argtypes = [C.c_void_p]
   L.sgw_state_words.argtypes = [C.c_void_p]
+  L.sgw_step_shape.argtypes = [C.c_void_p]
   L.sgw_set_episode_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
   L.sgw_set_rng_state.argtypes = [C.c_void_p, C.c_void_p]
   L.sgw_set_random_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
@@ -140,7 +141,8 @@ EXPORTS = [
     "sgw_abi_version", "sgw_last_error", "sgw_build_info", "sgw_sizeof_spec", "sgw_sizeof_out", "sgw_sizeof_extras", "sgw_create", "sgw_track_performance", "sgw_step_full",
     "sgw_destroy", "sgw_n_envs", "sgw_n_pad", "sgw_state_bytes", "sgw_set_episode_bits",
     "sgw_set_rng_state", "sgw_set_random_stream", "sgw_set_family_table", "sgw_pow_f64", "sgw_pow_selfcheck", "sgw_reset", "sgw_step", "sgw_step_n", "sgw_rollout", "sgw_replay", "sgw_group_create", "sgw_group_destroy", "sgw_group_step_n", "sgw_group_rollout", "sgw_read_returns", "sgw_fill_actions",
-    "sgw_accumulate_returns", "sgw_observe", "sgw_derived_stats", "sgw_observe_layers", "sgw_state_layers", "sgw_view_bytes", "sgw_agent_views", "sgw_agent_layer_views", "sgw_state_words", "sgw_get_state", "sgw_set_state"]
+    "sgw_accumulate_returns", "sgw_observe", "sgw_derived_stats", "sgw_observe_layers", "sgw_state_layers", "sgw_view_bytes", "sgw_agent_views", "sgw_agent_layer_views", "sgw_state_words", "sgw_get_state", "sgw_set_state",
+    "sgw_step_shape"]
 
 
 def check(rc, what=""):

@@ -6,6 +6,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sgw.h"
@@ -72,7 +74,8 @@ struct sgw_engine {
   long long graph_tick;
   std::vector<StepGraph> graphs;
   hipStream_t capture_stream;
-  unsigned lds_cap_raised; // bit KIND: this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
+  unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
+  int step_shape;          // 1 + the ShapedSteps entry whose kernel runs this engine's one-step launches, 0 = the generic kernel
   // sgw_step_full: one captured graph per (actions, out, extras) triple
   struct FullGraph { const int8_t* actions; sgw_out out; sgw_extras ex; long long last_use; hipGraphExec_t exec; };
   std::vector<FullGraph> full_graphs;
@@ -133,6 +136,8 @@ static long pow_selfcheck_run() {
   }
   return bad;
 }
+static int engine_step_shape(const sgw_engine* e);      // (below the launch dispatch)
+
 static long pow_selfcheck() {
   static const long cached = pow_selfcheck_run();           // C++11: initialised once, thread-safe
   return cached;
@@ -209,6 +214,9 @@ int sgw_create(const sgw_spec* spec, int64_t n_envs, int64_t env_id_base, int de
   if (spec->family == SGW_FIREMAKER_EX_MA) k.view_rotates = (spec->flags & (Firemaker::F_ODIR | Firemaker::F_ODIR_TURN)) ? 1 : 0;
   memcpy(k.dim_slot, spec->dim_slot, sizeof(k.dim_slot));
   memcpy(k.metric_slot, spec->metric_slot, sizeof(k.metric_slot));
+  // the one-step kernel with this spec's output geometry compiled in, if the library has one; SGW_GENERIC_STEP keeps the generic
+  // kernel (the tests compare the two)
+  e->step_shape = getenv("SGW_GENERIC_STEP") ? 0 : engine_step_shape(e);
 
   const size_t tbytes = TABLE_BYTES;
   uint8_t host_tables[TABLE_BYTES];
@@ -270,6 +278,7 @@ int sgw_destroy(sgw_engine* e) {
 int64_t sgw_n_envs(const sgw_engine* e) { return e ? e->n_envs : 0; }
 int64_t sgw_n_pad(const sgw_engine* e) { return e ? e->n_pad : 0; }
 int sgw_state_words(const sgw_engine* e) { return e ? e->ks.words : 0; }
+int sgw_step_shape(const sgw_engine* e) { return e ? e->step_shape : 0; }
 int64_t sgw_state_bytes(const sgw_engine* e) { return e ? (int64_t)e->ks.words * e->n_pad * 8 : 0; }
 
 int sgw_set_episode_bits(sgw_engine* e, const uint8_t* bits_dev, int n_per_env, uint64_t seed) {
@@ -388,6 +397,29 @@ template <class Fn> static int with_family(const sgw_engine* e, Fn&& fn) {
   }
 }
 
+// The shaped one-step kernels (sgw_kernels.hpp StepShape): a family (state variant included) and the output geometry its kernel
+// has compiled in.  An engine whose family and spec match an entry steps with that kernel; adding a shape is one line here.
+template <class F, class SH> struct ShapedStep { using Family = F; using Shape = SH; };
+using ShapedSteps = std::tuple<
+    // island_navigation_ex, level 9, default flags (the headline): 6 x 8 board, 10 reward columns, FINAL and DEATH not enabled
+    ShapedStep<IslandPacked, StepShape<6, 8, 10, 0, 1, 2, 3, -1, 4, 5, 6, 7, 8, 9, -1>>>;
+
+// 1 + the index of the entry for family F and this spec, or 0
+template <class F, size_t I = 0> static int find_step_shape(const KSpec& k) {
+  if constexpr (I < std::tuple_size<ShapedSteps>::value) {
+    using E = std::tuple_element_t<I, ShapedSteps>;
+    if constexpr (std::is_same<typename E::Family, F>::value) { if (E::Shape::matches(k)) return (int)I + 1; }
+    return find_step_shape<F, I + 1>(k);
+  } else {
+    return 0;
+  }
+}
+
+static int engine_step_shape(const sgw_engine* e) {
+  const int s = with_family(e, [&](auto ft, int) { using F = typename decltype(ft)::type; return find_step_shape<F>(e->ks); });
+  return s > 0 ? s : 0;
+}
+
 static int launch_kind(const KArgs& a) {                      // K_STEP reads the caller's actions only
   return a.mode == MODE_RESET ? K_RESET : ((a.T == 1 && a.actions) ? K_STEP : K_ROLLOUT);
 }
@@ -443,18 +475,32 @@ template <class F, int KIND> static int plan_launch(const sgw_engine* e, KArgs& 
   return SGW_OK;
 }
 
-template <class F, int KIND> static int launch_as(sgw_engine* e, KArgs& a, hipStream_t st) {
+template <class F, int KIND, class SH = NoShape> static int launch_as(sgw_engine* e, KArgs& a, hipStream_t st) {
   LaunchPlan p;
   int rc = plan_launch<F, KIND>(e, a, p);
   if (rc) return rc;
-  // above the default dynamic-LDS cap: raised ONCE per engine and kernel kind, to the CU's 160 KiB -- a launch that needs it
+  // above the default dynamic-LDS cap: raised ONCE per engine and kernel, to the CU's 160 KiB -- a launch that needs it
   // is then never the first inside a stream capture (sgw_step_n)
-  if (p.lds_bytes > 65536 && !(e->lds_cap_raised & (1u << KIND))) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_engine<F, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    e->lds_cap_raised |= 1u << KIND;
+  constexpr unsigned bit = 1u << (KIND + (SH::ON ? 3 : 0));
+  if (p.lds_bytes > 65536 && !(e->lds_cap_raised & bit)) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_engine<F, KIND, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    e->lds_cap_raised |= bit;
   }
-  hipLaunchKernelGGL((k_engine<F, KIND>), dim3(p.blocks), dim3(p.threads), p.lds_bytes, st, SGW_HOT_ARGS(a), a);
+  hipLaunchKernelGGL((k_engine<F, KIND, SH>), dim3(p.blocks), dim3(p.threads), p.lds_bytes, st, SGW_HOT_ARGS(a), a);
   return SGW_OK;
+}
+
+// one step: the engine's shaped kernel when it has one (e->step_shape), the generic one otherwise
+template <class F, size_t I = 0> static int launch_step(sgw_engine* e, KArgs& a, hipStream_t st) {
+  if constexpr (I < std::tuple_size<ShapedSteps>::value) {
+    using E = std::tuple_element_t<I, ShapedSteps>;
+    if constexpr (std::is_same<typename E::Family, F>::value) {
+      if (e->step_shape == (int)I + 1) return launch_as<F, K_STEP, typename E::Shape>(e, a, st);
+    }
+    return launch_step<F, I + 1>(e, a, st);
+  } else {
+    return launch_as<F, K_STEP>(e, a, st);
+  }
 }
 
 static int launch(sgw_engine* e, KArgs& a, hipStream_t st) {
@@ -464,7 +510,7 @@ static int launch(sgw_engine* e, KArgs& a, hipStream_t st) {
   const int kind = launch_kind(a);
   rc = with_family(e, [&](auto ft, int) {
     using F = typename decltype(ft)::type;
-    if (kind == K_STEP) return launch_as<F, K_STEP>(e, a, st);
+    if (kind == K_STEP) return launch_step<F>(e, a, st);
     if (kind == K_ROLLOUT) return launch_as<F, K_ROLLOUT>(e, a, st);
     return launch_as<F, K_RESET>(e, a, st);
   });

@@ -81,37 +81,38 @@ struct KArgs {
 #endif
 #define SGW_KARGS_OFFSET 48      // byte offset of the KArgs block in k_engine's kernarg segment: 5 x 8 + 4 (+4 padding)
 
-// In-kernel phase stamps: compiled in ONLY by the diagnostic probe (-DSGW_STAMPS); libsgw.so carries none.
+// In-kernel phase stamps: compiled in ONLY by the diagnostic probe (-DSGW_STAMPS); libsgw.so carries none.  SGW_STAMP_SLOTS
+// stamps per wave, at the wave's global index (one-step kernel: no pipelined pairs, so that is its env-wave): slots 0-5 the
+// phases of k_engine, 6-7 real-time start / end, 8-11 the marks inside the output phase.
 #ifdef SGW_STAMPS
-#define SGW_STAMP(a, k)                                                                          \
+#define SGW_STAMP_SLOTS 16
+#define SGW_STAMP_AT(a, k, insn)                                                                 \
   do {                                                                                           \
     unsigned long long t_;                                                                       \
     __builtin_amdgcn_sched_barrier(0);                                                           \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                    \
+    asm volatile(insn " %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                        \
     __builtin_amdgcn_sched_barrier(0);                                                           \
-    if ((threadIdx.x & 63) == 0) (a).sgw_stamps[sgw_stamp_wave * 8 + (k)] = t_;                   \
+    const long long w_ = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;                \
+    if ((threadIdx.x & 63) == 0) (a).sgw_stamps[w_ * SGW_STAMP_SLOTS + (k)] = t_;                 \
   } while (0)
-#define SGW_STAMP_RT(a, k)                                                                       \
-  do {                                                                                           \
-    unsigned long long t_;                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    if ((threadIdx.x & 63) == 0) (a).sgw_stamps[sgw_stamp_wave * 8 + (k)] = t_;                   \
-  } while (0)
+#define SGW_STAMP(a, k) SGW_STAMP_AT(a, k, "s_memtime")
+#define SGW_STAMP_RT(a, k) SGW_STAMP_AT(a, k, "s_memrealtime")
 #elif defined(SGW_PHASE_PROF)
 // diagnostic LIBRARY build (tools/diag/phase_prof.py): wave cycles between the same marks, summed per wave over launches,
-// for whatever family runs -- slot k = cycles from mark k-1 to mark k
+// for whatever family runs -- slot k = cycles from mark k-1 to mark k.  Only marks 0-5 count here: the marks inside the
+// output phase (8-11, the stamp probe's) are skipped, so slot 3 still spans the whole output phase and a row stays 8 wide.
 __device__ unsigned long long g_phase_prof[4096 * 8];
 __device__ unsigned long long g_phase_last[4096];
 #define SGW_STAMP(a, k)                                                                          \
   do {                                                                                           \
-    unsigned long long t_;                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                    \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    const int w_ = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) & 4095;                   \
-    if ((threadIdx.x & 63) == 0) { if ((k) != 0) g_phase_prof[w_ * 8 + (k)] += t_ - g_phase_last[w_]; g_phase_last[w_] = t_; } \
+    if constexpr ((k) < 8) {                                                                     \
+      unsigned long long t_;                                                                     \
+      __builtin_amdgcn_sched_barrier(0);                                                         \
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
+      __builtin_amdgcn_sched_barrier(0);                                                         \
+      const int w_ = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) & 4095;                 \
+      if ((threadIdx.x & 63) == 0) { if ((k) != 0) g_phase_prof[w_ * 8 + (k)] += t_ - g_phase_last[w_]; g_phase_last[w_] = t_; } \
+    }                                                                                            \
   } while (0)
 #define SGW_STAMP_RT(a, k) do { } while (0)
 #else

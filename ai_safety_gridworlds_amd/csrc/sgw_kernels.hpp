@@ -77,6 +77,7 @@ __device__ inline void emit_stage(const typename F::State& s, const double (&r)[
       lds_write_board_row<F::NSPRITE>(l.board, HW, lane, base, cells, chars);
     }
   }
+  SGW_STAMP(a, 9);
   if (nd & LN_REWARD) {
     const StageRow row_r(l.vec_r, l.trash, lane, K);
 #pragma unroll
@@ -91,6 +92,7 @@ __device__ inline void emit_stage(const typename F::State& s, const double (&r)[
 #pragma unroll
     for (int id = 0; id < F::NMETRIC; ++id) *stage_cell(l.vec_m, l.trash, lane, M, sp.metric_slot[id]) = F::metric(s, id);
   }
+  SGW_STAMP(a, 10);
   if constexpr (SMALL) {
   if (nd & LN_ST) {
 #pragma unroll
@@ -668,9 +670,6 @@ __device__ __forceinline__ void engine_body(const KArgs& a, const long long bloc
   const long long env_id = a.env_id_base + env;
   const bool real = env < a.n_envs;
   const bool wave_live = env0 < a.n_pad;                 // the last workgroup may hold fewer than EW env-waves
-#ifdef SGW_STAMPS
-  const long long sgw_stamp_wave = wave_live ? wave_id : 0;
-#endif
 
   SGW_STAMP_RT(a, 6);
   SGW_STAMP(a, 0);
@@ -891,6 +890,7 @@ __device__ __forceinline__ void engine_body(const KArgs& a, const long long bloc
         }
         if constexpr (PIPE) { if (lane == 0) le.flag[0] = acc_any ? 1u : 0u; }
       }
+      SGW_STAMP(ae, 8);
       if (writes) {
         emit_stage<F, PIPE, !has_board_part<F>::value>(s, r, discount, ae, le, lane);
         emit_decodes_direct<F>(s, ae, env0, lane, ae.write_every != 0 ? (long long)t * ae.n_pad : 0, true, kargs_off);
@@ -917,6 +917,7 @@ __device__ __forceinline__ void engine_body(const KArgs& a, const long long bloc
       lds_wave_sync();
       if (writes) {
         emit_drain<F, false, !has_board_part<F>::value>(ae, le, env0, lane, ae.write_every != 0 ? (long long)t * ae.n_pad : 0, true, true);
+        SGW_STAMP(ae, 11);
         emit_small_direct<F>(s, discount, ae, le, env0, lane, ae.write_every != 0 ? (long long)t * ae.n_pad : 0, true);
       }
       SGW_STAMP(ae, 3);
@@ -930,7 +931,33 @@ __device__ __forceinline__ void engine_body(const KArgs& a, const long long bloc
   SGW_STAMP_RT(a, 7);
 }
 
-template <class F, int KIND>
+// ---- compile-time output geometry ("shape") of a one-step kernel ----------------------------------------------------------
+// A shaped k_engine overwrites the geometry fields of its argument copy with constants: board H x W, reward row width A * K (one
+// agent) and the universe-dimension -> column map.  Everything downstream reads them from that copy, so the compiler folds them:
+// the board row becomes HW / 16 LDS quad writes plus the agent byte, every reward cell a fixed LDS offset with no trash row, each
+// drain a fixed number of unguarded 16-byte stores per lane and the returns transpose a single pass of fixed width.  Which
+// outputs a launch asks for (`need`) stays a runtime mask.  The launcher picks a shaped kernel only when the engine's spec holds
+// exactly these values (sgw_api.hip, ShapedSteps); everything else runs the generic kernel (NoShape).
+struct NoShape { static constexpr bool ON = false; };
+template <int H_, int W_, int K_, int... SLOT>
+struct StepShape {
+  static constexpr bool ON = true;
+  static constexpr int H = H_, W = W_, HW = H_ * W_, K = K_, NSLOT = (int)sizeof...(SLOT);
+  static_assert(HW <= SGW_MAX_CELLS && K >= 1 && K <= SGW_MAX_K && NSLOT <= SGW_MAX_K, "");
+  __host__ __device__ static constexpr int slot(int u) { constexpr int8_t s[NSLOT] = {(int8_t)SLOT...}; return s[u]; }
+  __host__ static bool matches(const KSpec& k) {
+    if (k.H != H || k.W != W || k.HW != HW || k.A != 1 || k.K != K) return false;
+    for (int u = 0; u < SGW_MAX_K; ++u) if (k.dim_slot[0][u] != (u < NSLOT ? slot(u) : -1)) return false;
+    return true;
+  }
+  __device__ static void apply(KSpec& k) {
+    k.H = H; k.W = W; k.HW = HW; k.A = 1; k.K = K;
+#pragma unroll
+    for (int u = 0; u < NSLOT; ++u) k.dim_slot[0][u] = (int8_t)slot(u);
+  }
+};
+
+template <class F, int KIND, class SH = NoShape>
 __global__ SGW_OCC __launch_bounds__((wg_threads<F, KIND>())) void k_engine(uint64_t* hot_state, const uint8_t* hot_tables, const int8_t* hot_actions,
                                                                       long long hot_n_pad, long long hot_n_envs, int hot_words,
                                                                       const KArgs a_in) {
@@ -939,6 +966,11 @@ __global__ SGW_OCC __launch_bounds__((wg_threads<F, KIND>())) void k_engine(uint
   // the first global loads issue without waiting for a scalar load of the kernarg segment from memory
   KArgs a = a_in;
   a.state = hot_state; a.tables = hot_tables; a.actions = hot_actions; a.n_pad = hot_n_pad; a.n_envs = hot_n_envs; a.sp.words = hot_words;
+  if constexpr (SH::ON) {
+    // (a re-reading family would fetch the runtime geometry back from the kernarg segment)
+    static_assert(KIND == K_STEP && !step_rereads<F>::value && !F::PER_AGENT && F::NA == 1 && SH::NSLOT == F::NU, "");
+    SH::apply(a.sp);
+  }
   engine_body<F, KIND>(a, (long long)blockIdx.x, SGW_KARGS_OFFSET);
 }
 

@@ -366,6 +366,11 @@ int sgw_state_words(const sgw_engine* e);
 int sgw_get_state(sgw_engine* e, uint64_t* state_dev, void* stream);
 int sgw_set_state(sgw_engine* e, const uint64_t* state_dev, void* stream);
 
+/* Which kernel runs the engine's one-step launches (sgw_step, sgw_step_n): 0 = the generic kernel, k > 0 = the k-th kernel with
+ * the output geometry of one spec compiled in (chosen by sgw_create when family, state variant and geometry match one exactly;
+ * SGW_GENERIC_STEP set in the environment at sgw_create keeps the generic kernel).  Both compute the same bytes. */
+int sgw_step_shape(const sgw_engine* e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
 // Diagnostic build ONLY (never shipped, never timed for a quoted number): per-wave s_memtime stamps around the phases of
 // the island step kernel, to see where a launch's ~10 us go.  Build & run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DSGW_STAMPS -I. tools/diag/stamp_probe.hip -o /tmp/stamp_probe && /tmp/stamp_probe
-// It drives k_engine<IslandPacked, K_STEP> directly (same code as libsgw.so, compiled with stamps) on 65 536 envs.
-// -DSGW_ISLAND_EW=n sets the env-waves per workgroup.
+// It drives k_engine<IslandPacked, K_STEP> directly (same code as libsgw.so, compiled with stamps) on 65 536 envs, with the
+// bench's outputs and the episodic-return accumulators.  -DSGW_ISLAND_EW=n sets the env-waves per workgroup.
+//   stamp_probe [n_envs] [extra LDS bytes] [output mask] [kernel: 0 generic, 1 shaped (the level-9 shape of sgw_api.hip)]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -23,6 +24,7 @@ int main(int argc, char** argv) {
   const int NW = (int)(n / 64);
   using Fam = IslandPacked;
   constexpr int EW = env_waves<Fam, K_STEP>();
+  const int NB = (NW + EW - 1) / EW, NWL = NB * EW;      // waves launched (a dead env-wave of the last workgroup stamps too)
   const int K = 10, HW = 48, words = Fam::words(K);
   KArgs a; memset(&a, 0, sizeof(a));
   KSpec& sp = a.sp;
@@ -50,46 +52,65 @@ int main(int argc, char** argv) {
   std::vector<signed char> acts(T * n);
   unsigned x = 12345; for (auto& v : acts) { x = x * 1664525u + 1013904223u; v = (signed char)((x >> 24) % 5); }
   CK(hipMemcpy(d_act, acts.data(), T * n, hipMemcpyHostToDevice));
-  CK(hipMalloc(&d_stamps, (size_t)NW * 8 * 8)); CK(hipMalloc(&d_board, n * HW)); CK(hipMalloc(&d_reward, n * K * 8));
+  CK(hipMalloc(&d_stamps, (size_t)NWL * SGW_STAMP_SLOTS * 8)); CK(hipMalloc(&d_board, n * HW)); CK(hipMalloc(&d_reward, n * K * 8));
   CK(hipMalloc(&d_st, n)); CK(hipMalloc(&d_term, n)); CK(hipMalloc(&d_safety, n * 4)); CK(hipMalloc(&d_frame, n * 4));
   a.tables = d_tables; a.state = reinterpret_cast<uint64_t*>(d_state); a.n_pad = n; a.n_envs = n; a.mode = MODE_STEP; a.T = 1;
-  const int omask = argc > 3 ? atoi(argv[3]) : 63;      // bit0 board, 1 reward, 2 step_type, 3 term_reason, 4 safety, 5 frame
+  const int omask = argc > 3 ? atoi(argv[3]) : 127;     // bit0 board, 1 reward, 2 step_type, 3 term_reason, 4 safety, 5 frame, 6 returns
+  const bool shaped = argc > 4 && atoi(argv[4]) != 0;
+  using Shape = StepShape<6, 8, 10, 0, 1, 2, 3, -1, 4, 5, 6, 7, 8, 9, -1>;
+  if (shaped && !Shape::matches(sp)) { printf("the probe's spec does not match the shape\n"); return 1; }
   if (omask & 1) a.out.board = d_board;
   if (omask & 2) a.out.reward = d_reward;
   if (omask & 4) a.out.step_type = d_st;
   if (omask & 8) a.out.term_reason = d_term;
   if (omask & 16) a.out.safety = d_safety;
   if (omask & 32) a.out.frame = d_frame;
+  double* d_acc = nullptr;
+  if (omask & 64) {
+    CK(hipMalloc(&d_acc, (size_t)NW * SGW_ACC_PARTS * (K + 1) * 8)); CK(hipMemset(d_acc, 0, (size_t)NW * SGW_ACC_PARTS * (K + 1) * 8));
+    a.ep_acc = d_acc;
+  }
   a.sgw_stamps = d_stamps;
   a.lp = lds_plan(HW, 1, K, 9, 1, lds_need(a, false), 0); a.need = lds_need(a, false);
   const size_t lds = lds_total_bytes(HW, 1, K, 9, 1, lds_need(a, false), 0, Fam::LDS_EXTRA, EW, 1) + (argc > 2 ? atoll(argv[2]) : 0);
-  printf("n %lld, %d env-waves per workgroup, dynamic LDS %zu bytes per workgroup\n", n, EW, lds);
-  std::vector<unsigned long long> h((size_t)NW * 8);
+  printf("n %lld, %d env-waves per workgroup, dynamic LDS %zu bytes per workgroup, output mask %d, %s kernel\n", n, EW, lds, omask,
+         shaped ? "shaped" : "generic");
+  const int S = SGW_STAMP_SLOTS;
+  std::vector<unsigned long long> h((size_t)NWL * S);
   std::vector<double> starts, ends;
-  double acc[8] = {0}; int cnt = 0;
+  double acc[16] = {0}; int cnt = 0;
+  constexpr int NPH = 9;
+  const int from[NPH] = {0, 1, 2, 8, 9, 10, 11, 3, 4}, to[NPH] = {1, 2, 8, 9, 10, 11, 3, 4, 5};
+  const char* names[NPH] = {"issue loads -> state+tables arrived", "play (rules)", "returns staging", "board stage (LDS)",
+                            "reward stage (LDS)", "wave sync + board/reward drains", "small direct stores", "returns accumulation",
+                            "state stores issued"};
   for (int t = 0; t < T; ++t) {
     a.actions = d_act + t * n;
-    hipLaunchKernelGGL((k_engine<Fam, K_STEP>), dim3((NW + EW - 1) / EW), dim3(EW * 64), lds, 0, SGW_HOT_ARGS(a), a);
+    if (shaped) hipLaunchKernelGGL((k_engine<Fam, K_STEP, Shape>), dim3(NB), dim3(EW * 64), lds, 0, SGW_HOT_ARGS(a), a);
+    else hipLaunchKernelGGL((k_engine<Fam, K_STEP>), dim3(NB), dim3(EW * 64), lds, 0, SGW_HOT_ARGS(a), a);
     if (t >= 100 && t % 10 == 0) {
       CK(hipDeviceSynchronize());
       CK(hipMemcpy(h.data(), d_stamps, h.size() * 8, hipMemcpyDeviceToHost));
-      unsigned long long t0min = ~0ull, tend = 0;
-      for (int w = 0; w < NW; ++w) { t0min = std::min(t0min, h[w * 8]); tend = std::max(tend, h[w * 8 + 5]); }
-      for (int k = 1; k < 6; ++k) { double s = 0; for (int w = 0; w < NW; ++w) s += (double)(h[w * 8 + k] - h[w * 8 + k - 1]); acc[k] += s / NW; }
-      double s0 = 0; for (int w = 0; w < NW; ++w) s0 += (double)(h[w * 8] - t0min); acc[0] += s0 / NW;
-      acc[6] += (double)(tend - t0min); ++cnt;
+      // phase k: from mark from[k] to mark to[k] (marks: sgw_common.hpp SGW_STAMP_SLOTS; 8-11 inside the output phase)
+      for (int k = 0; k < NPH; ++k) {
+        double sum = 0;
+        for (int w = 0; w < NW; ++w) sum += (double)(h[(size_t)w * S + to[k]] - h[(size_t)w * S + from[k]]);
+        acc[k] += sum / NW;
+      }
+      ++cnt;
       unsigned long long r0 = ~0ull;                       // s_memrealtime: 100 MHz, one clock for all XCDs
-      for (int w = 0; w < NW; ++w) r0 = std::min(r0, h[w * 8 + 6]);
-      for (int w = 0; w < NW; ++w) { starts.push_back((double)(h[w * 8 + 6] - r0) * 0.01); ends.push_back((double)(h[w * 8 + 7] - r0) * 0.01); }
+      for (int w = 0; w < NW; ++w) r0 = std::min(r0, h[(size_t)w * S + 6]);
+      for (int w = 0; w < NW; ++w) { starts.push_back((double)(h[(size_t)w * S + 6] - r0) * 0.01); ends.push_back((double)(h[(size_t)w * S + 7] - r0) * 0.01); }
     }
   }
   CK(hipDeviceSynchronize());
-  const char* names[] = {"wave start skew (mean start - first start)", "issue loads -> state+tables arrived", "play (rules)",
-                         "return staging + output phase issued", "accumulate tail", "state stores issued", "first wave start -> last wave end"};
   printf("mean shader cycles per wave (s_memtime ticks; 2.4 GHz nominal)\n");
-  // rows 0 and 6 compare s_memtime values of DIFFERENT waves: the shader clock is per XCD, so they mean nothing across the chip --
-  // the launch-wide spread is the s_memrealtime percentile lines below
-  for (int k = 1; k < 6; ++k) printf("  %-48s %9.0f cycles  %6.2f us\n", names[k], acc[k] / cnt, acc[k] / cnt / 2400.0);
+  double out_sum = 0;
+  for (int k = 0; k < NPH; ++k) {
+    printf("  %-48s %9.0f cycles  %6.2f us\n", names[k], acc[k] / cnt, acc[k] / cnt / 2400.0);
+    if (k >= 2 && k <= 7) out_sum += acc[k] / cnt;
+  }
+  printf("  %-48s %9.0f cycles  %6.2f us\n", "output phase (returns staging .. accumulation)", out_sum, out_sum / 2400.0);
   std::sort(starts.begin(), starts.end()); std::sort(ends.begin(), ends.end());
   auto pct = [](const std::vector<double>& v, double q) { return v[(size_t)(q * (v.size() - 1))]; };
   printf("wave START after the launch's first wave (us, s_memrealtime): p10 %.2f p50 %.2f p90 %.2f p99 %.2f max %.2f\n",
