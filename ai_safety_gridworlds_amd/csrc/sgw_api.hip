@@ -876,7 +876,10 @@ int sgw_accumulate_returns(sgw_engine* e, const double* cumulative_dev, const ui
   return SGW_OK;
 }
 
-// ceil(2^32 / x) for div_recip (sgw_kernels.hpp): exact for every f <= f_max, or 0xffffffff... refused by the caller
+// ceil(2^32 / x) for div_recip (sgw_kernels.hpp): exact for every f <= f_max, or refused by the caller.  Each reciprocal is
+// checked over the quotients its users take: a block's cell index / HW (< PLANES_ENVS * HW) and a block's 4-cell item / Q
+// (< PLANES_ENVS * Q).  (The bound used to be the block's P * HW output bytes, for a per-byte expansion no kernel calls: it
+// refused e.g. 32 layers of a 17 x 17 board.)
 static bool plane_geom(int HW, int P, PlaneGeom& g) {
   auto recip = [](uint64_t x, uint64_t f_max, uint32_t& out) {
     if (x <= 1) { out = 0; return true; }
@@ -885,11 +888,10 @@ static bool plane_geom(int HW, int P, PlaneGeom& g) {
     return f_max * err < (1ull << 32);
   };
   g.HW = HW; g.P = P;
-  uint32_t a = 0, b = 0;
-  const uint64_t total = (uint64_t)PLANES_ENVS * P * HW;
-  uint32_t c = 0;
-  const bool ok = recip((uint64_t)P * HW, total, a) && recip((uint64_t)HW, total, b) && recip((uint64_t)(HW + 3) / 4, total, c);
-  g.recip_PHW = (int)a; g.recip_HW = (int)b; g.recip_Q = (int)c;
+  const uint64_t Q = (uint64_t)(HW + 3) / 4;
+  uint32_t b = 0, c = 0;
+  const bool ok = recip((uint64_t)HW, (uint64_t)PLANES_ENVS * HW, b) && recip(Q, (uint64_t)PLANES_ENVS * Q, c);
+  g.recip_HW = (int)b; g.recip_Q = (int)c;
   return ok;
 }
 static int raise_lds_cap(sgw_engine* e, const void* fn, size_t lds, unsigned bit) {

@@ -1235,27 +1235,9 @@ __global__ __launch_bounds__(WAVE) void k_derived_stats(const double* reward, co
 // coordinates come from two reciprocal multiplies, instead of dividing per byte.  (Round 2: one thread per cell, an integer
 // division each, P one-byte stores at a stride of HW.)
 constexpr int PLANES_THREADS = 256, PLANES_ENVS = 64;      // (PLANES_ENVS: the most envs a workgroup takes; 16 for boards whose staging would crowd the CU's LDS)
-struct PlaneGeom { int HW, P, recip_PHW, recip_HW, recip_Q; };       // recip_x = ceil(2^32 / x) as uint32: (f * recip) >> 32 == f / x for f < 2^20; Q = ceil(HW / 4)
+struct PlaneGeom { int HW, P, recip_HW, recip_Q; };       // recip_x = ceil(2^32 / x) as uint32: (f * recip) >> 32 == f / x for f < 64 x; Q = ceil(HW / 4)
 __device__ inline uint32_t div_recip(uint32_t f, uint32_t recip) { return recip ? (uint32_t)(((uint64_t)f * recip) >> 32) : f; }   // recip 0: x == 1
-// phase 2.  value(p, code) -> output byte
-template <class Value>
-__device__ inline void planes_expand(uint8_t* out_block, const PlaneGeom& g, int n_env, Value value) {
-  const uint32_t per_env = (uint32_t)(g.P * g.HW), total = (uint32_t)n_env * per_env;
-  for (uint32_t f0 = 16u * threadIdx.x; f0 < total; f0 += 16u * PLANES_THREADS) {
-    uint32_t e = div_recip(f0, (uint32_t)g.recip_PHW), rem = f0 - e * per_env;
-    uint32_t p = div_recip(rem, (uint32_t)g.recip_HW), c = rem - p * (uint32_t)g.HW;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int b = 0; b < 16; ++b) {
-      const uint32_t v = f0 + b < total ? (uint32_t)value((int)p, (int)e, (int)c) & 0xffu : 0u;
-      w[b >> 2] |= v << (8 * (b & 3));
-      if (++c == (uint32_t)g.HW) { c = 0; if (++p == (uint32_t)g.P) { p = 0; ++e; } }
-    }
-    if (f0 + 16u <= total) *reinterpret_cast<uint4*>(out_block + f0) = make_uint4(w[0], w[1], w[2], w[3]);
-    else for (uint32_t b = 0; f0 + b < total; ++b) out_block[f0 + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
-  }
-}
-// phase 2, the fast form: a lane takes FOUR consecutive cells of an env, fetches their codes once and writes one dword per plane
+// phase 2: a lane takes FOUR consecutive cells of an env, fetches their codes once and writes one dword per plane
 // -- consecutive lanes write consecutive dwords of a row.  When H*W is not a multiple of 4 the rows do not start on dwords: the
 // stores are then unaligned dword stores (global memory takes them; the bytes of a wave's instruction are contiguous all the
 // same) and the last, partial group of a row leaves as single bytes.  dword4(e, c, nvalid, put): put(p, the 4 output bytes)
