@@ -79,9 +79,12 @@ struct sgw_engine {
   // sgw_step_full: one captured graph per (actions, out, extras) triple
   struct FullGraph { const int8_t* actions; sgw_out out; sgw_extras ex; long long last_use; hipGraphExec_t exec; };
   std::vector<FullGraph> full_graphs;
+  // bumped by drop_graphs: a group graph (sgw_group::Graph) records its members' epochs at capture and is stale once one moved
+  unsigned long long arg_epoch;
 };
 
 static void drop_graphs(sgw_engine* e) {      // any setter that changes what a launch's arguments hold invalidates the captures
+  ++e->arg_epoch;                             // (the groups' captures too: they hold this engine's KArgs by value)
   for (auto& g : e->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   e->graphs.clear();
   for (auto& g : e->full_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -198,7 +201,7 @@ int sgw_create(const sgw_spec* spec, int64_t n_envs, int64_t env_id_base, int de
   e->n_envs = n_envs;
   e->n_pad = (n_envs + SGW_ENV_ALIGN - 1) / SGW_ENV_ALIGN * SGW_ENV_ALIGN;
   e->env_id_base = env_id_base;
-  e->ep_bits = nullptr; e->ep_bits_n = 0; e->ep_seed = 0; e->rand_stream = nullptr; e->rand_n = 0; e->rand_seed = 0; e->acc_dev = nullptr; e->rng_set = 0; e->ftable_dev = nullptr; e->ftable_n = 0; e->capture_stream = nullptr; e->graph_tick = 0; e->lds_cap_raised = 0;
+  e->ep_bits = nullptr; e->ep_bits_n = 0; e->ep_seed = 0; e->rand_stream = nullptr; e->rand_n = 0; e->rand_seed = 0; e->acc_dev = nullptr; e->rng_set = 0; e->ftable_dev = nullptr; e->ftable_n = 0; e->capture_stream = nullptr; e->graph_tick = 0; e->lds_cap_raised = 0; e->arg_epoch = 0;
 
   KSpec& k = e->ks;
   memset(&k, 0, sizeof(k));
@@ -649,7 +652,8 @@ struct sgw_group {
   std::vector<sgw_engine*> members;
   int device;
   unsigned lds_cap_raised;
-  struct Graph { std::vector<const int8_t*> actions; std::vector<sgw_out> outs; int T, write_every, accumulate, has_out; long long last_use; hipGraphExec_t exec; };
+  // epochs: the members' arg_epoch when the graph was seen; a member setter since then makes the capture stale
+  struct Graph { std::vector<const int8_t*> actions; std::vector<sgw_out> outs; std::vector<unsigned long long> epochs; int T, write_every, accumulate, has_out; long long last_use; hipGraphExec_t exec; };
   std::vector<Graph> graphs;
   long long graph_tick;
   hipStream_t capture_stream;
@@ -775,12 +779,21 @@ int sgw_group_step_n(sgw_group* g, const int8_t* const* actions_dev, int T, int 
     sgw_group::Graph gr;
     gr.actions.assign(actions_dev, actions_dev + n);
     if (outs) gr.outs.assign(outs, outs + n);
+    for (sgw_engine* e : g->members) gr.epochs.push_back(e->arg_epoch);
     gr.T = T; gr.write_every = write_every != 0; gr.accumulate = accumulate != 0; gr.has_out = outs != nullptr;
     gr.last_use = ++g->graph_tick; gr.exec = nullptr;
     g->graphs.push_back(gr);
     return group_step_launches(g, actions_dev, T, write_every, outs, accumulate, st);
   }
   hit->last_use = ++g->graph_tick;
+  bool stale = false;
+  for (size_t m = 0; m < n; ++m) stale |= hit->epochs[m] != g->members[m]->arg_epoch;
+  if (stale) {                                  // a member setter changed what the captured KArgs hold: seen anew, launch directly
+    if (hit->exec) (void)hipGraphExecDestroy(hit->exec);
+    hit->exec = nullptr;
+    for (size_t m = 0; m < n; ++m) hit->epochs[m] = g->members[m]->arg_epoch;
+    return group_step_launches(g, actions_dev, T, write_every, outs, accumulate, st);
+  }
   if (!hit->exec) {
     if (!g->capture_stream) HIP_TRY(hipStreamCreateWithFlags(&g->capture_stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamBeginCapture(g->capture_stream, hipStreamCaptureModeThreadLocal));

@@ -1,0 +1,202 @@
+"""One row per base env name (specs.ENV_FAMILIES + aintelope_savanna) for the launch-path matrix of
+tests/test_launch_paths_gpu.py: sgw_step_n (direct, capture, replay), sgw_replay, sgw_rollout, sgw_group_step_n and
+sgw_group_rollout, each compared with the C oracle.  Kwargs end episodes inside the run (small max_iterations where the family
+takes one), so auto-reset happens inside captured and replayed graphs.  tests/test_launch_paths.py (CPU) checks that every
+base env name has a row and that `tag` names the SGW_GROUP_FAMILIES member exactly where csrc/sgw_group.hpp lists one.
+
+A row: id; name, kw (make_spec); n (envs: ragged, never a multiple of 64); outs; inputs -- bits / rand: None, "array"
+(explicit per-env arrays) or "philox" (the engine's seeded stream, restated on the host for the oracle), rng: per-env PCG64
+states; oracle: "scalar" (oracle.oracle), "ma" (oracle_ma), "ima" (oracle_ima) or "sav" (oracle_sav); tag: the group member
+tag name, or None where the family / configuration is refused as a member; state_words: expected sgw_state_words (the
+packed / plain island state); calls: step_n / replay / rollout calls of T = 16 steps -- 7 for tomato_watering, tomato_crmdp
+and rocks_diamonds, which take no max_iterations: their 100-step episodes end (and auto-reset) inside the seventh call."""
+import numpy as np
+
+from ai_safety_gridworlds_amd import philox
+from ai_safety_gridworlds_amd.engine import ALL_OUTPUTS
+
+WIN = ALL_OUTPUTS + ("views",)
+SAV = ALL_OUTPUTS + ("views", "safety2")
+
+
+def _row(id, name, kw, n, tag, oracle="scalar", outs=ALL_OUTPUTS, bits=None, rand=None, rng=False, state_words=None, calls=3):
+  return dict(id=id, name=name, kw=kw, n=n, tag=tag, oracle=oracle, outs=outs, bits=bits, rand=rand, rng=rng,
+              state_words=state_words, calls=calls)
+
+
+ROWS = [
+    _row("island_ex_packed", "island_navigation_ex", dict(level=5, max_iterations=12), 1000, "TAG_ISLAND_PACKED", state_words=10),
+    _row("island_ex_plain", "island_navigation_ex", dict(level=4, max_iterations=14, MOVEMENT_REWARD={"MOVEMENT_REWARD": -0.5}),
+         1003, "TAG_ISLAND", state_words=22),
+    _row("island_ex_general", "island_navigation_ex", dict(level=6, max_iterations=13, DRINK_REWARD={"DRINK_REWARD": 2.0, "FOOD_REWARD": -1.0}),
+         999, None),
+    _row("boat_race_ex", "boat_race_ex", dict(level=1, max_iterations=11), 1001, "TAG_BOAT"),
+    _row("boat_race", "boat_race", dict(level=0, max_iterations=10, noops=True), 957, "TAG_BOAT"),
+    _row("safe_interruptibility", "safe_interruptibility", dict(level=0, max_iterations=12), 1010, "TAG_SAFEINT", bits="array"),
+    _row("safe_interruptibility_ex", "safe_interruptibility_ex", dict(level=1, max_iterations=15), 33, "TAG_SAFEINT", bits="philox"),
+    _row("firemaker_ex_ma", "firemaker_ex_ma", dict(amount_agents=3, max_iterations=14), 401, None, oracle="ma", outs=WIN, rng=True),
+    _row("island_ex_ma", "island_navigation_ex_ma", dict(level=6, map_randomization_frequency=2, map_width=11, map_height=7,
+                                                           max_iterations=13), 803, None, oracle="ima", outs=WIN, rng=True),
+    _row("island_navigation", "island_navigation", dict(level=0, max_iterations=12), 1005, "TAG_TILE"),
+    _row("distributional_shift", "distributional_shift", dict(is_testing=False), 777, "TAG_TILE", bits="array"),
+    _row("absent_supervisor", "absent_supervisor", dict(), 1011, "TAG_TILE", bits="array"),
+    _row("side_effects_sokoban", "side_effects_sokoban", dict(level=0, noops=True), 1015, "TAG_SOKOBAN"),
+    _row("conveyor_belt", "conveyor_belt", dict(variant="sushi", max_iterations=12), 1017, "TAG_CONVEYOR"),
+    _row("conveyor_belt_ex", "conveyor_belt_ex", dict(variant="sushi_goal2", noops=True, max_iterations=13), 49, "TAG_CONVEYOR"),
+    _row("tomato_watering", "tomato_watering", dict(), 1019, "TAG_TOMATO", rand="array", calls=7),
+    _row("tomato_crmdp", "tomato_crmdp", dict(), 1021, "TAG_TOMATO", rand="philox", calls=7),
+    _row("friend_foe", "friend_foe", dict(bandit_type="friend"), 1023, "TAG_FRIEND_FOE", rand="array"),
+    _row("whisky_gold", "whisky_gold", dict(human_player=False, whisky_exploration=0.7), 1025, "TAG_WHISKY", rand="array"),
+    _row("rocks_diamonds", "rocks_diamonds", dict(level=1), 1027, "TAG_ROCKS", calls=7),
+    _row("aintelope_savanna", "aintelope_savanna",
+         dict(amount_agents=2, amount_predators=2, amount_water_tiles=2, amount_gold_deposits=2, amount_silver_deposits=1,
+              amount_small_food_patches=1, amount_drink_holes=1, amount_small_drink_holes=1, sustainability_challenge=True,
+              penalise_oversatiation=True, max_iterations=14, observation_radius=[2, 2, 2, 2]), 601, None, oracle="sav", outs=SAV,
+         rng=True),
+]
+BY_ID = {r["id"]: r for r in ROWS}
+
+# groups of member rows: every member tag at least once, one group of 4 (member index 3, hot_fb3), one member under 64 envs
+GROUPS = [
+    ("g4_scalar", ["island_ex_packed", "boat_race_ex", "safe_interruptibility_ex", "tomato_watering"]),
+    ("g4_tiles", ["island_ex_plain", "distributional_shift", "side_effects_sokoban", "conveyor_belt_ex"]),
+    ("g4_rand", ["friend_foe", "whisky_gold", "rocks_diamonds", "safe_interruptibility"]),
+    ("g3_mixed", ["absent_supervisor", "tomato_crmdp", "conveyor_belt"]),
+    ("g2_pair", ["boat_race", "island_navigation"]),
+]
+
+N_BITS, N_RAND = 64, 4096
+PCG_SEED = 321
+
+
+def philox_uniforms(seed, env_ids, n):
+  """The engine's in-play uniforms with no stream set (sgw_common.hpp next_uniform): draw k of an env is word pair k & 1 of
+  Philox(block k >> 1, TAG_EPISODE, 1, env id >> 32; key seed, env id).  float64 [len(env_ids), n]."""
+  env_ids = np.asarray(env_ids, dtype=np.uint64)[:, None]
+  blocks = np.arange((n + 1) // 2, dtype=np.uint64)[None, :]
+  x0, x1, x2, x3 = philox.philox4x32_10(blocks, philox.TAG_EPISODE, 1, env_ids >> np.uint64(32), seed, env_ids)
+  u0 = ((x0.astype(np.uint64) << np.uint64(21)) | (x1.astype(np.uint64) >> np.uint64(11))).astype(np.float64) * 2.0 ** -53
+  u1 = ((x2.astype(np.uint64) << np.uint64(21)) | (x3.astype(np.uint64) >> np.uint64(11))).astype(np.float64) * 2.0 ** -53
+  return np.stack([u0, u1], axis=2).reshape(len(env_ids), -1)[:, :n]
+
+
+def inputs(row, spec, seed):
+  """Host arrays for the row's external inputs: dict(bits=, bits_seed=, rand=, rand_seed=, rng=), with what the oracle reads
+  (bits_oracle / rand_oracle) -- the explicit arrays themselves, or the engine's seeded Philox streams restated."""
+  E, rs = row["n"], np.random.default_rng(seed)
+  ids = np.arange(E)
+  d = dict(bits=None, bits_seed=0, rand=None, rand_seed=0, rng=None, bits_oracle=None, rand_oracle=None)
+  if row["bits"] == "array":
+    d["bits"] = d["bits_oracle"] = rs.integers(0, 2, (E, N_BITS)).astype(np.uint8)
+  elif row["bits"] == "philox":                          # should_interrupt = episode_uniform(seed, id, episode) <= probability
+    d["bits_seed"] = 1000 + seed
+    p = spec.config["interruption_probability"]
+    d["bits_oracle"] = (philox.episode_uniform(d["bits_seed"], ids[:, None], np.arange(N_BITS)[None, :]) <= p).astype(np.uint8)
+  if row["rand"] == "array":
+    d["rand"] = d["rand_oracle"] = rs.random((E, N_RAND))
+  elif row["rand"] == "philox":
+    d["rand_seed"] = 2000 + seed
+    d["rand_oracle"] = philox_uniforms(d["rand_seed"], ids, N_RAND)
+  if row["rng"]:
+    from oracle import oracle_ma as OM
+    d["rng"] = np.stack([OM.rng_state_words(PCG_SEED + seed + e) for e in range(E)])
+  return d
+
+
+def run_oracle(row, host_actions, inp, nthreads=16):
+  """host_actions: int8 [T, E(, A)] (the device stream copied back) -> the oracle's arrays [E, T + 1, ...]."""
+  acts = np.ascontiguousarray(np.moveaxis(host_actions, 0, 1))
+  if row["oracle"] == "scalar":
+    from oracle import oracle as O
+    return O.run_streams(O.make_config(row["name"], **row["kw"]), acts, interrupt_bits=inp["bits_oracle"], nthreads=nthreads,
+                         rand_stream=inp["rand_oracle"])
+  from oracle import oracle_ima as OI, oracle_ma as OM, oracle_sav as OS
+  Or = {"ma": OM, "ima": OI, "sav": OS}[row["oracle"]]
+  return Or.run_streams(Or.make_config(**row["kw"]), acts, inp["rng"], nthreads=nthreads)
+
+
+def resets(row):
+  """Resets before the first step: the island_navigation_ex_ma / aintelope_savanna oracles record two (the reference's
+  environment resets once when it is built and once more when the episode starts; map randomisation draws at both)."""
+  return 2 if row["oracle"] in ("ima", "sav") else 1
+
+
+FIREMAKER_METRICS = [p + "Visits_" + a for p in ("External", "Internal", "Workshop", "Fire", "StopButton") for a in "12S"] + \
+    ["StopButtonPressCountdown"]
+SCALAR_FIELDS = ("step_type", "reward", "cumulative", "discount", "term_reason", "actual_action", "frame", "hidden", "board")
+
+
+def _same(g, w):
+  return bool(((g == w) | ((g != g) & (w != w))).all())             # NaN == NaN (metrics)
+
+
+def oracle_mismatches(row, spec, got, want, s0, views=None):
+  """got: {field: [E, S, ...] numpy} engine outputs of steps s0 .. s0 + S - 1 (step 0 = the (last) reset).  Returns the names of the
+  fields that differ from the oracle (empty: equal).  views: list over agents of [E, S, h, w] windows (split_views).  The
+  multi-agent families are compared on every output the oracle records: term_reason 255 -> -1, per-agent slots for firemaker,
+  the present agents' columns [:, :, :A] for island_navigation_ex_ma / aintelope_savanna."""
+  S = next(iter(got.values())).shape[1]
+  sl = slice(s0, s0 + S)
+  bad = []
+  if row["oracle"] == "scalar":
+    for f in SCALAR_FIELDS + (("metrics",) if spec.M else ()) + (("safety",) if row["name"] == "island_navigation_ex" else ()):
+      w, g = want[f][:, sl], got[f]
+      if f == "term_reason":
+        g = g.astype(np.int16); g[g == 255] = -1
+      if f == "metrics":
+        g = g[..., :spec.M]
+      if not _same(g.reshape(w.shape), w):
+        bad.append(f)
+    return bad
+  tr = got["term_reason"].astype(np.int16); tr[tr == 255] = -1
+  fl = got["agent_flags"]
+  if row["oracle"] == "ma":                                          # firemaker: per-agent slots
+    slots = list(getattr(spec, "agent_slots", range(spec.A)))
+    E = got["board"].shape[0]
+    pairs = [("board", got["board"].reshape(want["board"][:, sl].shape), want["board"][:, sl]),
+             ("frame", got["frame"], want["frame"][:, sl]), ("discount", got["discount"], want["discount"][:, sl]),
+             ("term_reason", tr, want["term_reason"][:, sl, 0]),
+             ("agent_pos", got["agent_pos"].reshape(E, S, spec.A, 2)[:, :, slots], want["pos"][:, sl][:, :, slots]),
+             ("action_direction", ((fl >> 1) & 3)[:, :, slots], want["action_direction"][:, sl][:, :, slots]),
+             ("observation_direction", ((fl >> 3) & 3)[:, :, slots], want["observation_direction"][:, sl][:, :, slots])]
+    pairs += [(f, got[f][:, :, slots], want[f][:, sl][:, :, slots]) for f in ("step_type", "reward", "cumulative")]
+    assert list(spec.metric_names) == FIREMAKER_METRICS, "the row's metric columns are the oracle's 16"
+    pairs.append(("metrics", got["metrics"], want["metrics"][:, sl]))
+    if views is not None:
+      pairs += [("views[%d]" % q, views[q], want["view_worker"][:, sl, q] if q < 2 else want["view_supervisor"][:, sl]) for q in slots]
+    return [f for f, g, w in pairs if not _same(g, w)]
+  E, A = got["board"].shape[0], want["step_type"].shape[2]           # island_navigation_ex_ma / aintelope_savanna
+  sl = slice(s0 + 1, s0 + 1 + S)                                     # (the oracle's record starts with two resets)
+  pairs = [("board", got["board"].reshape(want["board"][:, sl].shape), want["board"][:, sl]),
+           ("step_type", got["step_type"][:, :, :A], want["step_type"][:, sl]),
+           ("frame", got["frame"], want["frame"][:, sl]), ("discount", got["discount"], want["discount"][:, sl]),
+           ("metrics", got["metrics"], want["metrics"][:, sl]),
+           ("term_reason", tr[:, :, :A], want["term_reason"][:, sl]),
+           ("safety", got["safety"][:, :, :A], want["safety"][:, sl]),
+           ("agent_pos", got["agent_pos"].reshape(E, S, 2, 2)[:, :, :A], want["pos"][:, sl]),
+           ("action_direction", ((fl >> 1) & 3)[:, :, :A], want["action_direction"][:, sl]),
+           ("observation_direction", ((fl >> 3) & 3)[:, :, :A], want["observation_direction"][:, sl])]
+  pairs += [(f, got[f].reshape(E, S, 2, spec.K)[:, :, :A], want[f][:, sl]) for f in ("reward", "cumulative")]
+  if "safety2" in want:
+    pairs.append(("safety2", got["safety2"][:, :, :A], want["safety2"][:, sl]))
+  if views is not None:
+    pairs.append(("views", np.stack(views, axis=2)[:, :, :A], want["view"][:, sl]))
+  return [f for f, g, w in pairs if not _same(g, w)]
+
+
+def rng_mismatch(row, state, want, s):
+  """The per-env PCG64 words of an engine state [words, E] (int64) after s steps == the oracle's generator position."""
+  st = state.view(np.uint64)
+  off = resets(row) - 1
+  return not np.array_equal(np.stack([st[3], st[4], st[5], st[6]], axis=1), want["rng"][:, s + off])
+
+
+def finished_returns(step_type, cumulative):
+  """step_type [E, S, A], cumulative [E, S, A*K] of steps 1 .. S-1 after a reset at step 0 -> float64 [A*K + 1]: the summed
+  return vectors of the episodes that finished, and their count (the step at which every agent is done; read_returns)."""
+  done = (step_type >= 2).all(axis=2)
+  last = done[:, 1:] & ~done[:, :-1]
+  acc = np.zeros(cumulative.shape[2] + 1)
+  acc[:-1] = (cumulative[:, 1:] * last[..., None]).sum(axis=(0, 1))
+  acc[-1] = last.sum()
+  return acc

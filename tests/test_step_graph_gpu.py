@@ -37,9 +37,11 @@ def test_step_n_graph_replay_equals_single_steps(name, kw, side):
       buf.copy_(all_acts[c * T:(c + 1) * T])
       got = {k: v.clone() for k, v in a.step_n(buf, accumulate=True).items()}
       if c == 3 and name == "safe_interruptibility":
-        a.set_episode_bits(None, seed=5)        # same values: drops the captures, the next call launches directly again
+        a.set_episode_bits(None, seed=9)        # a new seed: drops the captures, the next call launches directly again
     ra = a.read_returns().clone()
   for t in range(T * calls):
+    if t == 4 * T and name == "safe_interruptibility":
+      b.set_episode_bits(None, seed=9)          # the same seed change at the same step
     want = b.step_n(all_acts[t:t + 1], accumulate=True)
   rb = b.read_returns()
   torch.cuda.synchronize()
