@@ -27,6 +27,7 @@
 #include "sgw_whisky.hpp"
 #include "sgw_group.hpp"
 #include "sgw_savanna_layers.hpp"
+#include "sgw_coords.hpp"
 
 using namespace sgw;
 
@@ -1115,6 +1116,61 @@ int sgw_agent_layer_views(sgw_engine* e, const uint8_t* layers_dev, const uint8_
                      agent_flags_dev, e->n_envs, v, layer_chars_dev, n_layers, outside_chr, out_dev, lds_per_wave);
   HIP_TRY(hipGetLastError());
   return SGW_OK;
+}
+
+// sgw_layer_coords / sgw_agent_layer_coords: the lane split and the reciprocals of k_plane_coords (sgw_coords.hpp) for planes of at most
+// max_cells cells, and the launch.  Plain launches on the caller's stream: nothing is allocated, nothing of the engine changes.
+static int coords_launch(sgw_engine* e, bool rel, const uint8_t* planes, long long items, CoordGeom& g, int max_cells, int32_t* counts,
+                         int16_t* coords, void* stream, const char* who) {
+  if (((uintptr_t)counts | (uintptr_t)coords) & 3) return fail(SGW_ERR_ARG, "%s: counts and coords must be 4-byte aligned (a coordinate pair is one store)", who);
+  if (items > 0x7fffffffLL) return fail(SGW_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 planes", who);
+  for (int a = 0; a < g.A; ++a) {
+    if (g.cells[a] > 32767) return fail(SGW_ERR_UNSUPPORTED, "%s: a plane has more cells than an int16 coordinate holds", who);
+    const uint32_t w = (uint32_t)(g.W[a] > 0 ? g.W[a] : 1);
+    g.recip_W[a] = w == 1 ? 0 : (int)(uint32_t)(((1ull << 32) + w - 1) / w);      // exact for every cell index: cells * W < 2^32
+  }
+  const int need = (max_cells + 3 + 3) / 4;             // dwords a plane touches at the worst alignment
+  g.seg_shift = 0;
+  while ((1 << g.seg_shift) < need && g.seg_shift < 6) ++g.seg_shift;
+  g.n_pass = (need + (1 << g.seg_shift) - 1) >> g.seg_shift;
+  if (items <= 0 || max_cells <= 0) return SGW_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  const long long per_wave = WAVE >> g.seg_shift, waves = (items + per_wave - 1) / per_wave;
+  const unsigned blocks = (unsigned)((waves + 3) / 4 < 8192 ? (waves + 3) / 4 : 8192);      // 4 waves per workgroup; each wave walks its planes
+  if (rel) hipLaunchKernelGGL(k_plane_coords<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, planes, (unsigned)items, g, counts, coords);
+  else hipLaunchKernelGGL(k_plane_coords<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, planes, (unsigned)items, g, counts, coords);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+int sgw_layer_coords(sgw_engine* e, const uint8_t* layers_dev, int n_layers, int cap, int32_t* counts_dev, int16_t* coords_dev,
+                     void* stream) {
+  if (!e || !layers_dev || !counts_dev || !coords_dev || n_layers < 1 || n_layers > 32 || cap < 1)
+    return fail(SGW_ERR_ARG, "sgw_layer_coords: bad argument (pointers, n_layers in 1..32, cap >= 1)");
+  CoordGeom g; memset(&g, 0, sizeof(g));
+  g.L = n_layers; g.A = 1; g.cap = cap;
+  g.cells[0] = e->ks.HW; g.W[0] = e->ks.W; g.own[0] = -1;
+  g.row_bytes = (long long)n_layers * e->ks.HW;
+  return coords_launch(e, false, layers_dev, e->n_envs * n_layers, g, e->ks.HW, counts_dev, coords_dev, stream, "sgw_layer_coords");
+}
+
+int sgw_agent_layer_coords(sgw_engine* e, const uint8_t* views_dev, int n_layers, const int32_t* agent_layer, int cap,
+                           int32_t* counts_dev, int16_t* coords_dev, void* stream) {
+  if (!e || !views_dev || !agent_layer || !counts_dev || !coords_dev || n_layers < 1 || n_layers > 32 || cap < 1)
+    return fail(SGW_ERR_ARG, "sgw_agent_layer_coords: bad argument (pointers, n_layers in 1..32, cap >= 1)");
+  const ViewSpec v = make_viewspec(e);
+  if (v.total <= 0) return fail(SGW_ERR_UNSUPPORTED, "sgw_agent_layer_coords: the spec defines no agent views");
+  CoordGeom g; memset(&g, 0, sizeof(g));
+  g.L = n_layers; g.A = v.A; g.cap = cap;
+  int max_cells = 0;
+  for (int a = 0; a < v.A; ++a) {
+    if (agent_layer[a] >= n_layers) return fail(SGW_ERR_ARG, "sgw_agent_layer_coords: agent_layer out of range");
+    g.cells[a] = v.vh[a] * v.vw[a]; g.W[a] = v.vw[a]; g.off[a] = v.off[a] * n_layers;
+    g.own[a] = agent_layer[a] < 0 ? -1 : agent_layer[a];
+    max_cells = g.cells[a] > max_cells ? g.cells[a] : max_cells;
+  }
+  g.row_bytes = (long long)v.total * n_layers;
+  return coords_launch(e, true, views_dev, e->n_envs * v.A * n_layers, g, max_cells, counts_dev, coords_dev, stream, "sgw_agent_layer_coords");
 }
 
 int sgw_track_performance(sgw_engine* e, const double* perf_dev, int n_cols, const uint8_t* step_type_dev, double* last_dev,

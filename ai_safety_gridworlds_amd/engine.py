@@ -388,6 +388,87 @@ class BatchedEngine(object):
       off += L * h * w
     return res
 
+  def _coords_buffers(self, what, lead, cap, out):
+    """(counts int32 lead, coords int16 lead + (cap, 2)) on this engine's device: the caller's `out` pair checked, or fresh zeros."""
+    if out is None:
+      return (torch.zeros(lead, dtype=torch.int32, device=self.device),
+              torch.zeros(lead + (cap, 2), dtype=torch.int16, device=self.device))
+    counts, coords = out
+    for t, dt, shp in ((counts, torch.int32, lead), (coords, torch.int16, lead + (cap, 2))):
+      if not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
+        raise N.SgwError("%s: out must be (int32 %s, int16 %s) contiguous tensors on %s" % (what, list(lead), list(lead + (cap, 2)), self.device))
+    return counts, coords
+
+  def layer_coords(self, layers=None, cap=None, out=None):
+    """Object coordinates of every observation layer (info_observation_coordinates, safety_game_mo.py:422-457): (counts int32
+    [N, L], coords int16 [N, L, cap, 2]); coords[n, l, :min(counts[n, l], cap)] are the (row, col) of layer l's set cells in
+    np.argwhere order.  counts is the true number of set cells even above `cap`; the entries past it are NOT written by the launch
+    (zeros in a fresh pair, the caller's bytes in `out`).  layers: uint8 [N, L, H, W] on the device (None: observe_layers());
+    cap=None: H*W, which is lossless; out: a (counts, coords) pair to write into."""
+    sp = self.spec
+    if layers is None:
+      layers = self.observe_layers()
+    HW = sp.H * sp.W
+    if (not torch.is_tensor(layers) or layers.device != self.device or layers.dtype != torch.uint8 or layers.dim() < 2
+        or layers.shape[0] != self.n_envs or layers[0].numel() % HW):
+      raise N.SgwError("layer_coords: layers must be a uint8 [N, L, H, W] tensor on %s (there is no CPU path)" % (self.device,))
+    layers = layers.contiguous()
+    L = layers[0].numel() // HW
+    cap = HW if cap is None else int(cap)
+    counts, coords = self._coords_buffers("layer_coords", (self.n_envs, L), cap, out)
+    N.check(self._lib.sgw_layer_coords(self._h, layers.data_ptr(), L, cap, counts.data_ptr(), coords.data_ptr(), self._stream()),
+            "sgw_layer_coords")
+    return counts, coords
+
+  def agent_layer_index(self):
+    """Per agent column of the library's layout: the index of the agent's own character in spec.layer_chars (-1: none)."""
+    sp = self.spec
+    chars = list(getattr(sp, "agent_chars", ()))
+    idx = [-1] * N.MAX_AGENTS
+    for c, q in zip(chars, getattr(sp, "agent_slots", range(len(chars)))):
+      idx[q] = sp.layer_chars.index(c) if c in sp.layer_chars else -1
+    return idx
+
+  def agent_layer_coords(self, agent_layer_views=None, cap=None, out=None):
+    """Object coordinates inside each agent's window, relative to the agent (info_agent_observation_coordinates,
+    safety_game_moma.py:528-580): list over agents of (counts int32 [N, L], coords int16 [N, L, cap, 2]), views into
+    [N, A, L(, cap, 2)] buffers.  coords[n, l, :min(counts[n, l], cap)] are (x - ax, y - ay), x first, of layer l's set cells in
+    the agent's window in np.argwhere order, (ay, ax) being the first set cell of the agent's own layer there; counts are -1 on
+    every layer of an agent that is not in its own layers (the wrappers' `[]`) and nothing is written for it.
+    agent_layer_views: what agent_layer_views() returned -- the list of views of ONE [N, L * view_bytes] buffer, or that buffer
+    (None: computed now); cap=None: the largest window's cell count; out: a (counts [N, A, L], coords [N, A, L, cap, 2]) pair."""
+    sp = self.spec
+    shapes = list(getattr(sp, "view_shapes", None) or ())
+    if agent_layer_views is None:
+      agent_layer_views = self.agent_layer_views()
+    vb = _view_bytes(sp)
+    if vb == 0:
+      raise N.SgwError("agent_layer_coords: the spec defines no agent views")
+    if torch.is_tensor(agent_layer_views):
+      t = agent_layer_views
+      if t.device != self.device or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != self.n_envs or t.shape[1] % vb or not t.is_contiguous():
+        raise N.SgwError("agent_layer_coords: the buffer must be a contiguous uint8 [N, L * view_bytes] tensor on %s (there is no CPU path)" % (self.device,))
+      L, ptr = t.shape[1] // vb, t.data_ptr()
+    else:                                       # the list must be the views of one [N, L * view_bytes] buffer, agent-major
+      wins = list(agent_layer_views)
+      L, ptr, off = (int(wins[0].shape[1]) if wins and wins[0].dim() == 4 else 0), None, 0
+      ok = len(wins) == len(shapes) and L > 0
+      for t, (h, w) in zip(wins, shapes) if ok else ():
+        ok = ok and t.device == self.device and t.dtype == torch.uint8 and tuple(t.shape) == (self.n_envs, L, h, w)
+        if ok and h * w:
+          ptr = t.data_ptr() - off if ptr is None else ptr
+          ok = t.data_ptr() == ptr + off and (self.n_envs == 1 or t.stride(0) == vb * L) and t[0].is_contiguous()
+        off += L * h * w
+      if not ok or ptr is None:
+        raise N.SgwError("agent_layer_coords: needs the uint8 windows agent_layer_views() returned (views of one [N, L * view_bytes] "
+                         "buffer on %s; there is no CPU path)" % (self.device,))
+    cap = max(h * w for (h, w) in shapes) if cap is None else int(cap)
+    counts, coords = self._coords_buffers("agent_layer_coords", (self.n_envs, sp.A, L), cap, out)
+    idx = (C.c_int32 * N.MAX_AGENTS)(*self.agent_layer_index())
+    N.check(self._lib.sgw_agent_layer_coords(self._h, ptr, L, idx, cap, counts.data_ptr(), coords.data_ptr(), self._stream()),
+            "sgw_agent_layer_coords")
+    return [(counts[:, a], coords[:, a]) for a in range(len(shapes))]
+
   def observe(self, board=None, rgb=True, layer_chars=None):
     """RGB uint8 [N, 3, H, W] and/or occluded layers uint8 [N, L, H, W] of a rendered ascii board."""
     if board is None:

@@ -415,15 +415,25 @@ class GridworldVectorEnv(object):
   uint8 [N, L, H, W] (unoccluded, `layers_order`), "cumulative_reward", "average_reward", "gini_index",
   "cumulative_gini_index", "mo_variance", "cumulative_mo_variance", "average_mo_variance", "metrics", "safety",
   "last_performance" / "performance_sum" / "episodes" -- produced by ONE library call per step (sgw_step_full: step kernel +
-  RGB + layers + derived statistics + performance bookkeeping chained in C, replayed as one hipGraph)."""
+  RGB + layers + derived statistics + performance bookkeeping chained in C, replayed as one hipGraph).
+
+  object_coordinates=True (with full_info=True): info also carries the reference's info_observation_coordinates as tensors, one
+  more launch per step (sgw_layer_coords over that step's "layers"): "coordinates" int16 [N, L, cap, 2], the (row, col) of every
+  layer's set cells in np.argwhere order, and "coordinates_count" int32 [N, L], how many of them there are (the entries past the
+  count are not written: they keep what an earlier step left there); layer order = `layers_order`; coordinates_cap=None: H*W, which is lossless."""
 
   FULL_OUTPUTS = ("board", "obs_board", "reward", "cumulative", "step_type", "term_reason", "hidden", "frame", "metrics", "safety",
                   "discount", "actual_action")
 
   def __init__(self, env_name, num_envs, device="cuda:0", env_id_base=0,
                outputs=("board", "obs_board", "reward", "cumulative", "step_type", "term_reason", "hidden"), full_info=False,
-               replay_graph=False, **kwargs):
+               replay_graph=False, object_coordinates=False, coordinates_cap=None, **kwargs):
     self._full = bool(full_info)
+    self._coords = bool(object_coordinates)
+    self._coords_cap = coordinates_cap
+    self._coords_out = None
+    if self._coords and not self._full:
+      raise ValueError("object_coordinates=True needs full_info=True (the coordinates are computed from the step's layers)")
     self._replay = bool(replay_graph)       # full_info: one hipGraph launch per step (less host time, more GPU time: sgw_extras.replay)
     if self._full:
       outputs = tuple(dict.fromkeys(tuple(outputs) + self.FULL_OUTPUTS))
@@ -474,6 +484,8 @@ class GridworldVectorEnv(object):
     o = self._env.engine.step_full(actions, rgb=True, layers=hasattr(self.spec_, "drape_chars"), stats=not self.spec_.scalar, performance=True,
                                    replay=self._replay)
     self._env._last = o
+    if self._coords:                         # one more launch into persistent buffers (the launch writes the lists only)
+      self._coords_out = self._env.engine.layer_coords(layers=o.get("layers"), cap=self._coords_cap, out=self._coords_out)
     if self._info is None or self._info["_for"] is not o["step_type"]:
       st = o["step_type"].reshape(self.num_envs, -1)[:, 0]
       info = {"step_type": st, "term_reason": o["term_reason"], "board": o["board"], "cumulative": o["cumulative"], "hidden": o["hidden"],
@@ -484,6 +496,8 @@ class GridworldVectorEnv(object):
       for k in ("gini_index", "cumulative_gini_index", "mo_variance", "cumulative_mo_variance", "average_mo_variance", "average_reward"):
         if k in o:
           info[k] = o[k]
+      if self._coords:
+        info["coordinates_count"], info["coordinates"] = self._coords_out
       self._info = {"_for": o["step_type"], "info": info, "done": o["done"], "obs": o["obs_board"].unsqueeze(1),
                     "reward": o["reward"] if not self.spec_.scalar else o["reward"].reshape(-1)}
     c = self._info

@@ -16,7 +16,14 @@ helpers/gridworld_zoo_parallel_env.py:429-615) returns for it:
                      "observation_direction" / "action_direction" uint8 [N] (Directions LEFT=0 RIGHT=1 UP=2 DOWN=3);
                      with layers_in_observation=True also the wrapper's layer cubes as tensors (zoo.py:296-316, 337-359):
                      "info_observation_layers_cube" uint8 [N, L, H, W] (shared) and "info_agent_observation_layers_cube"
-                     uint8 [N, L, h_a, w_a], both in `layers_order` = the sorted layer characters
+                     uint8 [N, L, h_a, w_a], both in `layers_order` = the sorted layer characters;
+                     with object_coordinates=True also the wrapper's coordinate lists as padded tensors (two more launches,
+                     sgw_layer_coords / sgw_agent_layer_coords): "info_observation_coordinates" int16 [N, L, cap, 2] = (row, col)
+                     of every layer's set cells in np.argwhere order with "info_observation_coordinates_count" int32 [N, L]
+                     (shared), and "info_agent_observation_coordinates" int16 [N, L, cap_a, 2] = (x - ax, y - ay) inside the
+                     agent's window with "info_agent_observation_coordinates_count" int32 [N, L] (-1 on every layer: the agent is
+                     not in its own layers, the wrapper's []); entries past a count are not written (they keep what an earlier step left there);
+                     coordinates_cap=None: H*W / the largest window's cells, which is lossless
 A finished env auto-resets at its next round exactly like the reference adapter (the round's actions are discarded); agents of
 the per-agent families that are already LAST/DEAD can be given -1 ("not in the dict").  One round = ONE kernel launch: the
 step (shuffled sequential plays, fire spread, rewards, auto-reset) writes the agent windows too (sgw_out.views / obs_views;
@@ -29,6 +36,7 @@ from .. import _native as N
 from ..engine import fused_views
 from ..environments import BatchedSafetyEnvironment
 from ..specs import make_spec
+from .gridworld_zoo_parallel_env import INFO_AGENT_OBSERVATION_COORDINATES, INFO_OBSERVATION_COORDINATES
 
 OUTS = ("board", "reward", "cumulative", "step_type", "term_reason", "discount", "metrics", "agent_pos", "agent_flags", "done")
 
@@ -37,7 +45,7 @@ class GridworldZooVectorEnv(object):
   metadata = {"name": "ai_safety_gridworlds_amd_vector"}
 
   def __init__(self, env_name, num_envs, ascii_observation_format=True, layers_in_observation=False, seed=None, device="cuda:0",
-               env_id_base=0, **kwargs):
+               env_id_base=0, object_coordinates=False, coordinates_cap=None, **kwargs):
     self._fused = fused_views(make_spec(env_name, **kwargs))
     self._ascii = bool(ascii_observation_format)
     cfg0 = getattr(make_spec(env_name, **kwargs), "config", None) or {}
@@ -57,6 +65,15 @@ class GridworldZooVectorEnv(object):
     self.agent_name_mapping = dict(zip(self.possible_agents, sp.agent_chars))
     self._k = {a: len(sp.agent_dim_names[c]) for a, c in self.agent_name_mapping.items()}
     self._layers = bool(layers_in_observation)
+    self._coords = bool(object_coordinates)
+    if self._coords:                                           # persistent (count, list) buffers, zeroed once: a launch writes the lists only
+      n, L = int(num_envs), len(sp.layer_chars)
+      cap = sp.H * sp.W if coordinates_cap is None else int(coordinates_cap)
+      cap_a = max(h * w for (h, w) in sp.view_shapes) if coordinates_cap is None else int(coordinates_cap)
+      self._coords_out = (torch.zeros((n, L), dtype=torch.int32, device=self.device),
+                          torch.zeros((n, L, cap, 2), dtype=torch.int16, device=self.device))
+      self._agent_coords_out = (torch.zeros((n, sp.A, L), dtype=torch.int32, device=self.device),
+                                torch.zeros((n, sp.A, L, cap_a, 2), dtype=torch.int16, device=self.device))
     self.layers_order = list(sp.layer_chars)                   # get_layers_order(...) of the reference: sorted layer keys
     self._vm = torch.tensor([sp.native.value_map[i] for i in range(128)], dtype=torch.float32, device=self.device)
     self._acts = torch.zeros((self.num_envs, sp.A), dtype=torch.int8, device=self.device)
@@ -123,9 +140,16 @@ class GridworldZooVectorEnv(object):
     obs, infos = dict(obs), {a: dict(d) for a, d in infos.items()}
     if not self._ascii and not self._fused:
       obs = {a: self._vm[v.long()] for a, v in obs.items()}
-    if self._layers:                                            # two more launches, tensors stay on the device
+    if self._layers or self._coords:                            # two more launches, tensors stay on the device
       cube = eng.observe_layers()
       agent_cubes = eng.agent_layer_views(layers=cube)
+    if self._coords:                                            # and two for the coordinate lists, into persistent buffers
+      eng.layer_coords(layers=cube, cap=self._coords_out[1].shape[2], out=self._coords_out)
+      per_agent = eng.agent_layer_coords(agent_cubes, cap=self._agent_coords_out[1].shape[3], out=self._agent_coords_out)
+      for i, a in enumerate(self.possible_agents):
+        infos[a][INFO_OBSERVATION_COORDINATES + "_count"], infos[a][INFO_OBSERVATION_COORDINATES] = self._coords_out
+        infos[a][INFO_AGENT_OBSERVATION_COORDINATES + "_count"], infos[a][INFO_AGENT_OBSERVATION_COORDINATES] = per_agent[self._slots[i]]
+    if self._layers:
       for i, a in enumerate(self.possible_agents):
         infos[a]["info_observation_layers_order"] = self.layers_order
         infos[a]["info_observation_layers_cube"] = cube

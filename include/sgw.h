@@ -360,6 +360,25 @@ int sgw_agent_views(sgw_engine* e, const uint8_t* board_dev, const uint8_t* agen
 int sgw_agent_layer_views(sgw_engine* e, const uint8_t* layers_dev, const uint8_t* agent_pos_dev, const uint8_t* agent_flags_dev,
                           const uint8_t* layer_chars_dev, int n_layers, uint8_t outside_chr, uint8_t* out_dev, void* stream);
 
+/* Object coordinates (object_coordinates_in_observation=True, the wrappers' default): the set cells of byte planes as padded
+ * lists, one launch for every env.  counts are the TRUE numbers of set cells (also when they exceed cap); entries
+ * 0 .. min(count, cap) - 1 of a list hold the cells in row-major (np.argwhere) order and the entries past them are NOT written
+ * (the caller's bytes stay: the launch stores as much as there are objects, not cap).  counts_dev and coords_dev 4-byte aligned.
+ *
+ * info_observation_coordinates: (row, col) of the set cells of every layer, np.argwhere order.
+ * layers_dev uint8 [N, L, H*W]; counts_dev int32 [N, L]; coords_dev int16 [N, L, cap, 2]. */
+int sgw_layer_coords(sgw_engine* e, const uint8_t* layers_dev, int n_layers, int cap,
+                     int32_t* counts_dev, int16_t* coords_dev, void* stream);
+
+/* info_agent_observation_coordinates: (x - ax, y - ay) inside each agent's window.
+ * views_dev uint8 [N, L * view_bytes] as written by sgw_agent_layer_views ([agent][layer][h_a][w_a] per env);
+ * agent_layer[A] = index of the agent's own character among the L layers, -1 = none;
+ * counts_dev int32 [N, A, L] (-1 = the agent is not in its own layers); coords_dev int16 [N, A, L, cap, 2].
+ * (ay, ax) is the first set cell, in row-major order, of the agent's own layer inside its own window (safety_game_moma.py:528-580;
+ * the windows are already rot90-ed by sgw_agent_layer_views).  agent_layer is HOST memory, read at call time. */
+int sgw_agent_layer_coords(sgw_engine* e, const uint8_t* views_dev, int n_layers, const int32_t* agent_layer,
+                           int cap, int32_t* counts_dev, int16_t* coords_dev, void* stream);
+
 /* State copy-out / copy-in (tests, checkpointing) in a layout-independent form: uint64 [words][N_pad], word w of env n at
  * [w][n] (the engine itself keeps word pairs interleaved per 64-env wave; these two calls convert). */
 int sgw_state_words(const sgw_engine* e);
