@@ -75,7 +75,7 @@ struct sgw_engine {
   long long graph_tick;
   std::vector<StepGraph> graphs;
   hipStream_t capture_stream;
-  unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
+  unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel, + 4 for the BigViews variant): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
   int step_shape;          // 1 + the ShapedSteps entry whose kernel runs this engine's one-step launches, 0 = the generic kernel
   // sgw_step_full: one captured graph per (actions, out, extras) triple
   struct FullGraph { const int8_t* actions; sgw_out out; sgw_extras ex; long long last_use; hipGraphExec_t exec; };
@@ -454,6 +454,17 @@ static int prepare_args(sgw_engine* e, KArgs& a) {
   return SGW_OK;
 }
 
+// Envs per chunk of the in-launch windows that are larger than the board (sgw_common.hpp lds_view_chunk rounds it up to what the
+// row size allows): VIEWS_CHUNK_DEFAULT, chosen by measurement.  A diagnostic build (-DSGW_VIEWS_CHUNK_KNOB, the
+// sweep of tools/diag/views_inlaunch_probe.py) reads SGW_VIEWS_CHUNK = 8 / 16 / 32 / 64 from the environment instead.
+static int views_chunk_envs() {
+#ifdef SGW_VIEWS_CHUNK_KNOB
+  const char* s = getenv("SGW_VIEWS_CHUNK");
+  const int g = s ? atoi(s) : 0;
+  if (g == 8 || g == 16 || g == 32 || g == 64) return g;
+#endif
+  return VIEWS_CHUNK_DEFAULT;
+}
 struct LaunchPlan { size_t lds_bytes; unsigned blocks, threads; };
 // LDS plan + grid of k_engine<F, KIND> for these arguments (fills a.lp / a.need)
 template <class F, int KIND> static int plan_launch(const sgw_engine* e, KArgs& a, LaunchPlan& p) {
@@ -462,13 +473,20 @@ template <class F, int KIND> static int plan_launch(const sgw_engine* e, KArgs& 
   const int need = lds_need(a, F::LDS_SCRATCH_M), pa = F::PER_AGENT ? F::NA : 1;
   if ((need & (LN_VIEWS | LN_OBSVIEWS)) && (!has_views<F>::value || a.sp.view_total <= 0))
     return fail(SGW_ERR_UNSUPPORTED, "launch: the views / obs_views outputs exist for the families with agent windows only");
-  if ((need & (LN_VIEWS | LN_OBSVIEWS)) && F::WAVES == 1 && a.sp.view_prefill)
-    return fail(SGW_ERR_UNSUPPORTED, "launch: a window larger than the board is not assembled inside this family's round kernel (one "
-                                     "wavefront per 64 envs would walk them env by env): use sgw_agent_views");
+  // one-wavefront families, a window larger than the board: the family's BigViews variant assembles them (launch() picks it)
+  if ((need & (LN_VIEWS | LN_OBSVIEWS)) && F::WAVES == 1 && a.sp.view_prefill && !has_chunked_views<F>::value)
+    return fail(SGW_ERR_UNSUPPORTED, "launch: a window larger than the board is not assembled by this launch path: use sgw_agent_views");
+  // (rot90 is for square windows, as in sgw_agent_views: the landing offsets of a non-square one would leave its row of the chunk)
+  if (has_chunked_views<F>::value && (need & (LN_VIEWS | LN_OBSVIEWS)) && a.sp.view_rotates)
+    for (int ag = 0; ag < SGW_MAX_AGENTS; ++ag)
+      if (a.sp.view_h[ag] != a.sp.view_w[ag])
+        return fail(SGW_ERR_UNSUPPORTED, "launch: rotation by observation direction needs square windows");
   const int vb = a.sp.view_total > 0 ? a.sp.view_total : 0;
+  // ... a chunk of the image at a time (views_chunked); every other launch stages the env-wave's whole image
+  const int VG = (has_chunked_views<F>::value && (need & (LN_VIEWS | LN_OBSVIEWS))) ? lds_view_chunk(vb, views_chunk_envs()) : WAVE;
   const int CS = cum_stash_rows<F>(a.sp.A, a.sp.K);
-  a.lp = lds_plan(a.sp.HW, a.sp.A, a.sp.K, a.sp.M, pa, need, vb, CS); a.need = need;
-  p.lds_bytes = lds_total_bytes(a.sp.HW, a.sp.A, a.sp.K, a.sp.M, pa, need, vb, F::LDS_EXTRA, EW, NB, CS);
+  a.lp = lds_plan(a.sp.HW, a.sp.A, a.sp.K, a.sp.M, pa, need, vb, CS, VG); a.need = need;
+  p.lds_bytes = lds_total_bytes(a.sp.HW, a.sp.A, a.sp.K, a.sp.M, pa, need, vb, F::LDS_EXTRA, EW, NB, CS, VG);
   p.blocks = (unsigned)((n_waves + EW - 1) / EW);
   p.threads = (unsigned)wg_threads<F, KIND>();
   // the bytes requested == the bytes the plan hands out (checked on every launch)
@@ -485,7 +503,7 @@ template <class F, int KIND, class SH = NoShape> static int launch_as(sgw_engine
   if (rc) return rc;
   // above the default dynamic-LDS cap: raised ONCE per engine and kernel, to the CU's 160 KiB -- a launch that needs it
   // is then never the first inside a stream capture (sgw_step_n)
-  constexpr unsigned bit = 1u << (KIND + (SH::ON ? 3 : 0));
+  constexpr unsigned bit = 1u << (KIND + (SH::ON ? 3 : 0) + (has_chunked_views<F>::value ? 4 : 0));
   if (p.lds_bytes > 65536 && !(e->lds_cap_raised & bit)) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_engine<F, KIND, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     e->lds_cap_raised |= bit;
@@ -507,13 +525,28 @@ template <class F, size_t I = 0> static int launch_step(sgw_engine* e, KArgs& a,
   }
 }
 
+template <class F> struct big_views_variant { using type = F; };
+template <> struct big_views_variant<Savanna> { using type = SavannaBigViews; };
+template <> struct big_views_variant<IslandMa> { using type = IslandMaBigViews; };
+template <> struct big_views_variant<IslandMaWide> { using type = IslandMaWideBigViews; };
+
 static int launch(sgw_engine* e, KArgs& a, hipStream_t st) {
   int rc = prepare_args(e, a);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(e->device));
   const int kind = launch_kind(a);
+  // a spec with a window larger than the board that asks for the windows runs the family's BigViews variant
+  const bool big = (a.out.views || a.out.obs_views) && e->ks.view_prefill;
   rc = with_family(e, [&](auto ft, int) {
     using F = typename decltype(ft)::type;
+    using B = typename big_views_variant<F>::type;
+    if constexpr (!std::is_same<B, F>::value) {
+      if (big) {
+        if (kind == K_STEP) return launch_as<B, K_STEP>(e, a, st);
+        if (kind == K_ROLLOUT) return launch_as<B, K_ROLLOUT>(e, a, st);
+        return launch_as<B, K_RESET>(e, a, st);
+      }
+    }
     if (kind == K_STEP) return launch_step<F>(e, a, st);
     if (kind == K_ROLLOUT) return launch_as<F, K_ROLLOUT>(e, a, st);
     return launch_as<F, K_RESET>(e, a, st);
@@ -531,6 +564,22 @@ int sgw_reset(sgw_engine* e, const uint8_t* mask_dev, const sgw_out* out, void* 
   a.mode = MODE_RESET; a.mask = mask_dev; a.T = 1;
   if (out) a.out = *out;
   return launch(e, a, (hipStream_t)stream);
+}
+
+int64_t sgw_step_lds_bytes(sgw_engine* e, const sgw_out* out) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_step_lds_bytes: null engine");
+  KArgs a; memset(&a, 0, sizeof(a));
+  a.mode = MODE_STEP; a.T = 1; a.sp = e->ks;
+  if (out) a.out = *out;
+  const bool big = (a.out.views || a.out.obs_views) && e->ks.view_prefill;
+  LaunchPlan p{};
+  const int rc = with_family(e, [&](auto ft, int) {
+    using F = typename decltype(ft)::type;
+    using B = typename big_views_variant<F>::type;
+    if constexpr (!std::is_same<B, F>::value) { if (big) return plan_launch<B, K_STEP>(e, a, p); }
+    return plan_launch<F, K_STEP>(e, a, p);
+  });
+  return rc ? (int64_t)rc : (int64_t)p.lds_bytes;
 }
 
 int sgw_step(sgw_engine* e, const int8_t* actions_dev, const sgw_out* out, void* stream) {

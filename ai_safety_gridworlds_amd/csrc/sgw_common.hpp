@@ -36,7 +36,8 @@ struct KSpec {
 
 // byte offsets of one env-wave staging buffer's regions, computed ONCE per launch on the host (lds_plan) and read from the
 // kernarg segment where needed: deriving them on the device cost a ~30-instruction scalar chain per region with spilled terms
-struct LdsPlan { int wave_bytes, vec_r, vec_c, vec_m, vec_a, trash, flag, ain, st, tr, act, pos, flg, disc, hid, saf, frm, views, cstash; };
+struct LdsPlan { int wave_bytes, vec_r, vec_c, vec_m, vec_a, trash, flag, ain, st, tr, act, pos, flg, disc, hid, saf, frm, views, cstash;
+                 int views_g; };   // envs whose windows the views region holds at a time: 64 (the whole image) or a chunk (lds_view_chunk)
 
 struct KArgs {
   KSpec sp;
@@ -192,7 +193,17 @@ __host__ __device__ inline int lds_need(const KArgs& a, bool family_scratch_m) {
          (o.safety2 ? LN_SAF2 : 0) | (o.views ? LN_VIEWS : 0) | (o.obs_views ? LN_OBSVIEWS : 0) |
          (o.done ? LN_DONE : 0) | (o.obs_dir ? LN_ODIR : 0) | (o.act_dir ? LN_ADIR : 0);
 }
-__host__ __device__ inline size_t lds_view_bytes(int vb, int need) { return (need & (LN_VIEWS | LN_OBSVIEWS)) ? ((size_t)64 * vb + 15) / 16 * 16 : 0; }
+// `vg` envs' windows at a time: the env-wave's whole image (64) or, for the one-wavefront families with a window larger than the
+// board, a chunk that the wave assembles and drains vg envs at a time (sgw_kernels.hpp views_chunked)
+__host__ __device__ inline size_t lds_view_bytes(int vb, int need, int vg = WAVE) { return (need & (LN_VIEWS | LN_OBSVIEWS)) ? ((size_t)vg * vb + 15) / 16 * 16 : 0; }
+// The chunk: the smallest of 8 / 16 / 32 / 64 envs that is at least `want` and makes the chunk's rows a whole number of 16-byte
+// stores (an odd view_total -- one 21 x 21 window -- needs a multiple of 16 envs).
+constexpr int VIEWS_CHUNK_DEFAULT = 8;
+__host__ inline int lds_view_chunk(int vb, int want) {
+  int g = 8;
+  while (g < WAVE && (g < want || ((g * vb) & 15) != 0)) g <<= 1;
+  return g;
+}
 __host__ __device__ inline size_t lds_rows(int A, int K, int M, int need, int which) {
   const int ak = A * K > 0 ? A * K : 1;
   switch (which) {
@@ -218,19 +229,19 @@ __host__ __device__ inline size_t lds_small_bytes(int A, int pa, int need, int w
   }
 }
 // one staging buffer of one env-wave
-__host__ __device__ inline size_t lds_wave_bytes(int HW, int A, int K, int M, int pa, int need, int vb, int cs = 0) {
+__host__ __device__ inline size_t lds_wave_bytes(int HW, int A, int K, int M, int pa, int need, int vb, int cs = 0, int vg = WAVE) {
   const size_t rows = lds_rows(A, K, M, need, LN_REWARD) + lds_rows(A, K, M, need, LN_CUMULATIVE) +
                       lds_rows(A, K, M, need, LN_METRICS) + lds_rows(A, K, M, need, LN_RETURNS) + 1;   // + trash
   size_t small = 16 + (size_t)(64 * A + 15) / 16 * 16;                  // flag words + the synthetic-action inbox (pipelined rollout)
   for (int w = LN_ST; w <= LN_FRM; w <<= 1) small += lds_small_bytes(A, pa, need, w);
   const bool cs_aliased = (need & (LN_REWARD | LN_CUMULATIVE | (SGW_ACC_PER_ENV ? 0 : LN_RETURNS))) != 0;
-  return lds_board_bytes(HW) + rows * 64 * 8 + small + lds_view_bytes(vb, need) + (cs_aliased ? 0 : (size_t)cs * 512);
+  return lds_board_bytes(HW) + rows * 64 * 8 + small + lds_view_bytes(vb, need, vg) + (cs_aliased ? 0 : (size_t)cs * 512);
 }
-__host__ __device__ inline size_t lds_total_bytes(int HW, int A, int K, int M, int pa, int need, int vb, int extra, int env_waves, int buffers, int cs = 0) {
-  return TABLE_BYTES + (size_t)extra + (size_t)env_waves * buffers * lds_wave_bytes(HW, A, K, M, pa, need, vb, cs);
+__host__ __device__ inline size_t lds_total_bytes(int HW, int A, int K, int M, int pa, int need, int vb, int extra, int env_waves, int buffers, int cs = 0, int vg = WAVE) {
+  return TABLE_BYTES + (size_t)extra + (size_t)env_waves * buffers * lds_wave_bytes(HW, A, K, M, pa, need, vb, cs, vg);
 }
 
-__host__ __device__ inline LdsPlan lds_plan(int HW, int A, int K, int M, int pa, int need, int vb, int cs = 0) {
+__host__ __device__ inline LdsPlan lds_plan(int HW, int A, int K, int M, int pa, int need, int vb, int cs = 0, int vg = WAVE) {
   LdsPlan p;
   int o = (int)lds_board_bytes(HW);
   p.vec_r = o; o += 512 * (int)lds_rows(A, K, M, need, LN_REWARD);
@@ -249,7 +260,7 @@ __host__ __device__ inline LdsPlan lds_plan(int HW, int A, int K, int M, int pa,
   p.hid = o; o += (int)lds_small_bytes(A, pa, need, LN_HID);
   p.saf = o; o += (int)lds_small_bytes(A, pa, need, LN_SAF);
   p.frm = o; o += (int)lds_small_bytes(A, pa, need, LN_FRM);
-  p.views = o; o += (int)lds_view_bytes(vb, need);
+  p.views = o; o += (int)lds_view_bytes(vb, need, vg); p.views_g = vg;
   // the parked cumulative vectors (families with CUM_IN_LDS; cs = A * K rows, indexed by output column) live in a staging region
   // that is only written AFTER the rules -- the reward rows, else the cumulative rows, else the returns rows -- and get rows of
   // their own only when none of those outputs is requested: an extra 11 KB per workgroup took aintelope_savanna from four

@@ -528,4 +528,9 @@ struct IslandMaT {
 using IslandMa = IslandMaT<4>;
 using IslandMaWide = IslandMaT<8>;      // maps of 65..128 cells
 
+// the same rules with the windows of a spec that has one larger than the board assembled a chunk of envs at a time
+// (sgw_kernels.hpp views_chunked): launched when such a spec asks for `views` / `obs_views`
+struct IslandMaBigViews : IslandMa { static constexpr bool VIEWS_CHUNKED = true; };
+struct IslandMaWideBigViews : IslandMaWide { static constexpr bool VIEWS_CHUNKED = true; };
+
 }  // namespace sgw

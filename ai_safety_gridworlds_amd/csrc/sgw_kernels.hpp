@@ -324,15 +324,18 @@ __device__ inline void view_rotate(int dir, int n, int& cr, int& cc) {
 //     `None` radius) no cell can fall outside and the bounds test is skipped.
 // ROT: the env has observation directions (a scalar property of the spec; the caller branches once): without them every `dir`
 // below is the constant UP and the rotation arithmetic folds away (firemaker's default mode: 86 instead of 89 us per round).
+// `e_img0`: the env whose row is row 0 of the image at l.views (0: the image holds the env-wave's 64 rows; the chunked phase of
+// the one-wavefront families hands over e_lo: its image holds rows [e_lo, e_hi) only).
 template <class F, bool ROT>
-__device__ inline void views_stage_wave_per_env(const typename F::State& s, const KSpec& sp, const Lds& l, int e_lo, int e_hi, int lane) {
+__device__ inline void views_stage_wave_per_env(const typename F::State& s, const KSpec& sp, const Lds& l, int e_lo, int e_hi, int lane,
+                                                int e_img0 = 0) {
   const int VB = sp.view_total, HW = sp.HW, W = sp.W, H = sp.H;
   const uint32_t pad = (uint32_t)sp.view_pad & 0xffu;
   uint8_t* img = l.views;
   const uint8_t* boards = reinterpret_cast<const uint8_t*>(l.board);
   if (sp.view_prefill) {                                     // (e_hi - e_lo) * VB is a multiple of 8 for blocks of 8 envs
     const uint64_t p8 = 0x0101010101010101ull * pad;
-    uint64_t* blk = reinterpret_cast<uint64_t*>(img + e_lo * VB);
+    uint64_t* blk = reinterpret_cast<uint64_t*>(img + (e_lo - e_img0) * VB);
     const int n8 = ((e_hi - e_lo) * VB) >> 3;
     for (int i = lane; i < n8; i += WAVE) blk[i] = p8;
   }
@@ -365,7 +368,7 @@ __device__ inline void views_stage_wave_per_env(const typename F::State& s, cons
         const int base = dir == 2 ? -(pr * vw + pc) : (dir == 3 ? (n1 + pr) * vw + n1 + pc : (dir == 0 ? n1 + pr - pc * vw : (n1 + pc) * vw - pr));
         const bool useQ = dir < 2, neg = dir == 3 || dir == 1;
         const uint8_t* src = boards + e * HW;
-        uint8_t* dst = img + e * VB + off + base;
+        uint8_t* dst = img + (e - e_img0) * VB + off + base;
         uint8_t val[NP];
 #pragma unroll
         for (int j = 0; j < NP; ++j) if (j < npass) val[j] = src[lane + WAVE * j < HW ? lane + WAVE * j : 0];
@@ -391,7 +394,7 @@ __device__ inline void views_stage_wave_per_env(const typename F::State& s, cons
         const int pr = __builtin_amdgcn_readlane(prow, e) - up, pc = __builtin_amdgcn_readlane(pcol, e) - left;
         const int dir = ROT ? __builtin_amdgcn_readlane(pdir, e) : 2;
         const uint8_t* src = boards + e * HW;
-        uint8_t* dst = img + e * VB + off;
+        uint8_t* dst = img + (e - e_img0) * VB + off;
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
           if (j < npass) {
@@ -411,7 +414,7 @@ __device__ inline void views_stage_wave_per_env(const typename F::State& s, cons
 // Families whose env-waves are single wavefronts (island_navigation_ex_ma, aintelope_savanna): a LANE assembles its own env's
 // windows -- 64 envs x 2 small windows would be 128 serial wave passes the other way.  The window cell index is uniform over
 // the wave (scalar row / column); only the agent's position and, where the env has observation directions, the rot90 are per
-// lane.  Windows no larger than the board only (a larger one takes the wave-per-env path).
+// lane.  Specs without a window larger than the board only (with one, views_chunked walks the envs with the whole wave).
 template <class F>
 __device__ inline void views_stage_lane_per_env(const typename F::State& s, const KSpec& sp, const Lds& l, int lane) {
   const int VB = sp.view_total, HW = sp.HW, W = sp.W, H = sp.H;
@@ -486,6 +489,69 @@ __device__ inline void views_drain_env(const KArgs& a, const Lds& l, long long e
   if (a.need & LN_OBSVIEWS) { float* g = a.out.obs_views + (env0 + e) * VB; for (int k = lane; k < VB; k += WAVE) g[k] = l.value_map[src[k] & 0x7f]; }
 }
 
+// ---- windows LARGER than the board in the one-wavefront families (island_navigation_ex_ma, aintelope_savanna) ----------------
+// The env-wave's whole image is 64 x view_total bytes (aintelope_savanna's default two 21 x 21 windows: 56 448 B), which would
+// cost the family resident workgroups.  The wave therefore assembles and drains G envs at a time through ONE region of
+// G x view_total bytes (G = LdsPlan::views_g, chosen by the launcher with G * view_total a multiple of 16): pad-prefill, drop
+// the board's cells (views_stage_wave_per_env), 16-byte write-through stores of the chunk's contiguous rows, next chunk.  The
+// wave's LDS instructions execute in order, so a chunk's reads are done before the next chunk's prefill overwrites them.
+// Masked reset: chunks without a reset env are skipped and the others leave row by row.
+// The path is a family VARIANT of its own (`static constexpr bool VIEWS_CHUNKED = true`: SavannaBigViews, IslandMaBigViews,
+// IslandMaWideBigViews), launched only when a spec with such a window asks for `views` / `obs_views`: as a runtime branch of the
+// families' own kernels its scalar-heavy env loop raised their SGPR spills (island_navigation_ex_ma's step kernel: 143 -> 215,
+// and with the spill lanes 230 -> 261 VGPR + 5 AGPR), whether or not a launch wanted windows.
+template <class F, class = void> struct has_chunked_views : std::false_type {};
+template <class F> struct has_chunked_views<F, std::void_t<decltype(F::VIEWS_CHUNKED)>> : std::integral_constant<bool, F::VIEWS_CHUNKED> {};
+__device__ inline void views_drain_chunk(const KArgs& a, const Lds& l, long long row0, int nbytes, int lane) {
+  const int VB = a.sp.view_total;
+  if (a.need & LN_VIEWS) {
+    uint4* g = reinterpret_cast<uint4*>(a.out.views + row0 * VB);
+    const uint4* src = reinterpret_cast<const uint4*>(l.views);
+    const int n = nbytes >> 4;
+    int j = lane;
+    for (; j + 3 * WAVE < n; j += 4 * WAVE) {                // four LDS reads in flight, then the four stores
+      const uint4 v0 = src[j], v1 = src[j + WAVE], v2 = src[j + 2 * WAVE], v3 = src[j + 3 * WAVE];
+      store16_wt(g + j, v0); store16_wt(g + j + WAVE, v1); store16_wt(g + j + 2 * WAVE, v2); store16_wt(g + j + 3 * WAVE, v3);
+    }
+    for (; j < n; j += WAVE) store16_wt(g + j, src[j]);
+  }
+  if (a.need & LN_OBSVIEWS) {
+    uint4* g = reinterpret_cast<uint4*>(a.out.obs_views + row0 * VB);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(l.views);
+    const int n = nbytes >> 2;
+    for (int j = lane; j < n; j += WAVE) {
+      const uint32_t q = src[j];
+      const float f0 = l.value_map[q & 0x7f], f1 = l.value_map[(q >> 8) & 0x7f], f2 = l.value_map[(q >> 16) & 0x7f], f3 = l.value_map[(q >> 24) & 0x7f];
+      store16_wt(g + j, make_uint4(__float_as_uint(f0), __float_as_uint(f1), __float_as_uint(f2), __float_as_uint(f3)));
+    }
+  }
+}
+template <class F>
+__device__ inline void views_chunked(const typename F::State& s, const KArgs& a, const Lds& l, long long env0, long long toff, int lane,
+                                     bool mask_on, bool lane_active) {
+  const int G = a.lp.views_g, VB = a.sp.view_total;
+  const unsigned long long on = mask_on ? __ballot(lane_active) : ~0ull;
+  const unsigned long long chunk_bits = G >= WAVE ? ~0ull : ((1ull << G) - 1ull);
+  const bool rot = has_view_dir<F>::value && a.sp.view_rotates;
+  for (int e0 = 0; e0 < WAVE; e0 += G) {
+    if (((on >> e0) & chunk_bits) == 0ull) continue;         // scalar
+    if (rot) views_stage_wave_per_env<F, has_view_dir<F>::value>(s, a.sp, l, e0, e0 + G, lane, e0);
+    else views_stage_wave_per_env<F, false>(s, a.sp, l, e0, e0 + G, lane, e0);
+    lds_wave_sync();
+    if (!mask_on) {
+      views_drain_chunk(a, l, toff + env0 + e0, G * VB, lane);
+    } else {
+      for (int e = e0; e < e0 + G; ++e) {
+        if (!((on >> e) & 1ull)) continue;
+        const uint8_t* src = l.views + (e - e0) * VB;
+        if (a.need & LN_VIEWS) { uint8_t* g = a.out.views + (env0 + e) * VB; for (int k = lane; k < VB; k += WAVE) g[k] = src[k]; }
+        if (a.need & LN_OBSVIEWS) { float* g = a.out.obs_views + (env0 + e) * VB; for (int k = lane; k < VB; k += WAVE) g[k] = l.value_map[src[k] & 0x7f]; }
+      }
+    }
+    lds_wave_sync();
+  }
+}
+
 // families whose workgroup's waves write the board rows together (cooperative families: every wave holds the same envs)
 template <class F, class = void> struct has_board_part : std::false_type {};
 template <class F> struct has_board_part<F, std::void_t<decltype(&F::stage_board_part)>> : std::true_type {};
@@ -544,7 +610,13 @@ __device__ inline void views_phase(const typename F::State& s, const KArgs& a_in
   // BOARD_DRAIN: the board rows also leave by the whole workgroup (their stores are in flight while the windows are assembled)
   if constexpr (BOARD_DRAIN) board_drain_wg(a, l, env0, toff, (int)threadIdx.x, NW * WAVE);
   if (!(a.need & (LN_VIEWS | LN_OBSVIEWS))) return;
-  if (NW == 1 && !a.sp.view_prefill) views_stage_lane_per_env<F>(s, a.sp, l, lane);
+  if constexpr (has_chunked_views<F>::value) {
+    // a spec with a window larger than the board: G envs at a time through the plan's chunk region (stages AND drains)
+    static_assert(NW == 1, "");
+    views_chunked<F>(s, a, l, env0, toff, lane, mask_on, lane_active);
+    return;
+  }
+  if (NW == 1) views_stage_lane_per_env<F>(s, a.sp, l, lane);
   else if (has_view_dir<F>::value && a.sp.view_rotates) views_stage_wave_per_env<F, has_view_dir<F>::value>(s, a.sp, l, w * EPW, (w + 1) * EPW, lane);
   else views_stage_wave_per_env<F, false>(s, a.sp, l, w * EPW, (w + 1) * EPW, lane);
   if (!mask_on) {

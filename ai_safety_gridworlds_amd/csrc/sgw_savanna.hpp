@@ -824,4 +824,8 @@ struct Savanna {
   static __device__ __forceinline__ int agent_safety2(const State& s, int ag, const KSpec&) { return s.saf2[ag]; }
 };
 
+// the same rules with the windows of a spec that has one larger than the board assembled a chunk of envs at a time
+// (sgw_kernels.hpp views_chunked): launched when such a spec asks for `views` / `obs_views`
+struct SavannaBigViews : Savanna { static constexpr bool VIEWS_CHUNKED = true; };
+
 }  // namespace sgw

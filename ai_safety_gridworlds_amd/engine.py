@@ -27,8 +27,11 @@ FUSED_VIEW_FAMILIES = (N.FIREMAKER_EX_MA, N.ISLAND_NAVIGATION_EX_MA, N.AINTELOPE
 
 
 def fused_views(spec):
-  """Can this spec's step launch write the agent windows itself (sgw_out.views / obs_views)?  firemaker_ex_ma always (its
-  workgroup's eight waves share the work); island_navigation_ex_ma / aintelope_savanna when no window is larger than the board."""
+  """Should this spec's windows come from the step launch itself (sgw_out.views / obs_views) rather than from sgw_agent_views?
+  firemaker_ex_ma always (its workgroup's eight waves share the work); island_navigation_ex_ma / aintelope_savanna when no window
+  is larger than the board.  Their step launch CAN write larger windows too (a chunk of envs at a time), but one wavefront per 64
+  envs is slower at it than the separate launch: 126 vs 92 us per round for default aintelope_savanna at 65 536 envs, 79 vs 53 us
+  for island_navigation_ex_ma with radius 3 (profiles/r06_views_inlaunch.json), so the wrappers keep two launches there."""
   if spec.family not in FUSED_VIEW_FAMILIES or not getattr(spec, "view_shapes", None):
     return False
   return spec.family == N.FIREMAKER_EX_MA or all(h * w <= spec.H * spec.W for (h, w) in spec.view_shapes)

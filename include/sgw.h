@@ -119,7 +119,13 @@ typedef struct sgw_out {
                           *               direction where the env has one, cells outside the board = spec.view_outside).  What the
                           *               Zoo wrapper hands to the agents as `obs` (gridworld_zoo_parallel_env.py:541-554): one launch
                           *               per round instead of step + sgw_agent_views.  Families with agent views only
-                          *               (firemaker_ex_ma, island_navigation_ex_ma, aintelope_savanna), SGW_ERR_UNSUPPORTED elsewhere */
+                          *               (firemaker_ex_ma, island_navigation_ex_ma, aintelope_savanna), SGW_ERR_UNSUPPORTED elsewhere.
+                          *               Windows with more cells than the board are accepted too (aintelope_savanna's default
+                          *               21 x 21 on 13 x 13; sizes may differ per agent; with observation directions such windows
+                          *               must be square, as for sgw_agent_views), on every launch path -- sgw_reset (a masked
+                          *               reset writes the rows of the reset envs only), sgw_step, sgw_step_n, sgw_step_full,
+                          *               sgw_replay, sgw_rollout.  For island_navigation_ex_ma / aintelope_savanna such windows
+                          *               cost more inside the launch than a following sgw_agent_views does */
   float* obs_views;      /* [N_pad, view_bytes] the same windows value-mapped to float32 (ascii_observation_format=False:
                           *               the window of observation['board'], observation_distiller_ex.py:147-187) */
   /* The wrappers' per-step decodes of the outputs above, written by the same launch so that a Python step does not launch a
@@ -389,6 +395,11 @@ int sgw_set_state(sgw_engine* e, const uint64_t* state_dev, void* stream);
  * the output geometry of one spec compiled in (chosen by sgw_create when family, state variant and geometry match one exactly;
  * SGW_GENERIC_STEP set in the environment at sgw_create keeps the generic kernel).  Both compute the same bytes. */
 int sgw_step_shape(const sgw_engine* e);
+
+/* Dynamic LDS, in bytes per workgroup, that a one-step launch (sgw_step, sgw_step_n) of this engine asks for when `out` names
+ * these outputs (NULL: none): what decides, with the kernel's registers, how many workgroups a CU keeps resident.  Nothing is
+ * launched.  Negative = the error code such a launch would return. */
+int64_t sgw_step_lds_bytes(sgw_engine* e, const sgw_out* out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,367 @@
+"""Agent windows LARGER than the board written by the round's own launch (sgw_out.views / obs_views) in the one-wavefront
+families, aintelope_savanna and island_navigation_ex_ma: bit-exact against the reference-run fixtures, the oracle's `view`
+(aintelope_savanna; the island_navigation_ex_ma oracle records 5 x 5 windows only and the aintelope_savanna oracle square ones),
+a numpy restatement of get_agent_perspective (crop, pad, rot90 by the observation direction) that is itself pinned to the
+oracle's `view`, and sgw_agent_views on the same step's outputs.  70 envs = two env-waves with a ragged tail, and 1 env; episodes
+of 12 rounds so that auto-resets happen, plus explicit resets."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from ai_safety_gridworlds_amd import _native as N
+from ai_safety_gridworlds_amd import philox
+from ai_safety_gridworlds_amd.engine import ALL_OUTPUTS, BatchedEngine
+from ai_safety_gridworlds_amd.specs import make_spec
+from tests import golden_util as G
+from tests import launch_paths as LP
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+RESET = -128
+E, T = 70, 40
+NAMES = {"sav": "aintelope_savanna", "ima": "island_navigation_ex_ma"}
+LEAN = ("board", "agent_pos", "agent_flags", "step_type", "views", "obs_views")
+TURN = dict(action_direction_mode=2, observation_direction_mode=2)       # turning actions: all four observation directions occur
+L3 = dict(level=3, amount_food_patches=1)                                # aintelope_savanna's 3 x 4 board
+
+
+def raw_agent_views(eng):
+  """sgw_agent_views on the engine's own board / agent_pos / agent_flags outputs: uint8 [n_envs, view bytes]."""
+  vb = int(eng._lib.sgw_view_bytes(eng._h))
+  out = torch.empty((eng.n_envs, vb), dtype=torch.uint8, device=eng.device)
+  N.check(eng._lib.sgw_agent_views(eng._h, eng._bufs["board"].data_ptr(), eng._bufs["agent_pos"].data_ptr(),
+                                   eng._view_flags(None), ord(getattr(eng.spec, "what_lies_outside", '#')), out.data_ptr(),
+                                   eng._stream()), "sgw_agent_views")
+  return out
+
+
+def value_map(spec):
+  return torch.tensor([spec.native.value_map[i] for i in range(128)], dtype=torch.float32, device=DEV)
+
+
+def windows_equal_side_kernel(eng, o, vm):
+  """The launch's `views` == sgw_agent_views on the same outputs, and `obs_views` == the value map applied to them."""
+  ok = torch.equal(o["views"], raw_agent_views(eng))
+  if "obs_views" in o:
+    ok = ok and torch.equal(o["obs_views"], vm[(o["views"] & 0x7f).long()])
+  return bool(ok)
+
+
+def run(spec, actions, rng, outs):
+  """reset, reset, then a step (or an explicit reset) per tick: {field: numpy [E, T + 2, ...]} and whether every record's
+  windows equalled the side kernel's."""
+  n = actions.shape[0]
+  eng = BatchedEngine(spec, n, device=DEV, outputs=outs)
+  eng.set_rng_state(rng)
+  acts = torch.from_numpy(np.ascontiguousarray(np.transpose(actions, (1, 0, 2)))).to(DEV)
+  vm = value_map(spec)
+  rec, same = {k: [] for k in outs}, []
+  def grab(o):
+    for k in outs:
+      rec[k].append(o[k].clone())
+    same.append(windows_equal_side_kernel(eng, o, vm))
+  grab(eng.reset()); grab(eng.reset())
+  for t in range(actions.shape[1]):
+    grab(eng.reset() if actions[0, t, 0] == RESET else eng.step(acts[t]))
+  torch.cuda.synchronize()
+  got = {k: torch.stack(v, dim=1).cpu().numpy() for k, v in rec.items()}
+  eng.close()
+  return got, same
+
+
+def split(spec, v):
+  out, off = [], 0
+  for (h, w) in spec.view_shapes:
+    out.append(v[..., off:off + h * w].reshape(v.shape[:-1] + (h, w)))
+    off += h * w
+  return out
+
+
+def numpy_windows(board, pos, dirs, rad, pad):
+  """get_agent_perspective (safety_game_moma.py:1996-2101) for one agent: board [n, H, W], pos [n, 2], dirs [n] (Directions
+  LEFT=0 RIGHT=1 UP=2 DOWN=3), rad (up, down, left, right): crop around the agent, `pad` outside the board, then rot90."""
+  up, down, left, right = rad
+  n, H, W = board.shape
+  P = max(rad)
+  padded = np.full((n, H + 2 * P, W + 2 * P), pad, np.uint8)
+  padded[:, P:P + H, P:P + W] = board
+  out = np.empty((n, up + down + 1, left + right + 1), np.uint8)
+  for i in range(n):
+    r, c = int(pos[i, 0]) + P, int(pos[i, 1]) + P
+    out[i] = np.rot90(padded[i, r - up:r + down + 1, c - left:c + right + 1], {2: 0, 3: 2, 0: -1, 1: 1}[int(dirs[i])])
+  return out
+
+
+# ---- 1. reference-run fixtures whose windows are larger than the board ------------------------------------------------------
+@pytest.mark.parametrize("name", ["sav_default", "sav_exp_sharing", "sav_L3_tiny"])
+def test_inlaunch_windows_match_reference_fixture(name):
+  fx, meta = G.load(name)
+  spec = make_spec("aintelope_savanna", **meta["kwargs"])
+  assert any(h * w > spec.H * spec.W for (h, w) in spec.view_shapes)
+  got, same = run(spec, fx["actions"], fx["rng_seeded"], LEAN)
+  A = spec.n_agents
+  views = np.stack(split(spec, got["views"]), axis=2)[:, :, :A]
+  G.assert_same(name + ".view", views[:, 1:], fx["view"][:, 1:])
+  vm = np.array([spec.native.value_map[i] for i in range(128)], np.float32)
+  G.assert_same(name + ".obs_views", got["obs_views"], vm[got["views"] & 0x7f])
+  assert all(same), "records whose windows differ from sgw_agent_views: %s" % [i for i, s in enumerate(same) if not s]
+
+
+# ---- 2. geometry matrix -----------------------------------------------------------------------------------------------------
+GEOMETRY = {
+    # the window covers the board wherever the agent stands (radius >= board size - 1): the bounds test is skipped
+    "sav_L3_covers": ("sav", dict(observation_radius=[3, 3, 3, 3], max_iterations=12, **L3, **TURN), True),
+    # more cells than the board but not covering; one agent (the spec still lays out both windows: view_total 882) and two
+    "sav_default_1": ("sav", dict(max_iterations=12), True),
+    "sav_default_2": ("sav", dict(amount_agents=2, max_iterations=12, **TURN), True),
+    # non-square (observation_radius is left, right, up, down: 9 rows x 5 columns on 3 x 4), fixed directions: rotation is for
+    # square windows only (the oracle records square ones)
+    "sav_L3_nonsquare": ("sav", dict(observation_radius=[3, 1, 2, 6], max_iterations=12, action_direction_mode=0,
+                                     observation_direction_mode=0, **L3), False),
+    # 7 x 7 = 49 cells on 6 x 8 = 48: narrower than the board's reach
+    "ima_L9_r3": ("ima", dict(level=9, observation_radius=[3, 3, 3, 3], max_iterations=12, **TURN), False),
+    # a resized map above 64 cells (the 8-word map kernels), 11 x 11 on 7 x 11
+    "ima_wide_r5": ("ima", dict(level=6, map_randomization_frequency=2, map_width=11, map_height=7, observation_radius=[5, 5, 5, 5],
+                                max_iterations=12, action_direction_mode=1, observation_direction_mode=1), False),
+}
+_GEO = {}
+
+
+def geometry_case(cid):
+  """(spec, row, actions [E, T, 2], rng, oracle arrays): computed once per case and shared (never modified)."""
+  if cid in _GEO:
+    return _GEO[cid]
+  from oracle import oracle_ima as OI, oracle_ma as OM, oracle_sav as OS
+  which, kw, _ = GEOMETRY[cid]
+  spec = make_spec(NAMES[which], **kw)
+  n_act = 9 if kw.get("action_direction_mode") == 2 else 5
+  actions = np.stack([philox.actions(0x51E + len(cid), np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(2)], axis=-1)
+  actions = np.transpose(actions, (1, 0, 2)).astype(np.int8).copy()
+  actions[:, 13, :] = RESET; actions[:, 27, :] = RESET
+  if which == "sav" and spec.n_agents == 1:
+    actions[:, :, 1] = np.where(actions[:, :, 0] == RESET, RESET, 0)
+  rng = np.stack([OM.rng_state_words(4100 + e) for e in range(E)])
+  okw = {k: v for k, v in kw.items() if not (which == "ima" and k == "observation_radius")}     # (that oracle's windows are 5 x 5)
+  if cid == "sav_L3_nonsquare":
+    okw["observation_radius"] = [3, 3, 3, 3]                                                    # (the oracle covers square views)
+  Or = {"sav": OS, "ima": OI}[which]
+  want = Or.run_streams(Or.make_config(**okw), actions, rng, nthreads=8)
+  row = dict(id=cid, name=NAMES[which], oracle=which)
+  _GEO[cid] = (spec, row, actions, rng, want)
+  return _GEO[cid]
+
+
+@pytest.mark.parametrize("n", [E, 1])
+@pytest.mark.parametrize("cid", list(GEOMETRY))
+def test_inlaunch_windows_geometry(cid, n):
+  spec, row, actions, rng, want = geometry_case(cid)
+  assert any(h * w > spec.H * spec.W for (h, w) in spec.view_shapes)
+  outs = ALL_OUTPUTS + ("views", "obs_views") + (("safety2",) if row["oracle"] == "sav" else ())
+  got, same = run(spec, actions[:n], rng[:n], outs)
+  assert all(same), "%s: records whose windows differ from sgw_agent_views: %s" % (cid, [i for i, s in enumerate(same) if not s])
+  wn = {k: v[:n] for k, v in want.items()}
+  A = wn["step_type"].shape[2]
+  views = split(spec, got["views"])
+  oracle_view = GEOMETRY[cid][2]
+  # every output the oracle records, with its `view` where it records this window
+  bad = LP.oracle_mismatches(row, spec, {k: v[:, 1:] for k, v in got.items() if k not in ("views", "obs_views")}, wn, 0,
+                             views=[v[:, 1:] for v in views] if oracle_view else None)
+  assert not bad, "%s: %s differ from the oracle" % (cid, bad)
+  if oracle_view:
+    assert len(np.unique(wn["observation_direction"])) == 4, "the case is meant to see all four observation directions"
+  # the numpy restatement on the oracle's board, positions and directions
+  rad = [int(spec.native.view_radius[0][j]) for j in range(4)]
+  S = T + 2
+  for ag in range(A):
+    dirs = wn["observation_direction"][:, :, ag] if spec.rotating_views else np.full((n, S), 2)
+    ref = numpy_windows(wn["board"].reshape(n * S, spec.H, spec.W), wn["pos"][:, :, ag].reshape(n * S, 2), dirs.reshape(-1), rad,
+                        ord(spec.what_lies_outside)).reshape((n, S) + views[ag].shape[2:])
+    G.assert_same("%s.numpy window of agent %d" % (cid, ag), views[ag][:, 1:], ref[:, 1:])
+
+
+# ---- 3. windows of different sizes in one spec (the C ABI's per-agent view_radius) ------------------------------------------
+@pytest.mark.parametrize("radii", [([10] * 4, [2] * 4), ([2] * 4, [10] * 4), ([10] * 4, None)], ids=["large_small", "small_large", "large_none"])
+def test_inlaunch_windows_mixed_sizes(radii):
+  """One window larger than the 13 x 13 board and one not (or absent: an odd row of 441 bytes) in one launch."""
+  spec = make_spec("aintelope_savanna", amount_agents=2, max_iterations=12, **TURN)
+  for ag, rad in enumerate(radii):
+    for j in range(4):
+      spec.native.view_radius[ag][j] = -1 if rad is None else rad[j]
+  spec.view_shapes = [(0, 0) if rad is None else (rad[0] + rad[1] + 1, rad[2] + rad[3] + 1) for rad in radii]
+  _, _, actions, rng, _ = geometry_case("sav_default_2")
+  got, same = run(spec, actions, rng, LEAN)
+  assert all(same), "records whose windows differ from sgw_agent_views: %s" % [i for i, s in enumerate(same) if not s]
+  S = T + 2
+  for ag, rad in enumerate(radii):
+    if rad is None:
+      continue
+    ref = numpy_windows(got["board"].reshape(E * S, spec.H, spec.W), got["agent_pos"].reshape(E * S, 2, 2)[:, ag],
+                        ((got["agent_flags"] >> 3) & 3).reshape(E * S, 2)[:, ag], rad, ord(spec.what_lies_outside))
+    G.assert_same("numpy window of agent %d" % ag, split(spec, got["views"])[ag].reshape(ref.shape), ref)
+
+
+# ---- 4. launch paths --------------------------------------------------------------------------------------------------------
+TP, CALLS, SEED = 16, 3, 0x77AA            # TP >= 8: the second step_n call of a buffer is captured, the third replayed
+PATH_SPECS = {"sav": ("aintelope_savanna", dict(amount_agents=2, max_iterations=12, **TURN)),
+              "ima": ("island_navigation_ex_ma", dict(level=9, observation_radius=[3, 3, 3, 3], max_iterations=12, **TURN))}
+_REF = {}
+
+
+def path_engine(which, outs=LEAN):
+  from oracle import oracle_ma as OM
+  name, kw = PATH_SPECS[which]
+  eng = BatchedEngine(make_spec(name, **kw), E, device=DEV, outputs=outs)
+  eng.set_rng_state(np.stack([OM.rng_state_words(7300 + e) for e in range(E)]))
+  eng.reset(); eng.reset()
+  return eng
+
+
+def path_reference(which):
+  """One sgw_step per step over CALLS * TP steps of the engine's synthetic action stream: (actions, {field: [S, E, ...]});
+  every step's windows equal the side kernel's."""
+  if which not in _REF:
+    eng = path_engine(which)
+    vm = value_map(eng.spec)
+    acts = eng.fill_actions(CALLS * TP, SEED).clone()
+    rec = {k: [] for k in LEAN}
+    for t in range(CALLS * TP):
+      o = eng.step(acts[t])
+      assert windows_equal_side_kernel(eng, o, vm), "sgw_step %d" % t
+      for k in LEAN:
+        rec[k].append(o[k].clone())
+    _REF[which] = (acts, {k: torch.stack(v) for k, v in rec.items()})
+    eng.close()
+  return _REF[which]
+
+
+@pytest.mark.parametrize("path", ["step_n_last", "step_n_every", "replay", "replay_last", "rollout"])
+@pytest.mark.parametrize("which", list(PATH_SPECS))
+def test_inlaunch_windows_launch_paths(which, path):
+  acts, ref = path_reference(which)
+  eng = path_engine(which)
+  buf = torch.empty_like(acts[:TP])
+  for k in range(CALLS):                       # step_n: direct launches, capture + replay, replay
+    sl = slice(k * TP, (k + 1) * TP)
+    every = path in ("step_n_every", "replay", "rollout")
+    if path.startswith("step_n"):
+      buf.copy_(acts[sl])
+      o = eng.step_n(buf, write_every=every)
+    elif path.startswith("replay"):
+      o = eng.replay(acts[sl], write_every=every)
+    else:
+      o = eng.rollout(TP, SEED, step0=k * TP, write_every=True)
+    for f in LEAN:
+      w = ref[f][sl] if every else ref[f][(k + 1) * TP - 1]
+      assert torch.equal(o[f], w), "%s %s call %d: %s differs from the sgw_step engine" % (which, path, k, f)
+  eng.close()
+
+
+@pytest.mark.parametrize("replay", [False, True], ids=["direct", "graph"])
+@pytest.mark.parametrize("which", list(PATH_SPECS))
+def test_inlaunch_windows_step_full(which, replay):
+  """sgw_step_full (its launches chained in C; `replay`: captured and replayed as a hipGraph from the third call on)."""
+  acts, ref = path_reference(which)
+  eng = path_engine(which)
+  for t in range(6):
+    o = eng.step_full(acts[t], rgb=True, replay=replay)
+    for f in LEAN:
+      assert torch.equal(o[f], ref[f][t]), "%s step_full call %d: %s differs from the sgw_step engine" % (which, t, f)
+  eng.close()
+
+
+def test_rotating_non_square_window_is_refused_like_sgw_agent_views():
+  """sgw_agent_views refuses rot90 of a non-square window; so does a launch that is asked for the windows."""
+  spec = make_spec("aintelope_savanna", amount_agents=2, max_iterations=12, **TURN)
+  for ag in range(2):
+    for j, r in enumerate((2, 6, 10, 10)):                     # up, down, left, right: 9 x 21 = 189 cells on 13 x 13 = 169
+      spec.native.view_radius[ag][j] = r
+  spec.view_shapes = [(9, 21), (9, 21)]
+  eng = BatchedEngine(spec, E, device=DEV, outputs=LEAN)
+  eng.set_rng_state(geometry_case("sav_default_2")[3])
+  with pytest.raises(N.SgwError, match="square"):
+    eng.reset()
+  eng.close()
+  eng = BatchedEngine(spec, E, device=DEV, outputs=("board", "agent_pos", "agent_flags"))       # without the windows: as before
+  eng.set_rng_state(geometry_case("sav_default_2")[3])
+  eng.reset()
+  with pytest.raises(N.SgwError, match="square"):
+    raw_agent_views(eng)
+  eng.close()
+
+
+@pytest.mark.parametrize("which", list(PATH_SPECS))
+def test_inlaunch_windows_masked_reset_leaves_other_rows(which):
+  acts, _ = path_reference(which)
+  eng = path_engine(which)
+  vm = value_map(eng.spec)
+  for t in range(5):
+    eng.step(acts[t])
+  m = torch.zeros(E, dtype=torch.bool, device=DEV)
+  m[[0, 3, 17, 40, 63, 64, 69]] = True          # both env-waves; chunks with one, several and no reset env
+  eng._bufs["views"].fill_(0xAB)
+  eng._bufs["obs_views"].fill_(-7.0)
+  o = eng.reset(m.to(torch.uint8))
+  want = raw_agent_views(eng)
+  assert torch.equal(o["views"][m], want[m])
+  assert torch.equal(o["obs_views"][m], vm[(want[m] & 0x7f).long()])
+  assert bool((o["views"][~m] == 0xAB).all()) and bool((eng._bufs["views"][E:] == 0xAB).all()), "rows of envs that were not reset were written"
+  assert bool((o["obs_views"][~m] == -7.0).all()) and bool((eng._bufs["obs_views"][E:] == -7.0).all())
+  eng.close()
+
+
+# ---- 5. the Zoo vector env over default aintelope_savanna -------------------------------------------------------------------
+# The in-launch windows were measured slower than the round followed by sgw_agent_views for this family (engine.fused_views), so
+# the env keeps two launches: its `obs` must equal the side kernel's windows either way, and it launches sgw_agent_views exactly
+# when it is not on the fused path.
+@pytest.mark.parametrize("ascii_format", [True, False])
+def test_zoo_vector_env_default_savanna_windows(ascii_format):
+  from ai_safety_gridworlds_amd.helpers.gridworld_zoo_vector_env import GridworldZooVectorEnv
+  env = GridworldZooVectorEnv("aintelope_savanna", num_envs=E, seed=3, device=DEV, ascii_observation_format=ascii_format, max_iterations=12)
+  eng = env._env.engine
+  side_kernel, calls = eng.agent_views, [0]
+  def counted(*a, **kw):
+    calls[0] += 1
+    return side_kernel(*a, **kw)
+  eng.agent_views = counted
+  vm = value_map(eng.spec)
+  lo, hi = env.action_range(env.possible_agents[0])
+  gen = torch.Generator().manual_seed(11)
+  def check(obs, label):
+    want = side_kernel()
+    for i, a in enumerate(env.possible_agents):
+      w = want[env._slots[i]]
+      assert torch.equal(obs[a], w if ascii_format else vm[(w & 0x7f).long()]), "%s: obs[%s]" % (label, a)
+  obs, _ = env.reset()
+  check(obs, "reset")
+  for t in range(20):
+    acts = torch.randint(lo, hi + 1, (E, eng.spec.A), generator=gen).to(torch.int8).to(DEV)
+    obs = env.step(acts)[0]
+    check(obs, "step %d" % t)
+  from ai_safety_gridworlds_amd.engine import fused_views
+  assert env._fused == fused_views(eng.spec)
+  assert (calls[0] == 0) == env._fused, "the env launched sgw_agent_views %d times (fused: %s)" % (calls[0], env._fused)
+  env.close()
+
+
+# ---- 6. specs without a larger window are launched as before (their windows and outputs are pinned by the existing suites) ----
+def test_small_window_specs_still_take_the_lane_per_env_path():
+  """sav_rich2 (5 x 5 windows) through the same harness: fixture `view` and sgw_agent_views."""
+  fx, meta = G.load("sav_rich2")
+  spec = make_spec("aintelope_savanna", **meta["kwargs"])
+  assert all(h * w <= spec.H * spec.W for (h, w) in spec.view_shapes)
+  got, same = run(spec, fx["actions"], fx["rng_seeded"], LEAN)
+  assert all(same)
+  G.assert_same("sav_rich2.view", np.stack(split(spec, got["views"]), axis=2)[:, 1:, :spec.n_agents], fx["view"][:, 1:])
+
+
+@pytest.mark.parametrize("kw,want", [(dict(), 23904), (dict(amount_agents=2), 26976)], ids=["1_agent", "2_agents"])
+def test_round_without_views_asks_for_the_same_lds_as_before(kw, want):
+  """Default aintelope_savanna, the Zoo vector env's outputs without the windows: the dynamic LDS per workgroup is what the
+  launcher's plan gave before the chunked region existed.  One agent (K = 3, M = 4): 2 048 B of tables + 10 832 B of board rows +
+  19 rows of 512 B (6 reward, 6 cumulative, 6 metrics, trash) + 1 296 B of flag words, action inbox and per-env outputs."""
+  outs = ("board", "reward", "cumulative", "step_type", "term_reason", "discount", "metrics", "agent_pos", "agent_flags", "done")
+  eng = BatchedEngine(make_spec("aintelope_savanna", **kw), E, device=DEV, outputs=outs)
+  assert int(eng._lib.sgw_step_lds_bytes(eng._h, C.byref(eng._out))) == want
+  eng.close()
