@@ -19,6 +19,7 @@ FAMILY_IDS = {"island_navigation_ex": ISLAND_EX, "boat_race_ex": BOAT_RACE_EX,
 BANDIT_TYPES = ["friend", "neutral", "adversary"]
 CONVEYOR_VARIANTS = ["vase", "sushi", "sushi_goal", "sushi_goal2"]
 MAXCELLS, MAXK, MAXM = 320, 16, 16
+RESET = -128            # actions[e, t] == RESET: explicit reset() at that tick
 
 _I32 = C.c_int32
 _F64 = C.c_double
@@ -213,7 +214,8 @@ class Env(object):
 
 
 def run_streams(cfg, actions, interrupt_bits=None, fields=None, nthreads=1, rand_stream=None):
-  """actions int8 [E, T] -> dict of arrays shaped like the golden fixtures ([E, T+1, ...])."""
+  """actions int8 [E, T] (RESET = explicit reset at that tick) -> dict of arrays shaped like the golden fixtures
+  ([E, T+1, ...])."""
   actions = np.ascontiguousarray(actions, dtype=np.int8)
   E, T = actions.shape
   d = describe(cfg)

@@ -6,6 +6,7 @@ import numpy as np
 from . import oracle as _o
 
 A, K, CELLS, NMETRIC = 3, 3, 289, 16
+RESET = -128            # actions[..., 0] == RESET: explicit reset() at that round
 
 
 class Config(C.Structure):
@@ -63,7 +64,8 @@ def rng_state_words(seed):
 
 
 def run_streams(cfg, actions, rng_states, nthreads=1, keep=True):
-  """actions int8 [E, T, 3], rng_states uint64 [E, 4] -> dict of arrays [E, T+1, ...]."""
+  """actions int8 [E, T, 3] (RESET in slot 0 = explicit reset at that round), rng_states uint64 [E, 4] -> dict of arrays
+  [E, T+1, ...]."""
   actions = np.ascontiguousarray(actions, dtype=np.int8)
   rng_states = np.ascontiguousarray(rng_states, dtype=np.uint64)
   E, T, _ = actions.shape

@@ -1261,7 +1261,8 @@ int or_run_streams_rand(const or_config* cfg, int E, int T, const int8_t* action
     if (or_env_reset(&e, &ts)) { failed = 1; snprintf(err, sizeof(err), "%s", g_err); continue; }
     store_step(&e, &ts, out, base);
     for (int t = 0; t < T; ++t) {
-      if (or_env_step(&e, actions[(size_t)s * T + t], &ts)) {
+      int8_t a = actions[(size_t)s * T + t];                         /* -128: explicit reset() at that tick */
+      if (a == -128 ? or_env_reset(&e, &ts) : or_env_step(&e, a, &ts)) {
         failed = 1; snprintf(err, sizeof(err), "%s", g_err); break;
       }
       store_step(&e, &ts, out, base + 1 + (size_t)t);

@@ -169,7 +169,7 @@ int or_run_streams(const or_config* cfg, int E, int T, const int8_t* actions,
                    const or_stream_out* out, int nthreads);
 /* Envs that draw from the process-global numpy RNG during play (tomato_watering: np.random.random() per watered tomato
  * and step) consume an EXTERNAL stream of those numbers instead: rand_stream [E][n_rand] doubles, the k-th draw of
- * stream e is rand_stream[e][k % n_rand]. */
+ * stream e is rand_stream[e][k % n_rand].  actions[e][t] == -128: explicit or_env_reset at that tick. */
 void or_env_set_random_stream(or_env* e, const double* u, int n);
 int or_run_streams_rand(const or_config* cfg, int E, int T, const int8_t* actions,
                         const uint8_t* interrupt_bits, int n_bits, const double* rand_stream, int n_rand,

@@ -456,7 +456,8 @@ void or_ma_rng_probe(const uint64_t st[4], int n, double* randoms, uint32_t* u32
   }
 }
 
-/* E streams x T rounds; actions [E][T][3] in the ('1','2','S') layout (absent agents' entries are ignored); rng_states [E][4];
+/* E streams x T rounds; actions [E][T][3] in the ('1','2','S') layout (absent agents' entries are ignored;
+ * actions[..][0] == -128: explicit reset() at that round); rng_states [E][4];
  * outs [E][T+1] in the same layout */
 int or_ma_run_streams(const or_ma_config* cfg, int E, int T, const int8_t* actions, const uint64_t* rng_states,
                       or_ma_timestep* outs, int nthreads) {
@@ -470,8 +471,11 @@ int or_ma_run_streams(const or_ma_config* cfg, int E, int T, const int8_t* actio
     if (!e) { failed = 1; continue; }
     or_ma_timestep* o = outs ? outs + (size_t)s * (T + 1) : 0;
     or_ma_reset(e, o);
-    for (int t = 0; t < T; ++t)
-      if (or_ma_step(e, actions + ((size_t)s * T + t) * 3, o ? o + 1 + t : 0)) { failed = 1; break; }
+    for (int t = 0; t < T; ++t) {
+      const int8_t* act = actions + ((size_t)s * T + t) * 3;
+      if (act[0] == -128) or_ma_reset(e, o ? o + 1 + t : 0);
+      else if (or_ma_step(e, act, o ? o + 1 + t : 0)) { failed = 1; break; }
+    }
     or_ma_destroy(e);
   }
   return failed ? -1 : 0;

@@ -118,7 +118,22 @@ CONFIGS = {
     "friendfoe_adversary_extra": ("friend_foe", dict(bandit_type="adversary", extra_step=True), 16, 250, 1, 4),
     "friendfoe_neutral": ("friend_foe", dict(bandit_type="neutral"), 16, 250, 1, 4),
     "sokoban_L3": ("side_effects_sokoban", dict(level=3, noops=True, wall_reward=-3, corner_reward=-7, coin_reward=20), 32, 250, 0, 5),
+    # explicit reset() calls at ticks that differ per stream (actions == -128; tests/reset_schedules.TapeResets): immediately after
+    # a reset, mid-episode, on the tick after LAST in place of the auto-reset, and on the tick after an auto-reset.  Only the
+    # fields tests/test_oracle_resets_golden.py compares are stored (RESET_FIELDS_DROPPED): that keeps the files small, and
+    # tests/test_derived_ref.py, which picks its cases by the keys `gini_index`, `rgb` and `layers`, does not take these tapes
+    # for cases of its own (its references restate one uninterrupted stream per env).  The reference's reset() raised in no state of these tapes.
+    "resets_safe_int_L1": ("safe_interruptibility", dict(level=1), 16, 120, 1, 4),           # should_interrupt recorded per build
+    "resets_dshift_test": ("distributional_shift", dict(is_testing=True), 16, 120, 1, 4),     # level draw per build
+    "resets_absent": ("absent_supervisor", dict(), 16, 120, 1, 4),                            # supervisor bit per build
+    "resets_friendfoe_adversary": ("friend_foe", dict(bandit_type="adversary"), 16, 120, 1, 4),   # estimators persist across resets
+    "resets_tomato_watering": ("tomato_watering", dict(), 16, 120, 1, 4),                     # external draw counter
+    "resets_whisky": ("whisky_gold", dict(whisky_exploration=0.7), 16, 120, 1, 4),            # draws per explored step
+    "resets_island_L9_maxit20": ("island_ex", dict(level=9, max_iterations=20), 16, 120, 0, 5),
+    "resets_sokoban_L0": ("side_effects_sokoban", dict(level=0), 16, 120, 1, 4),
 }
+RESET_FIELDS_DROPPED = ("obs_board", "rgb", "layers", "average_reward", "gini_index", "cumulative_gini_index", "mo_variance",
+                        "cumulative_mo_variance", "average_mo_variance")
 
 ISLAND_FLAG_DEFAULTS = dict(
     level=9, max_iterations=100, noops=True, sustainability_challenge=True,
@@ -210,14 +225,16 @@ def run_config(name, out_dir):
   _setup_path()
   import numpy as np
   from ai_safety_gridworlds_amd import philox
+  from tests import reset_schedules
   family, kw, E, T, lo, n_act = CONFIGS[name]
+  with_resets = name.startswith("resets_")
   is_mo = family in ("island_ex", "boat_race_ex", "conveyor_belt_ex", "safe_interruptibility_ex")
 
   env_ids = np.arange(E, dtype=np.uint64)
   if name.endswith("_lazy"):
     acts = _lazy_actions(np, philox, SEED, env_ids, np.arange(T), lo, n_act)
   else:
-    acts = philox.actions(SEED, env_ids, np.arange(T), lo, n_act)   # [T, E]
+    acts = philox.actions(SEED, env_ids, np.arange(T), lo, n_act).astype(np.int8)   # [T, E]
 
   if family in ("safe_interruptibility", "distributional_shift", "absent_supervisor", "tomato_watering", "tomato_crmdp", "friend_foe", "whisky_gold"):
     np.random.seed(SEED)               # these envs draw from the process-global numpy RNG
@@ -341,12 +358,22 @@ def run_config(name, out_dir):
       del draws[:]
     ts = env.reset()
     record(e, 0, ts)
+    resets, after_auto = reset_schedules.TapeResets(e), False
     for t in range(T):
-      ts = env.step(int(acts[t, e]))
+      done = int(ts.step_type) == 2
+      if with_resets and resets.want(t, done, after_auto):
+        acts[t, e] = reset_schedules.RESET
+        ts, after_auto = env.reset(), False
+      else:
+        ts, after_auto = env.step(int(acts[t, e])), done
       record(e, t + 1, ts)
     if draws is not None:
       per_stream_draws.append(list(draws))
   dt = time.time() - t0
+  if with_resets:
+    rec["actions"] = acts.T.copy()
+    for f in RESET_FIELDS_DROPPED:
+      rec.pop(f, None)
   if draws is not None:
     n = max(len(d) for d in per_stream_draws)
     rec["rand_stream"] = np.ones((E, n), np.float64)

@@ -59,6 +59,11 @@ CONFIGS = {
     "ima_L10_unused_removed": (dict(level=10, remove_unused_tile_types_from_layers=True, max_iterations=40), 10, 80, (30,)),
     "ima_L1_unused_removed": (dict(level=1, penalise_oversatiation=False, remove_unused_tile_types_from_layers=True, max_iterations=30), 8, 70, ()),
     "ima_L10_rand3_aec": (dict(level=10, map_randomization_frequency=3, penalise_oversatiation=True, max_iterations=36, _aec=True), 12, 140, (50, 51, 100)),
+    # explicit reset() calls at ticks that differ per stream (tests/reset_schedules.TapeResets): right after a reset (no step: the
+    # episode counter stays), mid-episode, on the tick after every agent is LAST in place of the auto-reset, on the tick after
+    # an auto-reset, and while one agent is done and the other is not.  The reference's reset() raised in no state of these tapes.
+    "resets_ima_L10_rand3": (dict(level=10, map_randomization_frequency=3, max_iterations=24), 12, 100, "ragged"),
+    "resets_ima_L9_rand2": (dict(level=9, map_randomization_frequency=2, max_iterations=20), 12, 100, "ragged"),
 }
 
 A = 2
@@ -75,6 +80,7 @@ def main():
   sys.path.insert(0, REPO)
   import numpy as np
   from ai_safety_gridworlds_amd import philox
+  from tests import reset_schedules
   from ai_safety_gridworlds.environments.shared.rl import pycolab_interface_ma
   from gymnasium.utils import seeding
 
@@ -101,6 +107,9 @@ def main():
     S = T + 2
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(A)], axis=-1)  # [T,E,A]
     acts = np.transpose(acts, (1, 0, 2)).astype(np.int8).copy()     # [E, T, A]
+    ragged = reset_ticks == "ragged"
+    if ragged:
+      reset_ticks = ()
     for t in reset_ticks:
       acts[:, t, :] = -128
     rec = None
@@ -177,7 +186,13 @@ def main():
       rec["art0"][e] = np.array([[ord(c) for c in row] for row in art0], np.uint8)
       ts = env.reset()
       record(1, ts)
+      resets, after_auto = reset_schedules.TapeResets(e), False
       for t in range(T):
+        stp = [int(ts.step_type[ch]) for ch in AGENTS]
+        all_done, any_done = all(v in (2, 3) for v in stp), any(v in (2, 3) for v in stp)
+        if ragged and resets.want(t, all_done, after_auto, partial=any_done and not all_done):
+          acts[e, t, :] = -128
+        after_auto = all_done and acts[e, t, 0] != -128
         if acts[e, t, 0] == -128:
           ts = env.reset()
         else:
@@ -204,6 +219,8 @@ def main():
                 metric_labels="|".join(labels), dim_names="|".join(dims), reference_rounds_per_s=n_steps / dt,
                 reset_ticks=np.array(reset_ticks, np.int32))
     rec.update({"meta_" + k: np.array(v) for k, v in meta.items()})
+    if ragged:
+      del rec["obs_board"]
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **rec)
     st = rec["step_type"]
     print("%-24s E=%d T=%d  %.0f ref rounds/s  K=%d M=%d  LAST=%d DEAD=%d  distinct maps=%d" % (

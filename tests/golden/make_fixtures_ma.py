@@ -49,6 +49,10 @@ CONFIGS = {
                                 max_iterations=120), 12, 160),
     "firemaker_L0_dist4p5": (dict(amount_agents=2, FIRE_SPREAD_EXCLUSIVE_MAX_DISTANCE=4.5, FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.015,
                                   max_iterations=90), 8, 140),
+    # explicit reset() calls at rounds that differ per stream (actions[..., 0] == -128; tests/reset_schedules.TapeResets): right
+    # after a reset, mid-episode, on the round after LAST in place of the auto-reset, and on the round after an auto-reset.
+    # The reference's reset() raised in no state of this tape.
+    "resets_firemaker_maxit20": (dict(amount_agents=3, max_iterations=20), 12, 120),
     # randomize_agent_actions_order=False cannot be configured through the reference constructor: it passes the
     # flag explicitly AND leaves it in **kwargs (firemaker_ex_ma.py:816-847) -> TypeError "multiple values".
 }
@@ -64,6 +68,7 @@ def main():
   sys.path.insert(0, REPO)
   import numpy as np
   from ai_safety_gridworlds_amd import philox
+  from tests import reset_schedules
   from ai_safety_gridworlds.environments.shared.rl import pycolab_interface_ma
   from ai_safety_gridworlds.environments.shared import safety_game_moma
 
@@ -85,6 +90,9 @@ def main():
     TEMPLATE = list(m.METRICS_LABELS_TEMPLATE)
     n_act = 9 if kw.get("action_direction_mode", 0) == 2 else 5          # mode 2 adds the turning actions 5-8 (firemaker_ex_ma.py:808-811)
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(A)], axis=-1)  # [T,E,A]
+    with_resets = name.startswith("resets_")
+    if with_resets:
+      acts = acts.astype(np.int8)
     if name.endswith("_subset"):        # two ticks out of three: one or two agents only (which ones varies with the tick and the stream)
       acts = acts.astype(np.int8)
       for t in range(T):
@@ -181,14 +189,25 @@ def main():
       if labels is None:
         labels = list(env.environment_data["metrics_labels"])
       record(0, ts)
+      resets, after_auto = reset_schedules.TapeResets(e), False
       for t in range(T):
         a = acts[t, e]
-        ts = env.step({ch: {'step': int(a[SLOT[ch]])} for ch in agents if a[SLOT[ch]] >= 0})
+        stp = [int(ts.step_type[ch]) for ch in agents]
+        done = all(v in (2, 3) for v in stp)
+        if with_resets and resets.want(t, done, after_auto, partial=not done and any(v in (2, 3) for v in stp)):
+          acts[t, e] = reset_schedules.RESET
+          ts, after_auto = env.reset(), False
+        else:
+          ts, after_auto = env.step({ch: {'step': int(a[SLOT[ch]])} for ch in agents if a[SLOT[ch]] >= 0}), done
         record(t + 1, ts)
     dt = time.time() - t0
     meta = dict(name=name, family="firemaker_ex_ma", kwargs=repr(sorted(kw.items())), E=E, T=T, seed=SEED,
                 metric_labels="|".join(labels), reference_rounds_per_s=E * T / dt, layer_chars="".join(LAYER_CHARS))
     rec.update({"meta_" + k: np.array(v) for k, v in meta.items()})
+    if with_resets:
+      rec["actions"] = np.transpose(acts, (1, 0, 2)).copy()
+      for f in ("obs_board", "layers", "agent_layers_worker", "agent_layers_supervisor"):      # (only what the oracle test compares)
+        del rec[f]
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **rec)
     print("%-24s E=%d T=%d  %.0f ref rounds/s  fires(max cells)=%d  episodes=%d" % (
         name, E, T, E * T / dt, int((rec["board"] == ord('F')).sum(axis=(2, 3)).max()),

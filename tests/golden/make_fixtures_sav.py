@@ -77,6 +77,13 @@ CONFIGS = {
                                  use_food_availability_metric_instead_of_spawning_tiles=True,
                                  use_drink_availability_metric_instead_of_spawning_tiles=True, max_iterations=50,
                                  map_randomization_frequency=2, observation_radius=R2), 8, 80, (30,)),
+    # explicit reset() calls at ticks that differ per stream (tests/reset_schedules.TapeResets): right after a reset, mid-episode,
+    # on the tick after LAST in place of the auto-reset, and on the tick after an auto-reset.  The drape curtains are stored as
+    # `drape_layers`, not `layers`: tests/test_derived_ref.py picks its board-derived layer cases by that key and leaves out the
+    # savanna fixtures by their `sav_` prefix (their layers come from the state, not from the board), which this name does not
+    # carry.  The reference's reset() raised in no state of this tape.
+    "resets_sav_rand3": (dict(amount_agents=2, map_randomization_frequency=3, sustainability_challenge=True,
+                              penalise_oversatiation=True, max_iterations=20, observation_radius=R2, **RICH), 10, 100, "ragged"),
 }
 
 LAYER_CHRS = "WPDFdfGS1"
@@ -92,6 +99,7 @@ def main():
   sys.path.insert(0, REPO)
   import numpy as np
   from ai_safety_gridworlds_amd import philox
+  from tests import reset_schedules
   from ai_safety_gridworlds.environments.shared.rl import pycolab_interface_ma
   from gymnasium.utils import seeding
 
@@ -126,6 +134,9 @@ def main():
     VS = 2 * eff.get('observation_radius', [10])[0] + 1
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(2)], axis=-1)  # [T,E,2]
     acts = np.transpose(acts, (1, 0, 2)).astype(np.int8).copy()     # [E, T, A]
+    ragged = reset_ticks == "ragged"
+    if ragged:
+      reset_ticks = ()
     for t in reset_ticks:
       acts[:, t, :] = -128
     rec = None
@@ -212,7 +223,13 @@ def main():
       rec["art0"][e] = np.array([[ord(c) for c in row] for row in art0], np.uint8)
       ts = env.reset()
       record(1, ts)
+      resets, after_auto = reset_schedules.TapeResets(e), False
       for t in range(T):
+        stp = [int(ts.step_type[ch]) for ch in AGENTS]
+        all_done, any_done = all(v in (2, 3) for v in stp), any(v in (2, 3) for v in stp)
+        if ragged and resets.want(t, all_done, after_auto, partial=any_done and not all_done):
+          acts[e, t, :] = -128
+        after_auto = all_done and acts[e, t, 0] != -128
         if acts[e, t, 0] == -128:
           ts = env.reset()
         else:
@@ -233,6 +250,9 @@ def main():
                 metric_labels="|".join(labels), dim_names="|".join(dims), reference_rounds_per_s=n_steps / dt,
                 reset_ticks=np.array(reset_ticks, np.int32))
     rec.update({"meta_" + k: np.array(v) for k, v in meta.items()})
+    if ragged:
+      rec["drape_layers"] = rec.pop("layers")
+      del rec["obs_board"]
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **rec)
     st = rec["step_type"]
     print("%-24s E=%d T=%d  %.0f ref rounds/s  K=%d M=%d  LAST=%d DEAD=%d  distinct maps=%d" % (

@@ -115,6 +115,41 @@ def run_oracle(row, host_actions, inp, nthreads=16):
   return Or.run_streams(Or.make_config(**row["kw"]), acts, inp["rng"], nthreads=nthreads)
 
 
+DEV = "cuda:0"
+
+
+def make_engine(row, spec, inp):
+  """The row's engine on the GPU with the external inputs of inputs() set; not reset."""
+  from ai_safety_gridworlds_amd.engine import BatchedEngine
+  eng = BatchedEngine(spec, row["n"], device=DEV, outputs=row["outs"])
+  if inp["bits"] is not None or inp["bits_seed"]:
+    eng.set_episode_bits(inp["bits"], seed=inp["bits_seed"])
+  if inp["rand"] is not None or inp["rand_seed"]:
+    eng.set_random_stream(inp["rand"], seed=inp["rand_seed"])
+  if inp["rng"] is not None:
+    eng.set_rng_state(inp["rng"])
+  return eng
+
+
+def start(eng, row):
+  for _ in range(resets(row)):
+    o = eng.reset()
+  return o
+
+
+def to_np(views, stacked):
+  """{field: device tensor} -> {field: numpy [E, S, ...]}; `stacked`: [S, E, ...] (write_every / a list of steps)."""
+  return {k: np.moveaxis(v.cpu().numpy(), 0, 1) if stacked else v.cpu().numpy()[:, None] for k, v in views.items()}
+
+
+def split_views(spec, v):
+  out, off = [], 0
+  for (h, w) in spec.view_shapes:
+    out.append(v[..., off:off + h * w].reshape(v.shape[:-1] + (h, w)))
+    off += h * w
+  return out
+
+
 def resets(row):
   """Resets before the first step: the island_navigation_ex_ma / aintelope_savanna oracles record two (the reference's
   environment resets once when it is built and once more when the episode starts; map randomisation draws at both)."""

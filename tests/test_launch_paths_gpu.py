@@ -14,9 +14,9 @@ from ai_safety_gridworlds_amd import _native as N
 from ai_safety_gridworlds_amd.engine import BatchedEngine, EngineGroup
 from ai_safety_gridworlds_amd.specs import make_spec
 from tests import launch_paths as LP
+from tests.launch_paths import DEV, make_engine, split_views, start, to_np
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 T, CALLS, SEED = 16, 3, 0x1A7C        # T >= step_graphs_min_T (8): the second call of a buffer is captured
 AFTER = 3                             # setter tests: calls after the setter (the stale graph's direct launch, capture, replay)
 
@@ -25,28 +25,6 @@ def steps_of(row):
   """Steps a row's action stream covers: its step_n / replay / rollout calls; groups: CALLS step_n calls, then one rollout;
   setter tests: CALLS calls, then AFTER more."""
   return max(row["calls"], CALLS + 1, CALLS + AFTER) * T
-
-
-def make_engine(row, spec, inp):
-  eng = BatchedEngine(spec, row["n"], device=DEV, outputs=row["outs"])
-  if inp["bits"] is not None or inp["bits_seed"]:
-    eng.set_episode_bits(inp["bits"], seed=inp["bits_seed"])
-  if inp["rand"] is not None or inp["rand_seed"]:
-    eng.set_random_stream(inp["rand"], seed=inp["rand_seed"])
-  if inp["rng"] is not None:
-    eng.set_rng_state(inp["rng"])
-  return eng
-
-
-def start(eng, row):
-  for _ in range(LP.resets(row)):
-    o = eng.reset()
-  return o
-
-
-def to_np(views, stacked):
-  """{field: device tensor} -> {field: numpy [E, S, ...]}; `stacked`: [S, E, ...] (write_every / a list of steps)."""
-  return {k: np.moveaxis(v.cpu().numpy(), 0, 1) if stacked else v.cpu().numpy()[:, None] for k, v in views.items()}
 
 
 _CASES = {}
@@ -90,14 +68,6 @@ def case(row_id):
   ref.close()
   _CASES[row_id] = c
   return c
-
-
-def split_views(spec, v):
-  out, off = [], 0
-  for (h, w) in spec.view_shapes:
-    out.append(v[..., off:off + h * w].reshape(v.shape[:-1] + (h, w)))
-    off += h * w
-  return out
 
 
 def check(c, got, s0, label):
