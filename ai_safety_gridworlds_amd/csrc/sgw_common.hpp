@@ -300,16 +300,19 @@ __host__ __device__ inline Lds lds_carve(uint8_t* smem, const LdsPlan& p, int ex
 
 // tables (2048 bytes = 128 x 16 B) -> LDS in two halves: `issue` only LOADS (unconditionally, index clamped), so the
 // caller can put every other global load of the prologue behind it before anything waits; `commit` writes LDS.
-struct TableStage { uint4 t0, t1; };
+// The halves are plain vector VALUES (not HIP's uint4 class, whose copies are memcpys through a stack slot until the optimiser
+// forwards them): they stay in registers whatever sits between `issue` and `commit` (the kernarg touch is an opaque asm).
+typedef uint32_t TableQuad __attribute__((vector_size(16)));
+struct TableStage { TableQuad t0, t1; };
 template <int THREADS>
 __device__ inline void lds_tables_issue(TableStage& ts, const uint8_t* tables) {
-  const uint4* src = reinterpret_cast<const uint4*>(tables);
+  const TableQuad* src = reinterpret_cast<const TableQuad*>(tables);
   if constexpr (THREADS == WAVE) { ts.t0 = src[threadIdx.x]; ts.t1 = src[threadIdx.x + WAVE]; }
   else { ts.t0 = src[threadIdx.x & (TABLE_BYTES / 16 - 1)]; }
 }
 template <int THREADS>
 __device__ inline void lds_tables_commit(const TableStage& ts, uint8_t* smem) {
-  uint4* dst = reinterpret_cast<uint4*>(smem);
+  TableQuad* dst = reinterpret_cast<TableQuad*>(smem);
   if constexpr (THREADS == WAVE) { dst[threadIdx.x] = ts.t0; dst[threadIdx.x + WAVE] = ts.t1; }
   else { dst[threadIdx.x & (TABLE_BYTES / 16 - 1)] = ts.t0; }   // unconditional (upper threads rewrite the same bytes): no branch for the loads to sink into
 }

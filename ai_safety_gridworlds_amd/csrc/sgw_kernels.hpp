@@ -660,17 +660,18 @@ __device__ inline void accumulate_returns_per_env(const typename F::State& s, co
 // lanes; 16 columns per pass (one pass for C <= 16: every single-agent family and firemaker; island_navigation_ex_ma has
 // 2K + 1 = 17..25).  Deterministic: every accumulator cell has one writer per launch and launches are ordered.  Traffic: one
 // 8-byte RMW per column per 16 envs.
-__device__ inline void accumulate_returns(const KArgs& a, const Lds& l, long long wave_id, long long env0, int lane) {
+// Every one of the wave's 64 rows is staged -- a lane that is not a real env (the ragged end of the batch: it steps and ends
+// episodes like any other) stages exact zeros -- so the reads need no per-row guard: one address per lane and pass, the 16 rows
+// at fixed strides from it.  A lane past the last column reads the last column instead (inside vec_a) and adds nothing.
+__device__ inline void accumulate_returns(const KArgs& a, const Lds& l, long long wave_id, int lane) {
   const int C = a.sp.A * a.sp.K + 1;
   const int part = lane >> 4;
   for (int c0 = 0; c0 < C; c0 += 16) {
     const int col = c0 + (lane & 15);
+    const double* src = l.vec_a + part * 16 * C + (col < C ? col : C - 1);
     double v[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int row = part * 16 + j;
-      v[j] = (col < C && env0 + row < a.n_envs) ? l.vec_a[row * C + col] : 0.0;
-    }
+    for (int j = 0; j < 16; ++j) v[j] = src[j * C];
     // a fixed tree over the part's 16 rows (four add levels instead of a chain of sixteen); the four parts keep their own
     // accumulator rows -- no cross-lane exchange -- and k_read_returns adds the rows up in a fixed order
 #pragma unroll
@@ -716,6 +717,26 @@ template <class F, int KIND> constexpr int env_waves() {
 template <class F, int KIND> constexpr int lds_buffers() { return (pipelined<F, KIND>() && KIND == K_ROLLOUT) ? 2 : 1; }
 template <class F, int KIND> constexpr int wg_threads() { return F::WAVES * env_waves<F, KIND>() * WAVE * (pipelined<F, KIND>() ? 2 : 1); }
 
+// Warm the scalar cache with the launch's whole argument block while the prologue's global loads are in flight.  The bodies
+// read their arguments in several batches, each at its first use and each followed by a wait (SGPR pressure keeps the compiler
+// from hoisting them), and a launch's kernarg segment is cold: every batch that starts a new 64-byte line is a serial miss on a
+// lone wave's critical path, most of them after the staging barrier.  One load per line, all issued at once behind the global
+// loads, then one wait that the state's round trip covers; the later reads hit.  The values are discarded (one scratch SGPR).
+// Bytes [0, END) of the segment: a load every 64 bytes and the last dword, so every line is touched whatever the segment's
+// alignment, and nothing past the last argument byte is read.
+template <int END>
+__device__ __forceinline__ void kernarg_touch() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int LAST = END - 4, N = (LAST + 63) / 64;          // strided loads at 0, 64, ..., (N - 1) * 64 < LAST, then LAST
+  static_assert(END % 4 == 0 && LAST >= 0 && (N - 1) * 64 + 4 <= END && LAST + 4 <= END && LAST - (N - 1) * 64 <= 64,
+                "the touch loads cover every line of the argument block and stay inside it");
+  uint32_t t;
+  asm volatile(".set sgw_touch_off, 0\n\t.rept %c2\n\ts_load_dword %0, %1, sgw_touch_off\n\t.set sgw_touch_off, sgw_touch_off + 64\n\t.endr\n\t"
+               "s_load_dword %0, %1, %c3\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(t) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "i"(N), "i"(LAST) : "memory");
+#endif
+}
+
 #ifdef SGW_WAVES_PER_EU      // experiment: force an occupancy target (registers beyond it go to scratch)
 #define SGW_OCC __attribute__((amdgpu_waves_per_eu(SGW_WAVES_PER_EU, SGW_WAVES_PER_EU)))
 #else
@@ -724,7 +745,9 @@ template <class F, int KIND> constexpr int wg_threads() { return F::WAVES * env_
 // The engine's body: workgroup `block` of a launch whose KArgs block sits `kargs_off` bytes into the kernarg segment (the
 // re-reading paths below go back to it there).  k_engine is this and nothing else; k_engine_group runs it for the member of a
 // heterogeneous launch that the workgroup belongs to.
-template <class F, int KIND>
+// TOUCH_END > 0: the launch's argument block is bytes [0, TOUCH_END) of the kernarg segment and nobody has read it yet
+// (k_engine; k_engine_group has touched its member's block before it gets here).
+template <class F, int KIND, int TOUCH_END = 0>
 __device__ __forceinline__ void engine_body(const KArgs& a, const long long block, const unsigned kargs_off) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int EW = env_waves<F, KIND>();
@@ -764,6 +787,7 @@ __device__ __forceinline__ void engine_body(const KArgs& a, const long long bloc
     const int v = (int)*ap;
     action0[ag] = have ? v : 0;
   }
+  if constexpr (TOUCH_END > 0) kernarg_touch<TOUCH_END>();
   lds_tables_commit<NT>(ts, smem);
   F::init_ctx(cx, l);
   if constexpr (has_init_args<F>::value) F::init_args(cx, l, a);
@@ -800,7 +824,7 @@ __device__ __forceinline__ void engine_body(const KArgs& a, const long long bloc
         const Lds lb = lds_carve(smem, a_step.lp, F::LDS_EXTRA, wv * NB + (NB > 1 ? (t & 1) : 0));
         if (a_step.write_every != 0 || t == TT - 1)
           emit_drain<F>(a_step, lb, env0, lane, a_step.write_every != 0 ? (long long)t * a_step.n_pad : 0, true, true);
-        if (!SGW_ACC_PER_ENV && (a_step.need & LN_RETURNS) && lb.flag[0] != 0u) accumulate_returns(a_step, lb, wave_id, env0, lane);
+        if (!SGW_ACC_PER_ENV && (a_step.need & LN_RETURNS) && lb.flag[0] != 0u) accumulate_returns(a_step, lb, wave_id, lane);
         if (a_step.actions == nullptr && t + 2 < TT) {      // the computing wave read this inbox before the barrier above
 #pragma unroll
           for (int ag = 0; ag < F::NA; ++ag)
@@ -957,8 +981,8 @@ __device__ __forceinline__ void engine_body(const KArgs& a, const long long bloc
         if (acc_any) {
           const StageRow row_a(le.vec_a, le.trash, lane, C);
 #pragma unroll
-          for (int u = 0; u < F::NU; ++u) *row_a.cell(F::slot(ae.sp, u)) = over_now ? s.cum[u] : 0.0;
-          le.vec_a[lane * C + C - 1] = over_now ? 1.0 : 0.0;
+          for (int u = 0; u < F::NU; ++u) *row_a.cell(F::slot(ae.sp, u)) = (over_now && real) ? s.cum[u] : 0.0;
+          le.vec_a[lane * C + C - 1] = (over_now && real) ? 1.0 : 0.0;       // a padded lane's row: zeros (accumulate_returns)
         }
         if constexpr (PIPE) { if (lane == 0) le.flag[0] = acc_any ? 1u : 0u; }
       }
@@ -993,7 +1017,7 @@ __device__ __forceinline__ void engine_body(const KArgs& a, const long long bloc
         emit_small_direct<F>(s, discount, ae, le, env0, lane, ae.write_every != 0 ? (long long)t * ae.n_pad : 0, true);
       }
       SGW_STAMP(ae, 3);
-      if (acc_any) accumulate_returns(ae, le, wave_id, env0, lane);
+      if (acc_any) accumulate_returns(ae, le, wave_id, lane);
     }
     if constexpr (KIND == K_STEP && step_rereads<F>::value) { if (leader) F::store(s, ae, env); return; }
   }
@@ -1043,7 +1067,7 @@ __global__ SGW_OCC __launch_bounds__((wg_threads<F, KIND>())) void k_engine(uint
     static_assert(KIND == K_STEP && !step_rereads<F>::value && !F::PER_AGENT && F::NA == 1 && SH::NSLOT == F::NU, "");
     SH::apply(a.sp);
   }
-  engine_body<F, KIND>(a, (long long)blockIdx.x, SGW_KARGS_OFFSET);
+  engine_body<F, KIND, SGW_KARGS_OFFSET + (int)sizeof(KArgs)>(a, (long long)blockIdx.x, SGW_KARGS_OFFSET);
 }
 
 // ---- heterogeneous launch: several engines (env families) in ONE grid --------------------------------------------------
