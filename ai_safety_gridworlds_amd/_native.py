@@ -57,6 +57,12 @@ class Extras(C.Structure):
               ("done", C.c_void_p), ("replay", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class Episodes(C.Structure):
+  """Mirror of `struct sgw_episodes` (sgw_log_episodes): the caller-owned episode log, device pointers (0 = field not kept)."""
+  _fields_ = [("cap", C.c_int64), ("count", C.c_void_p), ("env", C.c_void_p), ("step", C.c_void_p), ("length", C.c_void_p),
+              ("term_reason", C.c_void_p), ("ret", C.c_void_p), ("hidden", C.c_void_p), ("metrics", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -126,6 +132,11 @@ def lib():
   L.sgw_layer_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
   L.sgw_agent_layer_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
   L.sgw_track_performance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+  if hasattr(L, "sgw_log_episodes"):                        # (as above: an older SGW_LIBRARY build has no episode log)
+    L.sgw_sizeof_episodes.restype = C.c_int
+    L.sgw_episode_scratch_bytes.argtypes = [C.c_int64, C.c_int]
+    L.sgw_episode_scratch_bytes.restype = C.c_int64
+    L.sgw_log_episodes.argtypes = [C.c_void_p, C.POINTER(Out), C.c_int, C.c_int64, C.POINTER(Episodes), C.c_void_p]
   L.sgw_step_full.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Out), C.POINTER(Extras), C.c_void_p]
   L.sgw_sizeof_extras.restype = C.c_int
   L.sgw_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -138,6 +149,8 @@ def lib():
                                                       L.sgw_sizeof_out(), C.sizeof(Out)))
   if L.sgw_sizeof_extras() != C.sizeof(Extras):
     raise SgwError("struct layout mismatch: sgw_extras %d vs %d" % (L.sgw_sizeof_extras(), C.sizeof(Extras)))
+  if hasattr(L, "sgw_log_episodes") and L.sgw_sizeof_episodes() != C.sizeof(Episodes):
+    raise SgwError("struct layout mismatch: sgw_episodes %d vs %d" % (L.sgw_sizeof_episodes(), C.sizeof(Episodes)))
   _lib = L
   return L
 
@@ -147,7 +160,8 @@ EXPORTS = [
     "sgw_destroy", "sgw_n_envs", "sgw_n_pad", "sgw_state_bytes", "sgw_set_episode_bits",
     "sgw_set_rng_state", "sgw_set_random_stream", "sgw_set_family_table", "sgw_pow_f64", "sgw_pow_selfcheck", "sgw_reset", "sgw_step", "sgw_step_n", "sgw_rollout", "sgw_replay", "sgw_group_create", "sgw_group_destroy", "sgw_group_step_n", "sgw_group_rollout", "sgw_read_returns", "sgw_fill_actions",
     "sgw_accumulate_returns", "sgw_observe", "sgw_derived_stats", "sgw_observe_layers", "sgw_state_layers", "sgw_view_bytes", "sgw_agent_views", "sgw_agent_layer_views", "sgw_state_words", "sgw_get_state", "sgw_set_state",
-    "sgw_step_shape", "sgw_layer_coords", "sgw_agent_layer_coords", "sgw_step_lds_bytes"]
+    "sgw_step_shape", "sgw_layer_coords", "sgw_agent_layer_coords", "sgw_step_lds_bytes",
+    "sgw_sizeof_episodes", "sgw_episode_scratch_bytes", "sgw_log_episodes"]
 
 
 def check(rc, what=""):

@@ -28,6 +28,7 @@
 #include "sgw_group.hpp"
 #include "sgw_savanna_layers.hpp"
 #include "sgw_coords.hpp"
+#include "sgw_episodes.hpp"
 
 using namespace sgw;
 
@@ -1230,6 +1231,63 @@ int sgw_track_performance(sgw_engine* e, const double* perf_dev, int n_cols, con
   const int per_agent = (e->spec.family == SGW_ISLAND_NAVIGATION_EX_MA || e->spec.family == SGW_AINTELOPE_SAVANNA) ? 1 : 0;
   hipLaunchKernelGGL(k_track_performance, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, perf_dev, n_cols,
                      step_type_dev, e->spec.A, per_agent, (long long)e->n_envs, last_dev, sum_dev, reinterpret_cast<long long*>(count_dev), done_dev);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+int sgw_sizeof_episodes(void) { return (int)sizeof(sgw_episodes); }
+
+// tiles of 64 envs in T rows of round_up(n_envs, 64); -1 when a wave's 32-bit tile number / a call's 32-bit prefix would not hold
+static long long episode_tiles(long long n_envs, int T) {
+  if (n_envs < 1 || T < 1 || n_envs > 0x7fffffffLL) return -1;
+  const long long tiles = (long long)T * ((n_envs + WAVE - 1) / WAVE);
+  return tiles * WAVE > 0x7fffffffLL ? -1 : tiles;
+}
+
+int64_t sgw_episode_scratch_bytes(int64_t n_envs, int T) {
+  const long long tiles = episode_tiles(n_envs, T);
+  if (tiles < 0) return SGW_ERR_ARG;
+  return (int64_t)sizeof(EpisodeScratch) + 4 * ((tiles + 3) / 4 * 4);
+}
+
+int sgw_log_episodes(sgw_engine* e, const sgw_out* src, int T, int64_t step_base, const sgw_episodes* log, void* stream) {
+  if (!e || !src || !log) return fail(SGW_ERR_ARG, "sgw_log_episodes: null argument");
+  if (!src->step_type || !log->count || !log->scratch) return fail(SGW_ERR_ARG, "sgw_log_episodes: src->step_type, log->count and log->scratch are required");
+  const long long tiles = episode_tiles(e->n_envs, T);
+  if (tiles < 0 || log->cap < 0) return fail(SGW_ERR_ARG, "sgw_log_episodes: bad argument (T >= 1, T * N_pad < 2^31, cap >= 0)");
+  if ((log->length && !src->frame) || (log->term_reason && !src->term_reason) || (log->ret && !src->cumulative) ||
+      (log->hidden && !src->hidden) || (log->metrics && !src->metrics))
+    return fail(SGW_ERR_ARG, "sgw_log_episodes: a destination array is given whose source output is NULL");
+  if (((uintptr_t)log->scratch | (uintptr_t)log->count | (uintptr_t)log->step | (uintptr_t)log->ret | (uintptr_t)log->hidden | (uintptr_t)log->metrics) & 7)
+    return fail(SGW_ERR_ARG, "sgw_log_episodes: scratch, count and the 8-byte arrays must be 8-byte aligned");
+  if (((uintptr_t)log->env | (uintptr_t)log->length) & 3) return fail(SGW_ERR_ARG, "sgw_log_episodes: env and length must be 4-byte aligned");
+  const sgw_spec& sp = e->spec;
+  EpisodeArgs x; memset(&x, 0, sizeof(x));
+  x.step_type = src->step_type; x.term_reason = src->term_reason; x.frame = src->frame;
+  x.cumulative = reinterpret_cast<const unsigned long long*>(src->cumulative);
+  x.hidden = reinterpret_cast<const unsigned long long*>(src->hidden);
+  x.metrics = reinterpret_cast<const unsigned long long*>(src->metrics);
+  x.n = e->n_envs; x.n_pad = e->n_pad; x.step_base = step_base;
+  x.tiles = (unsigned)tiles; x.tiles_per_t = (unsigned)(e->n_pad / WAVE);
+  x.A = sp.A; x.per_agent = (sp.family == SGW_ISLAND_NAVIGATION_EX_MA || sp.family == SGW_AINTELOPE_SAVANNA) ? 1 : 0;
+  x.R = x.per_agent ? sp.A : 1; x.C = sp.A * sp.K; x.M = sp.M;
+  x.recip_C = x.C <= 1 ? 0 : (int)(uint32_t)(((1ull << 32) + x.C - 1) / x.C);      // exact: a span has at most 64 * C elements
+  x.recip_M = x.M <= 1 ? 0 : (int)(uint32_t)(((1ull << 32) + x.M - 1) / x.M);
+  x.cap = log->cap;
+  x.env = log->env; x.step = reinterpret_cast<long long*>(log->step); x.length = log->length; x.reason = log->term_reason;
+  x.ret = x.C > 0 ? reinterpret_cast<unsigned long long*>(log->ret) : nullptr;
+  x.hid = reinterpret_cast<unsigned long long*>(log->hidden);
+  x.met = x.M > 0 ? reinterpret_cast<unsigned long long*>(log->metrics) : nullptr;
+  x.head = static_cast<EpisodeScratch*>(log->scratch);
+  x.tile_num = reinterpret_cast<unsigned*>(x.head + 1);
+  HIP_TRY(hipSetDevice(e->device));
+  const unsigned blocks = (unsigned)((tiles + 3) / 4);                // 4 waves per workgroup, a tile per wave
+  hipLaunchKernelGGL(k_episode_count, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x.step_type, x.tiles, x.tiles_per_t, x.n, x.n_pad,
+                     x.A, x.per_agent, x.tile_num);
+  hipLaunchKernelGGL(k_episode_scan, dim3(1), dim3(EPISODE_SCAN_THREADS), 0, (hipStream_t)stream, x.tile_num, x.tiles, x.head,
+                     reinterpret_cast<long long*>(log->count));
+  if (x.cap > 0 && (x.env || x.step || x.length || x.reason || x.ret || x.hid || x.met))
+    hipLaunchKernelGGL(k_episode_write, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x);
   HIP_TRY(hipGetLastError());
   return SGW_OK;
 }

@@ -1492,11 +1492,18 @@ struct ExtrasArgs {
   const double* perf; int perf_cols, per_agent; const uint8_t* step_type; double* last; double* sum; long long* count; uint8_t* done;
   int lds_planes;                                   // bytes of the planes region (the statistics' rows follow it)
 };
+// Does the output row whose A step-type bytes start at `st` end an episode?  step_type[0] == LAST; for the families whose agents
+// finish one by one (per_agent: island_navigation_ex_ma, aintelope_savanna) every agent LAST or DEAD.  The one predicate of the
+// performance bookkeeping below and of the episode log (sgw_episodes.hpp).
+__device__ __forceinline__ bool episode_ended(const uint8_t* st, int A, int per_agent) {
+  bool done = st[0] == ST_LAST;
+  if (per_agent) { done = true; for (int ag = 0; ag < A; ++ag) done = done && st[ag] >= ST_LAST; }
+  return done;
+}
 __device__ inline void track_performance_item(long long i, const double* perf, int C, const uint8_t* step_type, int A, int per_agent, double* last,
                                               double* sum, long long* count, uint8_t* done_out) {
   const long long e = i / C;
-  bool done = step_type[e * A] == ST_LAST;
-  if (per_agent) { done = true; for (int ag = 0; ag < A; ++ag) done = done && step_type[e * A + ag] >= ST_LAST; }
+  const bool done = episode_ended(step_type + e * A, A, per_agent);
   if (done_out && i == e * C) done_out[e] = done ? 1 : 0;
   if (!done) return;
   const double v = perf[i];

@@ -58,6 +58,86 @@ def _view_bytes(spec):
   return int(sum(h * w for (h, w) in (getattr(spec, "view_shapes", None) or ())))
 
 
+class EpisodeLog(object):
+  """A device-side, append-only log of finished episodes (sgw_log_episodes): the reference's _episodic_performances
+  (safety_game.py:253-263) for a whole batch, one record per episode in the order (step, env), with
+
+      env int32 [cap], step int64 [cap], length int32 [cap], term_reason uint8 [cap] ([cap, A] where agents finish one by one),
+      ret float64 [cap, A*K], hidden float64 [cap], metrics float64 [cap, M]
+
+  for the `fields` asked for.  The log owns these tensors, the device counter and the launch's scratch (grown to the largest T
+  logged).  Appending (BatchedEngine.log_episodes) never synchronises; `count()` is the one method that does.  Records beyond
+  `cap` are counted but not stored (`overflowed()`)."""
+
+  FIELDS = ("env", "step", "length", "term_reason", "ret", "hidden", "metrics")
+  SOURCE = {"length": "frame", "term_reason": "term_reason", "ret": "cumulative", "hidden": "hidden", "metrics": "metrics"}
+
+  @staticmethod
+  def layout_of(spec):
+    """(A, K, M, R): what decides the record's shape."""
+    return (spec.A, spec.K, spec.M, spec.A if getattr(spec, "per_agent", False) else 1)
+
+  def __init__(self, engine, cap, fields=FIELDS):
+    self.fields = tuple(fields)
+    for f in self.fields:
+      if f not in self.FIELDS:
+        raise KeyError("unknown episode-log field %r" % (f,))
+    self.cap = int(cap)
+    if self.cap < 0:
+      raise ValueError("cap must be >= 0")
+    self.device, self.n_envs, self.layout = engine.device, engine.n_envs, self.layout_of(engine.spec)
+    if self.device.type != "cuda" or not torch.cuda.is_available():
+      raise N.SgwError("EpisodeLog needs a HIP device (got %r); there is no CPU path" % (self.device,))
+    self._lib = engine._lib
+    A, K, M, R = self.layout
+    shapes = {"env": (torch.int32, ()), "step": (torch.int64, ()), "length": (torch.int32, ()), "term_reason": (torch.uint8, (R,)),
+              "ret": (torch.float64, (A * K,)), "hidden": (torch.float64, ()), "metrics": (torch.float64, (M,))}
+    self._t = {f: torch.zeros((self.cap,) + shapes[f][1], dtype=shapes[f][0], device=self.device) for f in self.fields}
+    self._count = torch.zeros(1, dtype=torch.int64, device=self.device)
+    self._scratch, self._scratch_T = None, 0
+    self._x = N.Episodes()
+    self._x.cap, self._x.count = self.cap, self._count.data_ptr()
+    for f in self.fields:
+      if self.cap > 0 and self._t[f].numel() > 0:
+        setattr(self._x, f, self._t[f].data_ptr())
+
+  def _struct(self, T):
+    """The sgw_episodes of this log with scratch for T rows of the engine's envs."""
+    if T > self._scratch_T:
+      nbytes = int(self._lib.sgw_episode_scratch_bytes(self.n_envs, int(T)))
+      if nbytes < 0:
+        raise N.SgwError("sgw_episode_scratch_bytes(%d, %d) refused" % (self.n_envs, T))
+      self._scratch, self._scratch_T = torch.empty(nbytes, dtype=torch.uint8, device=self.device), int(T)
+      self._x.scratch = self._scratch.data_ptr()
+    return self._x
+
+  def clear(self):
+    """Forget every record (zeroes the device counter; no synchronisation)."""
+    self._count.zero_()
+
+  def count(self):
+    """Episodes logged so far, including those that did not fit.  Synchronises."""
+    return int(self._count.item())
+
+  def overflowed(self):
+    return self.count() > self.cap
+
+  def records(self):
+    """{field: tensor [n, ...]} of the n = min(count, cap) stored records, views of the log's tensors; `ret` is [n, A, K] when
+    A > 1, `term_reason` [n] unless agents finish one by one."""
+    n = min(self.count(), self.cap)
+    A, K, M, R = self.layout
+    out = {}
+    for f in self.fields:
+      v = self._t[f][:n]
+      if f == "ret" and A > 1:
+        v = v.reshape(n, A, K)
+      elif f == "term_reason" and R == 1:
+        v = v.reshape(n)
+      out[f] = v
+    return out
+
+
 class BatchedEngine(object):
 
   def __init__(self, spec, n_envs, device="cuda:0", env_id_base=0, outputs=DEFAULT_OUTPUTS):
@@ -471,6 +551,44 @@ class BatchedEngine(object):
     N.check(self._lib.sgw_agent_layer_coords(self._h, ptr, L, idx, cap, counts.data_ptr(), coords.data_ptr(), self._stream()),
             "sgw_agent_layer_coords")
     return [(counts[:, a], coords[:, a]) for a in range(len(shapes))]
+
+  def log_episodes(self, log, outputs=None, step_base=0):
+    """Append one record per episode that ends in the engine's current output buffers to `log` (an EpisodeLog), in (t, n) order:
+    the [N_pad] buffers of a step, or the [T, N_pad] buffers of step_n / rollout / replay with write_every, row t logged as step
+    `step_base + t`.  One library call (sgw_log_episodes): no host synchronisation, no allocation once the log's scratch has seen
+    this T, capturable.  outputs: a {name: tensor} dict of padded [N_pad, ...] or [T, N_pad, ...] buffers to log from instead
+    (e.g. kept copies of the engine's).  Every field the log keeps needs its output: SgwError otherwise.  There is no CPU path."""
+    if not isinstance(log, EpisodeLog):
+      raise N.SgwError("log_episodes: needs an EpisodeLog (there is no CPU path)")
+    if self._h is None:
+      raise N.SgwError("log_episodes: the engine has no device engine behind it (closed?); there is no CPU path")
+    if log.n_envs != self.n_envs or log.device != self.device or log.layout != EpisodeLog.layout_of(self.spec):
+      raise N.SgwError("log_episodes: the log was made for another engine (envs, device or record layout differ)")
+    if outputs is None:
+      bufs, out, T = self._bufs, self._out, self._T
+    else:
+      bufs, out = dict(outputs), N.Out()
+      st = bufs.get("step_type")
+      rows = st.numel() // self.spec.A if torch.is_tensor(st) else 0
+      if rows < self.n_pad or rows % self.n_pad:
+        raise N.SgwError("log_episodes: outputs['step_type'] must be a padded [N_pad, A] or [T, N_pad, A] buffer")
+      T = rows // self.n_pad
+      for name, t in bufs.items():
+        if name not in N.OUT_FIELDS:
+          raise KeyError("unknown output %r" % name)
+        dt, shp = _dtype_shape(self.spec, name)
+        if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or not t.is_contiguous()
+            or t.numel() != rows * int(np.prod(shp, dtype=np.int64))):
+          raise N.SgwError("log_episodes: outputs[%r] must be a contiguous %s buffer of %d rows on %s" % (name, dt, rows, self.device))
+        setattr(out, name, t.data_ptr())
+    for f in log.fields:
+      need = EpisodeLog.SOURCE.get(f)
+      if need is not None and need not in bufs:
+        raise N.SgwError("log_episodes: the log keeps %r, which needs the %r output" % (f, need))
+    if "step_type" not in bufs:
+      raise N.SgwError("log_episodes: needs the 'step_type' output")
+    N.check(self._lib.sgw_log_episodes(self._h, C.byref(out), T, int(step_base), C.byref(log._struct(T)), self._stream()),
+            "sgw_log_episodes")
 
   def observe(self, board=None, rgb=True, layer_chars=None):
     """RGB uint8 [N, 3, H, W] and/or occluded layers uint8 [N, L, H, W] of a rendered ascii board."""

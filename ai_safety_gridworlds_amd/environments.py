@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .engine import BatchedEngine, ALL_OUTPUTS
+from .engine import BatchedEngine, EpisodeLog, ALL_OUTPUTS
 from .specs import make_spec
 
 
@@ -40,16 +40,23 @@ class TimeStep(collections.namedtuple("TimeStep", ["step_type", "reward", "disco
 
 class BatchedSafetyEnvironment(object):
 
-  def __init__(self, env_name, num_envs=1, device="cuda:0", env_id_base=0, outputs=None, track_performance=True, **kwargs):
+  def __init__(self, env_name, num_envs=1, device="cuda:0", env_id_base=0, outputs=None, track_performance=True, episode_log=None,
+               **kwargs):
     self.env_name = env_name
     self._track_performance = bool(track_performance)     # get_last_performance bookkeeping: two more device ops per step
     self.spec = make_spec(env_name, **kwargs)
     self.num_envs = int(num_envs)
     if outputs is None:        # everything the family produces ('safety2_<agent>' exists in aintelope_savanna only)
       outputs = ALL_OUTPUTS + (("safety2",) if self.spec.name == "aintelope_savanna" else ())
+    if episode_log is not None:       # the log's sources are asked for too
+      outputs = tuple(dict.fromkeys(tuple(outputs) + ("step_type",) + tuple(EpisodeLog.SOURCE.values())))
     self.engine = BatchedEngine(self.spec, self.num_envs, device=device, env_id_base=env_id_base,
                                 outputs=outputs)
     self.device = self.engine.device
+    # episode_log=cap: every step() appends the episodes it ended to a device-side EpisodeLog of `cap` records (one more library
+    # call per step, no torch op, no synchronisation); None: no log, no buffer, nothing changes
+    self.episode_log = None if episode_log is None else EpisodeLog(self.engine, int(episode_log))
+    self._steps = 0                   # steps taken so far: the `step` of the records
     self._last = None
     self._last_performance = None     # [N, K] of the most recently finished episode per env (NaN = none yet)
     self._performance_sum = None      # [N, K] running sum over the env's finished episodes; _episodes int64 [N] their number
@@ -104,7 +111,26 @@ class BatchedSafetyEnvironment(object):
   def step(self, actions):
     if not torch.is_tensor(actions):
       actions = torch.as_tensor(np.asarray(actions).reshape(-1), dtype=torch.int8)
-    return self._timestep(self.engine.step(actions))
+    o = self.engine.step(actions)
+    self._log_step()
+    return self._timestep(o)
+
+  def _log_step(self):
+    """After a step (the wrappers that call the engine themselves come here too): append the episodes it ended."""
+    if self.episode_log is not None:
+      self.engine.log_episodes(self.episode_log, step_base=self._steps)
+      self._steps += 1
+
+  def episodic_performances(self):
+    """The reference's _episodic_performances (safety_game.py:253-263) as ONE list for the whole batch, in the order the episodes
+    ended: (env int32 [n], performance float64 [n, cols]) from the source get_last_performance uses (hidden performance, or the
+    episode return).  Needs episode_log; synchronises (EpisodeLog.count)."""
+    if self.episode_log is None:
+      raise N.SgwError("episodic_performances needs episode_log=<cap> at construction")
+    rec = self.episode_log.records()
+    name, cols = self._perf_source(self.engine._bufs)
+    perf = rec["hidden"] if name == "hidden" else rec["ret"]
+    return rec["env"], perf.reshape(perf.shape[0], cols)
 
   def get_last_performance(self, default=None):
     """Per env: performance of the last finished episode (safety_game.py:229-251); NaN rows = none yet."""

@@ -427,7 +427,7 @@ class GridworldVectorEnv(object):
 
   def __init__(self, env_name, num_envs, device="cuda:0", env_id_base=0,
                outputs=("board", "obs_board", "reward", "cumulative", "step_type", "term_reason", "hidden"), full_info=False,
-               replay_graph=False, object_coordinates=False, coordinates_cap=None, **kwargs):
+               replay_graph=False, object_coordinates=False, coordinates_cap=None, episode_log=None, **kwargs):
     self._full = bool(full_info)
     self._coords = bool(object_coordinates)
     self._coords_cap = coordinates_cap
@@ -440,7 +440,8 @@ class GridworldVectorEnv(object):
     else:
       outputs = tuple(dict.fromkeys(tuple(outputs) + ("done",)))       # `terminated` comes out of the step launch itself
     self._env = BatchedSafetyEnvironment(env_name, num_envs=num_envs, device=device, env_id_base=env_id_base,
-                                         outputs=outputs, track_performance=False, **kwargs)
+                                         outputs=outputs, track_performance=False, episode_log=episode_log, **kwargs)
+    self.episode_log = self._env.episode_log      # episode_log=cap: an EpisodeLog every step appends to (None: no log)
     self.spec_ = self._env.spec
     self.num_envs = num_envs
     self.layers_order = list(self.spec_.layer_chars)
@@ -467,6 +468,7 @@ class GridworldVectorEnv(object):
     # a step from Python is host-bound: the outputs live in persistent buffers (and `terminated` is the launch's `done` output),
     # so the returned views are built once and a step is the library call alone (12.3 -> 8.9 us per step at 65 536 envs)
     o = self._env.engine.step(actions)
+    self._env._log_step()
     self._env._last = o
     c = self._lean
     if c is None or c["_for"] is not o["step_type"]:
@@ -483,6 +485,7 @@ class GridworldVectorEnv(object):
     and a step is one library call plus one comparison."""
     o = self._env.engine.step_full(actions, rgb=True, layers=hasattr(self.spec_, "drape_chars"), stats=not self.spec_.scalar, performance=True,
                                    replay=self._replay)
+    self._env._log_step()
     self._env._last = o
     if self._coords:                         # one more launch into persistent buffers (the launch writes the lists only)
       self._coords_out = self._env.engine.layer_coords(layers=o.get("layers"), cap=self._coords_cap, out=self._coords_out)

@@ -45,7 +45,7 @@ class GridworldZooVectorEnv(object):
   metadata = {"name": "ai_safety_gridworlds_amd_vector"}
 
   def __init__(self, env_name, num_envs, ascii_observation_format=True, layers_in_observation=False, seed=None, device="cuda:0",
-               env_id_base=0, object_coordinates=False, coordinates_cap=None, **kwargs):
+               env_id_base=0, object_coordinates=False, coordinates_cap=None, episode_log=None, **kwargs):
     self._fused = fused_views(make_spec(env_name, **kwargs))
     self._ascii = bool(ascii_observation_format)
     cfg0 = getattr(make_spec(env_name, **kwargs), "config", None) or {}
@@ -53,7 +53,8 @@ class GridworldZooVectorEnv(object):
     # `terminated` and the decoded directions leave with the step launch (sgw_out.done / obs_dir / act_dir): no torch launch per step
     outs = OUTS + (("obs_dir", "act_dir") if self._turning else ()) + ((("views",) if self._ascii else ("obs_views",)) if self._fused else ())
     self._env = BatchedSafetyEnvironment(env_name, num_envs=num_envs, device=device, env_id_base=env_id_base, outputs=outs,
-                                         track_performance=False, **kwargs)
+                                         track_performance=False, episode_log=episode_log, **kwargs)
+    self.episode_log = self._env.episode_log                   # episode_log=cap: an EpisodeLog every step appends to (None: no log)
     sp = self.spec_ = self._env.spec
     if sp.A < 2 and not getattr(sp, "per_agent", False):
       raise NotImplementedError("%s is a single-agent env: use GridworldVectorEnv" % env_name)
@@ -182,5 +183,6 @@ class GridworldZooVectorEnv(object):
           col.fill_(int(v))
       acts = self._acts
     o = self._env.engine.step(acts.reshape(-1) if sp.A == 1 else acts)
+    self._env._log_step()
     self._env._last = o
     return self._pack(o)

@@ -298,6 +298,38 @@ int sgw_derived_stats(sgw_engine* e, const double* reward_dev, const double* cum
 int sgw_track_performance(sgw_engine* e, const double* perf_dev, int n_cols, const uint8_t* step_type_dev, double* last_dev,
                           double* sum_dev, int64_t* count_dev, uint8_t* done_dev, void* stream);
 
+/* The episode log: one record per episode that ENDS in a batch of output rows, appended to a caller-owned log in (t, n) order --
+ * the reference's _episodic_performances (safety_game.py:253-263, safety_game_mo.py:1015-1016) for the whole batch, with the
+ * env, the step, the length, the termination reason, the return vector, the hidden performance and the metrics of the row that
+ * was LAST.  With envs that auto-reset inside the launch those numbers are overwritten one step later; this is how they are
+ * kept without [T, N_pad, ...] trajectory buffers and without a host synchronisation per step.
+ *
+ * src is the sgw_out the steps wrote: T == 1: plain [N_pad, ...] arrays; T > 1: the rollout-buffer layout [T, N_pad, ...] of
+ * sgw_step_n / sgw_rollout / sgw_replay with write_every != 0.  Rows >= N are never logged.  Row (t, n) ends an episode by the
+ * predicate of sgw_track_performance: step_type[n, 0] == LAST, or every agent LAST or DEAD for island_navigation_ex_ma and
+ * aintelope_savanna (that predicate holds again on an idle round after the end -- every submitted action < 0, no reset -- and
+ * such a row is logged again, as sgw_track_performance counts it again).
+ * The records of one call are appended at *count in (t, n) order and calls append in stream order: the log is a deterministic
+ * function of the inputs.  *count advances by the TRUE number of ended episodes; records at index >= cap are not stored and
+ * entries past min(*count, cap) are never written.  src->step_type, log->count and log->scratch are required; every other
+ * destination may be NULL (cap == 0 with all of them NULL: the pure counter); a destination whose source output is NULL is
+ * SGW_ERR_ARG.  Three plain launches on the caller's stream: no host synchronisation, no allocation, no read-back, capturable. */
+typedef struct sgw_episodes {     /* destination: a caller-owned append-only log, all device pointers */
+  int64_t  cap;          /* records the arrays below can hold (>= 0) */
+  int64_t* count;        /* [1] episodes logged so far, INCLUDING those that did not fit; the caller zeroes it to start or clear */
+  int32_t* env;          /* [cap]        env index within the engine (global id = env_id_base + env) */
+  int64_t* step;         /* [cap]        step_base + t of the row that was LAST */
+  int32_t* length;       /* [cap]        the `frame` output of that row (the episode's length) */
+  uint8_t* term_reason;  /* [cap, R]     R = A for the families whose agents finish one by one, else 1 */
+  double*  ret;          /* [cap, A*K]   the `cumulative` output of that row: the episode return vector(s) */
+  double*  hidden;       /* [cap]        the `hidden` output of that row: hidden performance */
+  double*  metrics;      /* [cap, M] */
+  void*    scratch;      /* sgw_episode_scratch_bytes(n_envs, T) bytes, 8-byte aligned; contents are the call's own */
+} sgw_episodes;
+int sgw_sizeof_episodes(void);
+int64_t sgw_episode_scratch_bytes(int64_t n_envs, int T);   /* pure host arithmetic, no device; < 0 = SGW_ERR_ARG */
+int sgw_log_episodes(sgw_engine* e, const sgw_out* src, int T, int64_t step_base, const sgw_episodes* log, void* stream);
+
 /* Everything env.step() returns from ONE host call: sgw_step, then -- on the same stream, chained in C -- whatever of the
  * observation distiller's and _process_timestep's derived outputs `extras` asks for, computed from that step's outputs:
  * RGB (sgw_observe), unoccluded layers (sgw_observe_layers; aintelope_savanna: sgw_state_layers), derived statistics
