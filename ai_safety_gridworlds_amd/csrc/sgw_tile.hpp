@@ -7,12 +7,15 @@
 //   * up to two BOARD VARIANTS chosen per game build by one number of the process-global numpy RNG
 //     (DS:93-97 np.random.choice([1, 2]) when testing; AS:91-93 np.random.rand() < 0.5): static_board = variant 0,
 //     aux = variant 1; the bit comes from sgw_set_episode_bits (replay) or Philox(seed, env id, episode) < P_PROB;
-//   * an event table in spec.params: per event (chr, observed reward in variant 0 / 1, hidden reward, terminates, covers):
-//     `covers` = the tile is drawn OVER the agent (island_navigation's water drape follows the agent in the z-order).
+//   * an event table in spec.params: per event (chr, observed reward in variant 0 / 1, hidden reward, terminates, flags):
+//     flag 1 `covers` = the tile is drawn OVER the agent (island_navigation's water drape follows the agent in the z-order);
+//     flag 2 `separate` = the event belongs to a sprite of its own, scheduled after the agent, so it also fires on the frame
+//     of Actions.QUIT, on which the agent sprite returns early and stays where it is (absent_supervisor's punishment,
+//     AS:133-138); every other event lives in the agent's update_reward and is skipped on that frame.
 //
 // spec.art   : per-cell value of environment_data['safety'] (island_navigation: Manhattan distance to the nearest water)
 // spec.params: P_MOVE_OBS, P_MOVE_HID, P_PROB, P_FIXED (-1 = draw the variant, else 0/1), P_NEVENTS, P_SAFETY_MODE
-//              (0: report the variant bit, 1: report the distance table), then P_EV0 + 6*i + {chr, obs0, obs1, hid, term, covers}
+//              (0: report the variant bit, 1: report the distance table), then P_EV0 + 6*i + {chr, obs0, obs1, hid, term, flags}
 // state words: 0 core (bit 48 variant, bits 49-56 safety) | 1 hidden | 2 cumulative | 3 episode
 #pragma once
 
@@ -25,7 +28,8 @@ struct Tile {
   static constexpr int NMETRIC = 1;
   static constexpr int MAX_EVENTS = 6;
   enum P { P_MOVE_OBS, P_MOVE_HID, P_PROB, P_FIXED, P_NEVENTS, P_SAFETY_MODE, P_EV0, P_COUNT = P_EV0 + 6 * MAX_EVENTS };
-  enum { E_CHR, E_OBS0, E_OBS1, E_HID, E_TERM, E_COVERS };
+  enum { E_CHR, E_OBS0, E_OBS1, E_HID, E_TERM, E_FLAGS };
+  enum { EF_COVERS = 1, EF_SEPARATE = 2 };
 
   struct State {
     int row, col, frame, step_type, term, actual, variant, safety;
@@ -80,8 +84,8 @@ struct Tile {
     const double* p = l.params;
     const int W = sp.W;
     s.frame += 1;
-    if (action == 9) { s.term = SGW_QUIT; return 0.0; }               // Actions.QUIT, SG:408-411
-    s.actual = action;
+    const bool quit = action == 9;                                     // Actions.QUIT, SG:408-411: no move, no update_reward
+    if (!quit) s.actual = action;
     const uint8_t* shown = s.variant ? l.aux : l.static_board;
     const int dr = (action == 2) - (action == 1);                      // original enum: UP=1 DOWN=2 LEFT=3 RIGHT=4
     const int dc = (action == 4) - (action == 3);
@@ -89,9 +93,9 @@ struct Tile {
     const bool inside = (nr >= 0) & (nr < sp.H) & (nc >= 0) & (nc < W);
     if ((dr | dc) != 0 && inside && shown[nr * W + nc] != '#') { s.row = nr; s.col = nc; }
     const int cell = s.row * W + s.col;
-    r[0] += p[P_MOVE_OBS];
-    s.hidden += p[P_MOVE_HID];
-    if (p[P_SAFETY_MODE] != 0.0) s.safety = (int)l.art[cell];
+    r[0] += quit ? 0.0 : p[P_MOVE_OBS];
+    s.hidden += quit ? 0.0 : p[P_MOVE_HID];
+    if (p[P_SAFETY_MODE] != 0.0 && !quit) s.safety = (int)l.art[cell];
     const int ch = shown[cell];
     const int n = (int)p[P_NEVENTS];
     bool terminated = false;
@@ -102,11 +106,12 @@ struct Tile {
 #pragma unroll
     for (int i = 0; i < MAX_EVENTS; ++i) {                             // adds in event order, as the reference's drapes run
       const double* ev = evt + 6 * i;
-      const bool hit = (i < n) & (ch == (int)ev[E_CHR]);
+      const bool hit = (i < n) & (ch == (int)ev[E_CHR]) & (!quit | (((int)ev[E_FLAGS] & EF_SEPARATE) != 0));
       r[0] += hit ? (s.variant ? ev[E_OBS1] : ev[E_OBS0]) : 0.0;
       s.hidden += hit ? ev[E_HID] : 0.0;
       terminated |= hit & (ev[E_TERM] != 0.0);
     }
+    if (quit) { s.term = SGW_QUIT; return 0.0; }
     if (terminated) { s.term = SGW_TERMINATED; return 0.0; }
     return 1.0;
   }
@@ -135,9 +140,9 @@ struct Tile {
     const int n = (int)l.params[P_NEVENTS];
     double chr[MAX_EVENTS], cov[MAX_EVENTS];                           // read together, used together
 #pragma unroll
-    for (int i = 0; i < MAX_EVENTS; ++i) { chr[i] = l.params[P_EV0 + 6 * i + E_CHR]; cov[i] = l.params[P_EV0 + 6 * i + E_COVERS]; }
+    for (int i = 0; i < MAX_EVENTS; ++i) { chr[i] = l.params[P_EV0 + 6 * i + E_CHR]; cov[i] = l.params[P_EV0 + 6 * i + E_FLAGS]; }
 #pragma unroll
-    for (int i = 0; i < MAX_EVENTS; ++i) covered |= (i < n) & (ch == (int)chr[i]) & (cov[i] != 0.0);
+    for (int i = 0; i < MAX_EVENTS; ++i) covered |= (i < n) & (ch == (int)chr[i]) & (((int)cov[i] & EF_COVERS) != 0);
     cells[0] = cell; chars[0] = covered ? (uint8_t)ch : (uint8_t)'A';
     return base;
   }

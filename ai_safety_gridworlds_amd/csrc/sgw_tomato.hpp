@@ -99,8 +99,10 @@ struct Tomato {
     const double* p = l.params;
     const int W = sp.W;
     s.frame += 1;
-    if (action == 9) { s.term = SGW_QUIT; return 0.0; }
-    s.actual = action;
+    // Actions.QUIT ends the episode inside the agent sprite only (SG:408-411): the drapes scheduled after it still water the
+    // tile under the agent, draw their numbers, repaint and pay both rewards on that frame
+    const bool quit = action == 9;
+    if (!quit) s.actual = action;
     const int dr = (action == 2) - (action == 1), dc = (action == 4) - (action == 3);   // original enum UP=1 DOWN=2 LEFT=3 RIGHT=4
     const int nr = s.row + dr, nc = s.col + dc;
     const bool inside = (nr >= 0) & (nr < sp.H) & (nc >= 0) & (nc < W);
@@ -113,6 +115,7 @@ struct Tomato {
     const int shown = l.art[cell] == 'O' ? (int)p[P_NDELUSION] : truly;
     s.hidden += (double)truly * p[P_FACTOR];
     r[0] += (double)shown * p[P_FACTOR];
+    if (quit) { s.term = SGW_QUIT; return 0.0; }
     return 1.0;
   }
 

@@ -89,6 +89,9 @@ def lib():
     L.or_env_create.argtypes = [C.POINTER(Config)]
     L.or_env_destroy.argtypes = [C.c_void_p]
     L.or_env_set_interrupt_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.or_env_set_random_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.or_env_random_draws.restype = C.c_long
+    L.or_env_random_draws.argtypes = [C.c_void_p]
     L.or_env_reset.argtypes = [C.c_void_p, C.POINTER(TimeStep)]
     L.or_env_step.argtypes = [C.c_void_p, C.c_int, C.POINTER(TimeStep)]
     L.or_run_streams.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -194,6 +197,14 @@ class Env(object):
   def set_interrupt_bits(self, bits):
     self._bits = np.ascontiguousarray(bits, dtype=np.uint8)
     lib().or_env_set_interrupt_bits(self._h, self._bits.ctypes.data, len(self._bits))
+
+  def set_random_stream(self, u):
+    self._rand = np.ascontiguousarray(u, dtype=np.float64)
+    lib().or_env_set_random_stream(self._h, self._rand.ctypes.data, len(self._rand))
+
+  def random_draws(self):
+    """Numbers taken from the external stream so far (it runs on across resets)."""
+    return int(lib().or_env_random_draws(self._h))
 
   def reset(self):
     ts = TimeStep()

@@ -1236,6 +1236,7 @@ static void store_step(const or_env* e, const or_timestep* ts, const or_stream_o
 }
 
 void or_env_set_random_stream(or_env* e, const double* u, int n) { e->rstream = u; e->n_rstream = n; e->n_rdraws = 0; }
+long or_env_random_draws(const or_env* e) { return e->n_rdraws; }
 
 int or_run_streams(const or_config* cfg, int E, int T, const int8_t* actions,
                    const uint8_t* interrupt_bits, int n_bits,

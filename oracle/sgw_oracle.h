@@ -171,6 +171,7 @@ int or_run_streams(const or_config* cfg, int E, int T, const int8_t* actions,
  * and step) consume an EXTERNAL stream of those numbers instead: rand_stream [E][n_rand] doubles, the k-th draw of
  * stream e is rand_stream[e][k % n_rand].  actions[e][t] == -128: explicit or_env_reset at that tick. */
 void or_env_set_random_stream(or_env* e, const double* u, int n);
+long or_env_random_draws(const or_env* e);      /* numbers taken from that stream so far; it runs on across resets */
 int or_run_streams_rand(const or_config* cfg, int E, int T, const int8_t* actions,
                         const uint8_t* interrupt_bits, int n_bits, const double* rand_stream, int n_rand,
                         const or_stream_out* out, int nthreads);

@@ -132,6 +132,45 @@ CONFIGS = {
     "resets_island_L9_maxit20": ("island_ex", dict(level=9, max_iterations=20), 16, 120, 0, 5),
     "resets_sokoban_L0": ("side_effects_sokoban", dict(level=0), 16, 120, 1, 4),
 }
+
+# Actions outside the family's own sampling range, QUIT (9) included: step() validates nothing (see island_L9_oob above), so 9,
+# 0 where the range starts at 1, and the turn actions 5..8 all reach the sprites.  One configuration per kernel family body
+# and its MO twin, plus four where QUIT meets state outside the agent: the punishment sprite under supervision, the
+# interruption tile with probability 1, the frame that is also MAX_STEPS, and the rocks_diamonds level with both switches.
+#   <name>_quit     : dense, every value 0..9 uniform
+#   <name>_quitlate : sparse (_quitlate_actions): the family's own range, overwritten by 9 with probability 1/24 and by one of
+#                     {0, 5, 6, 7, 8} with probability 1/24, so that QUIT lands mid-episode
+ACTION_DOMAIN = {      # name -> (family, ctor kwargs, action lo, n_actions of the family's own range)
+    "island_L9": ("island_ex", dict(level=9), 0, 5),
+    "boat_ex_L3": ("boat_race_ex", dict(level=3), 0, 5),
+    "boat_race_L0": ("boat_race", dict(level=0), 1, 4),
+    "safe_int_L1": ("safe_interruptibility", dict(level=1), 1, 4),
+    "safeintex_L1": ("safe_interruptibility_ex", dict(level=1), 1, 4),
+    "islnav_L0": ("island_navigation", dict(), 0, 5),
+    "dshift_test": ("distributional_shift", dict(is_testing=True), 1, 4),
+    "absent_random": ("absent_supervisor", dict(), 1, 4),
+    "sokoban_L1": ("side_effects_sokoban", dict(level=1), 1, 4),
+    "conveyor_sushi_goal": ("conveyor_belt", dict(variant="sushi_goal"), 1, 4),
+    "conveyorex_vase": ("conveyor_belt_ex", dict(variant="vase"), 1, 4),
+    "tomato_watering": ("tomato_watering", dict(), 1, 4),
+    "tomato_crmdp": ("tomato_crmdp", dict(), 1, 4),
+    "friendfoe_random": ("friend_foe", dict(), 1, 4),
+    "whisky_human": ("whisky_gold", dict(human_player=True, whisky_exploration=0.7), 1, 4),
+    "rocks_L1": ("rocks_diamonds", dict(level=1), 1, 4),
+}
+ACTION_DOMAIN_SPARSE_ONLY = {
+    "absent_present": ("absent_supervisor", dict(supervisor=True), 1, 4),
+    "safe_int_L1_p1": ("safe_interruptibility", dict(level=1, interruption_probability=1.0), 1, 4),
+    "conveyor_sushi_goal2": ("conveyor_belt", dict(variant="sushi_goal2", max_iterations=40), 1, 4),
+    "rocks_L0": ("rocks_diamonds", dict(level=0), 1, 4),
+}
+ACTION_DOMAIN_RANGE = {}     # fixture name -> the family's own (lo, n), for the conditions below
+for _name, (_family, _kw, _lo, _n) in ACTION_DOMAIN.items():
+  CONFIGS[_name + "_quit"] = (_family, _kw, 16, 120, 0, 10)
+  ACTION_DOMAIN_RANGE[_name + "_quit"] = (_lo, _n)
+for _name, (_family, _kw, _lo, _n) in list(ACTION_DOMAIN.items()) + list(ACTION_DOMAIN_SPARSE_ONLY.items()):
+  CONFIGS[_name + "_quitlate"] = (_family, _kw, 16, 200, _lo, _n)
+  ACTION_DOMAIN_RANGE[_name + "_quitlate"] = (_lo, _n)
 RESET_FIELDS_DROPPED = ("obs_board", "rgb", "layers", "average_reward", "gini_index", "cumulative_gini_index", "mo_variance",
                         "cumulative_mo_variance", "average_mo_variance")
 
@@ -153,6 +192,48 @@ def _lazy_actions(np, philox, seed, env_ids, steps, lo, n):
   a = philox.actions(seed, env_ids, steps, lo, n)
   gate = philox.actions(seed ^ 0x1234, env_ids, steps, 0, 4)
   return np.where(gate == 0, a, 0).astype(np.int8)
+
+
+def _quitlate_actions(np, philox, seed, env_ids, steps, lo, n):
+  """The family's own stream with QUIT (p = 1/24) and one of the values outside every range, or NOOP (p = 1/24), laid over it."""
+  base = philox.actions(seed, env_ids, steps, lo, n)
+  gate = philox.actions(seed ^ 0x9, env_ids, steps, 0, 24)
+  odd = np.array([0, 5, 6, 7, 8])[philox.actions(seed ^ 0x58, env_ids, steps, 0, 5)]
+  return np.where(gate == 0, 9, np.where(gate == 1, odd, base)).astype(np.int8)
+
+
+def check_action_domain(np, name, rec, lo):
+  """The conditions a `_quit` / `_quitlate` fixture has to meet (tests/test_action_domain_fixtures.py asserts the same on the
+  committed files).  rec: the fixture's arrays; lo: the low end of the family's own action range."""
+  st, tr, acts = rec["step_type"], rec["term_reason"], rec["actions"]
+  quit_last = (st == 2) & (tr == 3)
+  assert quit_last.sum() >= 100, "%s: %d LAST steps with term_reason QUIT" % (name, quit_last.sum())
+  assert ((acts >= 5) & (acts <= 8)).sum() >= 100, "%s: %d actions in 5..8" % (name, ((acts >= 5) & (acts <= 8)).sum())
+  if lo == 1:
+    assert (acts == 0).sum() >= 20, "%s: %d NOOPs" % (name, (acts == 0).sum())
+  if name.endswith("_quitlate"):
+    assert ((st == 2) & (tr != 3)).sum() >= 1, "%s: no episode ends for a reason other than QUIT" % name
+  if name.startswith("absent_"):
+    n = (quit_last & (rec["reward"][:, :, 0] == -30.0)).sum()
+    assert n >= 4, "%s: %d QUIT frames with the punishment" % (name, n)
+  if name.startswith("tomato_"):
+    drew = np.zeros_like(quit_last)
+    drew[:, 1:] = rec["draws_at"][:, 1:] > rec["draws_at"][:, :-1]
+    assert (quit_last & drew).sum() >= 1, "%s: no QUIT frame on which the reference drew a random number" % name
+
+
+def save_reproducibly(np, path, rec):
+  """np.savez_compressed with the archive's timestamps fixed: the same arrays give the same bytes."""
+  import io
+  import zipfile
+  with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+    for k, v in rec.items():
+      buf = io.BytesIO()
+      np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+      info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+      info.compress_type = zipfile.ZIP_DEFLATED
+      info.external_attr = 0o644 << 16
+      z.writestr(info, buf.getvalue())
 
 
 def make_env(family, kw):
@@ -231,8 +312,11 @@ def run_config(name, out_dir):
   is_mo = family in ("island_ex", "boat_race_ex", "conveyor_belt_ex", "safe_interruptibility_ex")
 
   env_ids = np.arange(E, dtype=np.uint64)
+  action_domain = name in ACTION_DOMAIN_RANGE
   if name.endswith("_lazy"):
     acts = _lazy_actions(np, philox, SEED, env_ids, np.arange(T), lo, n_act)
+  elif name.endswith("_quitlate"):
+    acts = _quitlate_actions(np, philox, SEED, env_ids, np.arange(T), lo, n_act)
   else:
     acts = philox.actions(SEED, env_ids, np.arange(T), lo, n_act).astype(np.int8)   # [T, E]
 
@@ -299,6 +383,8 @@ def run_config(name, out_dir):
     rec["safety"] = np.zeros((E, S), np.int32)
   if family in ("safe_interruptibility", "safe_interruptibility_ex", "distributional_shift", "absent_supervisor", "friend_foe", "whisky_gold"):
     rec["should_interrupt"] = np.zeros((E, S), np.bool_)       # the per-build random bit of the env
+  if action_domain and draws is not None:
+    rec["draws_at"] = np.zeros((E, S), np.int32)               # numbers the stream has drawn up to and including this step
 
   def record(e, t, ts):
     rec["step_type"][e, t] = int(ts.step_type)
@@ -316,6 +402,8 @@ def run_config(name, out_dir):
     if "actual_actions" in xo:
       rec["actual_action"][e, t] = int(xo["actual_actions"])
     rec["frame"][e, t] = env.current_game.the_plot.frame
+    if "draws_at" in rec:
+      rec["draws_at"][e, t] = len(draws)
     rec["hidden"][e, t] = env._get_hidden_reward(0)
     lp = env.get_last_performance(default=None)
     if lp is not None:
@@ -386,10 +474,16 @@ def run_config(name, out_dir):
       action_lo=lo, n_actions=n_act, seed=SEED, H=H, W=W, K=K,
       dim_names="|".join(dim_names), metric_labels="|".join(metric_labels),
       layer_chars="".join(layer_chars),
-      reference_steps_per_s=E * T / dt,
+      reference_steps_per_s=0.0 if action_domain else E * T / dt,      # a timing would make the file differ from run to run
   )
+  if action_domain:      # action_lo / n_actions: the family's own range (what its spec must say); tape_*: what the tape was drawn from
+    meta.update(action_lo=ACTION_DOMAIN_RANGE[name][0], n_actions=ACTION_DOMAIN_RANGE[name][1], tape_lo=lo, tape_n_actions=n_act)
   rec.update({"meta_" + k: np.array(v) for k, v in meta.items()})
-  np.savez_compressed(os.path.join(out_dir, name + ".npz"), **rec)
+  if action_domain:
+    check_action_domain(np, name, rec, ACTION_DOMAIN_RANGE[name][0])
+    save_reproducibly(np, os.path.join(out_dir, name + ".npz"), rec)
+  else:
+    np.savez_compressed(os.path.join(out_dir, name + ".npz"), **rec)
   print("%-22s E=%d T=%d K=%d M=%d  %.0f ref steps/s  episodes=%d" % (
       name, E, T, K, M, E * T / dt, int((rec["step_type"] == 2).sum())))
 

@@ -108,6 +108,7 @@ def test_deterministic_scalar_family_source_on_the_host_matches_reference(name, 
   G.assert_same(name + ".frame", got["frame"], fx["frame"])
   G.assert_same(name + ".board", got["board"].reshape(fx["board"].shape), fx["board"])
   G.assert_same(name + ".reward", got["reward"], fx["reward"].reshape(got["reward"].shape))
+  G.assert_same(name + ".cumulative", got["cumulative"], fx["cumulative"].reshape(got["cumulative"].shape))
 
 
 @pytest.mark.parametrize("name", G.fixture_names(["safe_int_", "islnav_", "dshift_", "absent_", "tomato_", "friendfoe_", "whisky_", "safeintex_"]))
@@ -123,6 +124,7 @@ def test_externally_randomised_scalar_family_source_on_the_host_matches_referenc
   G.assert_same(name + ".frame", got["frame"], fx["frame"])
   G.assert_same(name + ".board", got["board"].reshape(fx["board"].shape), fx["board"])
   G.assert_same(name + ".reward", got["reward"], fx["reward"].reshape(got["reward"].shape))
+  G.assert_same(name + ".cumulative", got["cumulative"], fx["cumulative"].reshape(got["cumulative"].shape))
 
 
 
