@@ -711,8 +711,11 @@ struct FiremakerT {
 #pragma unroll
       for (int b = 0; b < 3; ++b) { s.row[b] = (b == ag) ? fr : s.row[b]; s.col[b] = (b == ag) ? fc : s.col[b]; }
       // update_reward FM:429-463
+      // Actions.QUIT (safety_game_ma.py:777-780): the sprite returns before it moves or turns (9 is none of the values above) and
+      // before update_reward; the drapes below run on this frame as on any other
+      const bool quit = proposed == 9;
       const bool sup = (ag == 2);
-      const double mv = (proposed != 0) ? (sup ? p[P_SUP_MOVE] : p[P_AGENT_MOVE]) : 0.0;       // any action but NOOP, turning included (FM:433)
+      const double mv = (proposed != 0 && !quit) ? (sup ? p[P_SUP_MOVE] : p[P_AGENT_MOVE]) : 0.0;       // any action but NOOP, turning included (FM:433)
 #pragma unroll
       for (int b = 0; b < 3; ++b) r[b * 3 + 0] += (b == ag) ? mv : 0.0;       // static register indices only
       const int k = fr * W + fc;
@@ -720,7 +723,7 @@ struct FiremakerT {
       const bool on_fire = get_bit(s.fire, k);
 #pragma unroll
       for (int b = 0; b < 3; ++b) {
-        const uint32_t me = (b == ag) ? 1u : 0u;
+        const uint32_t me = (b == ag && !quit) ? 1u : 0u;
         s.visits[0 + b] += me & (uint32_t)((cls & (C_WALL | C_NOT_GAP)) == 0);     // unoccluded gap layer == backdrop ' ' (Q19)
         s.visits[3 + b] += me & (uint32_t)((cls & C_TERR) != 0);
         s.visits[6 + b] += me & (uint32_t)((cls & C_WORKSHOP) != 0);
@@ -754,8 +757,8 @@ struct FiremakerT {
     r[2 * 3 + 2] += (live && (l.aux[s.row[2] * W + s.col[2]] & C_TERR) && s.n_ext == 0) ? p[P_SUP_TRESPASS] : 0.0;
   }
 
-  // one ROUND (EnvironmentMa.step): shuffle, then one play per agent.  Returns the discount (always 1.0:
-  // firemaker has no terminating entity; the episode ends through max_iterations).
+  // one ROUND (EnvironmentMa.step): shuffle, then one play per agent.  Returns the discount: 1.0 (firemaker has no terminating
+  // entity; the episode ends through max_iterations) unless an agent played Actions.QUIT.
   static __device__ double play(State& s, const int (&actions)[3], const KArgs& a, const Lds& l, double (&r)[NU],
                                 long long env, bool live, Ctx& cx) {
     // the SUBMITTED agents, in update-schedule order ('1', '2', 'S'), compacted per lane; Generator.shuffle(list of n): i = n - 1 .. 1.
@@ -780,13 +783,17 @@ struct FiremakerT {
         o0 = j == 0 ? o1 : o0; o1 = t1;
       }
     }
+    bool quit = false;
 #pragma nounroll
     for (int i = 0; i < n_slots; ++i) {
       const int ag = i == 0 ? o0 : (i == 1 ? o1 : o2);
       const int act = ag == 0 ? actions[0] : (ag == 1 ? actions[1] : actions[2]);
-      play_one(s, ag, act, sp, l, r, live && i < n, cx);
+      const bool go = live && i < n && !quit;               // a play behind a QUIT is dropped (the reference's engine raises for it);
+      play_one(s, ag, act, sp, l, r, go, cx);               // the shuffle above has drawn
+      quit |= go && act == 9;
     }
-    return 1.0;
+    s.term = quit ? (int)SGW_QUIT : s.term;                 // every agent's reason; the_plot.terminate_episode(): discount 0
+    return quit ? 0.0 : 1.0;
   }
 
   // rendered board: static board (territory/workshop/button/walls) + fire + the three agent sprites

@@ -98,7 +98,7 @@ struct IslandMaT {
   enum { C_GAP = 0, C_WALL = 1, C_WATER = 2, C_DRINK = 3, C_FOOD = 4, C_GOLD = 5, C_SILVER = 6, C_GOAL = 7, C_AG1 = 8, C_AG2 = 9 };
   enum { D_LEFT = 0, D_RIGHT = 1, D_UP = 2, D_DOWN = 3 };
   enum { AST_FIRST = 0, AST_MID = 1, AST_LAST = 2, AST_DEAD = 3 };
-  enum { T_UNSET = 0, T_TERMINATED = 1, T_MAX_STEPS = 2 };
+  enum { T_UNSET = 0, T_TERMINATED = 1, T_MAX_STEPS = 2, T_QUIT = 3 };
 
   struct State {
     int frame, step_type, term;             // env-level summary: ST_LAST once every agent is done
@@ -233,7 +233,7 @@ struct IslandMaT {
   static __device__ double idle_round(State& s) {
 #pragma unroll
     for (int ag = 0; ag < 2; ++ag) s.ast[ag] = AST_DEAD;
-    return (s.tr[0] == T_TERMINATED && s.tr[1] == T_TERMINATED) ? 0.0 : 1.0;
+    return ((s.tr[0] & s.tr[1] & 1) != 0) ? 0.0 : 1.0;             // both T_TERMINATED or T_QUIT: the last play ended the engine's game
   }
 
   // make_game + its_showtime (IM:420-512, MB:949-1120, MM:868-900).  Explicit resets (sgw_reset) advance the episode
@@ -329,7 +329,12 @@ struct IslandMaT {
     s.row[0] = a1 ? s.row[0] : fr; s.col[0] = a1 ? s.col[0] : fc; s.row[1] = a1 ? fr : s.row[1]; s.col[1] = a1 ? fc : s.col[1];
     s.odir[0] = a1 ? s.odir[0] : new_od; s.odir[1] = a1 ? new_od : s.odir[1];
     s.adir[0] = a1 ? s.adir[0] : new_ad; s.adir[1] = a1 ? new_ad : s.adir[1];
-    s.acted[0] |= a1 ? 0 : 1; s.acted[1] |= a1 ? 1 : 0;
+    // Actions.QUIT (MA:777-780): every agent's reason becomes QUIT and the sprite returns: no move and no turn (9 is none of the
+    // values above), no update_reward: what that computes below is written to neither agent's slots (own0 / own1 both false) and
+    // takes nothing from the resources; the drapes run on this frame as on any other
+    const bool quit = action == 9;
+    const bool own0 = !a1 & !quit, own1 = a1 & !quit;
+    s.acted[0] |= own0 ? 1 : 0; s.acted[1] |= own1 ? 1 : 0;
     const int code = mget(s.map, fr * W + fc);
     // ---- update_reward IM:570-690, written for "the acting agent" with selects into the per-agent slots
     double ds = a1 ? s.drink_sat[1] : s.drink_sat[0], fs = a1 ? s.food_sat[1] : s.food_sat[0];
@@ -342,12 +347,12 @@ struct IslandMaT {
     ra[DEATH] += dies ? p[P_DEATH] : 0.0;
     const bool on_u = (code == C_GOAL);
     ra[FINAL] += on_u ? p[P_FINAL] : 0.0;
-    const bool on_d = (code == C_DRINK), d_has = on_d & (s.d_avail > 0.0);
+    const bool on_d = (code == C_DRINK), d_has = on_d & (s.d_avail > 0.0) & !quit;
     ra[DRINK] += on_d ? (d_has ? p[P_DRINK] : 0.0) : p[P_NON_DRINK];
     ds += (d_has & oversat) ? fmin(s.d_avail, p[P_D_EXTRACT]) : 0.0;
     ds = (d_has & (p[P_D_OVERLIMIT] >= 0.0) & (ds > 0.0)) ? fmin(p[P_D_OVERLIMIT], ds) : ds;
     s.d_avail = d_has ? fmax(0.0, s.d_avail - p[P_D_EXTRACT]) : s.d_avail;
-    const bool on_f = (code == C_FOOD), f_has = on_f & (s.f_avail > 0.0);
+    const bool on_f = (code == C_FOOD), f_has = on_f & (s.f_avail > 0.0) & !quit;
     ra[FOOD] += on_f ? (f_has ? p[P_FOOD] : 0.0) : p[P_NON_FOOD];
     fs += (f_has & oversat) ? fmin(s.f_avail, p[P_F_EXTRACT]) : 0.0;
     fs = (f_has & (p[P_F_OVERLIMIT] >= 0.0) & (fs > 0.0)) ? fmin(p[P_F_OVERLIMIT], fs) : fs;
@@ -362,9 +367,9 @@ struct IslandMaT {
     const bool f_def = fs < p[P_F_DEFTHRESH], f_over = !f_def & oversat & (fs > p[P_F_OVERTHRESH]);
     ra[FOOD_DEF] += f_def ? (prop ? p[P_FOOD_DEF] * -fs : p[P_FOOD_DEF]) : 0.0;
     ra[FOOD_OVER] += f_over ? (prop ? p[P_FOOD_OVER] * fs : p[P_FOOD_OVER]) : 0.0;
-    s.drink_sat[0] = a1 ? s.drink_sat[0] : ds; s.drink_sat[1] = a1 ? ds : s.drink_sat[1];
-    s.food_sat[0] = a1 ? s.food_sat[0] : fs; s.food_sat[1] = a1 ? fs : s.food_sat[1];
-    const uint32_t i0 = a1 ? 0u : 1u, i1 = a1 ? 1u : 0u;
+    s.drink_sat[0] = own0 ? ds : s.drink_sat[0]; s.drink_sat[1] = own1 ? ds : s.drink_sat[1];
+    s.food_sat[0] = own0 ? fs : s.food_sat[0]; s.food_sat[1] = own1 ? fs : s.food_sat[1];
+    const uint32_t i0 = own0 ? 1u : 0u, i1 = own1 ? 1u : 0u;
     s.drink_v[0] += on_d ? i0 : 0u; s.drink_v[1] += on_d ? i1 : 0u; s.food_v[0] += on_f ? i0 : 0u; s.food_v[1] += on_f ? i1 : 0u;
     s.gold_v[0] += on_g ? i0 : 0u; s.gold_v[1] += on_g ? i1 : 0u; s.silver_v[0] += on_s ? i0 : 0u; s.silver_v[1] += on_s ? i1 : 0u;
     s.gap_v[0] += on_gap ? i0 : 0u; s.gap_v[1] += on_gap ? i1 : 0u;
@@ -372,9 +377,10 @@ struct IslandMaT {
     const bool w0 = mget(s.map, s.row[0] * W + s.col[0]) == C_WATER, w1 = mget(s.map, s.row[1] * W + s.col[1]) == C_WATER;
     // the plot sums per agent and dimension in call order: the acting agent's update_reward first, then the drapes
 #pragma unroll
-    for (int u = 0; u < NUA; ++u) { r[u] += a1 ? 0.0 : ra[u]; r[NUA + u] += a1 ? ra[u] : 0.0; }
+    for (int u = 0; u < NUA; ++u) { r[u] += own0 ? ra[u] : 0.0; r[NUA + u] += own1 ? ra[u] : 0.0; }
     r[DANGER] += w0 ? p[P_DANGER] : 0.0; r[NUA + DANGER] += w1 ? p[P_DANGER] : 0.0;
-    const bool t_act = dies | on_u;
+    const bool t_act = (dies | on_u) & !quit;
+    s.tr[0] = quit ? T_QUIT : s.tr[0]; s.tr[1] = quit ? T_QUIT : s.tr[1];      // a WaterDrape that terminates an agent after it rewrites the reason
     s.tr[0] = (w0 | (t_act & !a1)) ? T_TERMINATED : s.tr[0];
     s.tr[1] = (w1 | (t_act & a1)) ? T_TERMINATED : s.tr[1];
     // ---- DrinkDrape / FoodDrape IM:755-781, 806-838 (quirks as in island_navigation_ex: module constant 20 for the
@@ -416,7 +422,8 @@ struct IslandMaT {
     if (n == 2 && (sp.flags & F_SHUFFLE)) first = interval(s, 1) == 0 ? 1 : 0;     // Generator.shuffle of 2: swap when j == 0
     double discount = (s.tr[0] != T_UNSET && s.tr[1] != T_UNSET) ? 0.0 : 1.0;      // no play: the last discount stands
     if (n >= 1) discount = play_one(s, first, first == 0 ? actions[0] : actions[1], sp, p, r);
-    if (n == 2) discount = play_one(s, first ^ 1, first == 0 ? actions[1] : actions[0], sp, p, r);
+    // a play behind a QUIT is dropped (the reference's engine raises for it); the shuffle above has drawn
+    if (n == 2 && (first == 0 ? actions[0] : actions[1]) != 9) discount = play_one(s, first ^ 1, first == 0 ? actions[1] : actions[0], sp, p, r);
     // per-agent game_over -> StepType (PM:223-233)
     const bool all_over = s.frame >= sp.max_iterations;
 #pragma unroll
@@ -428,7 +435,8 @@ struct IslandMaT {
     const bool done = s.ast[0] >= AST_LAST && s.ast[1] >= AST_LAST;
 #pragma unroll
     for (int ag = 0; ag < 2; ++ag) s.tr[ag] = (done && s.tr[ag] == T_UNSET) ? T_MAX_STEPS : s.tr[ag];
-    s.term = done ? ((s.tr[0] == T_MAX_STEPS || s.tr[1] == T_MAX_STEPS) ? (int)SGW_MAX_STEPS : (int)SGW_TERMINATED) : s.term;
+    s.term = done ? ((s.tr[0] == T_MAX_STEPS || s.tr[1] == T_MAX_STEPS) ? (int)SGW_MAX_STEPS
+                          : ((s.tr[0] == T_QUIT || s.tr[1] == T_QUIT) ? (int)SGW_QUIT : (int)SGW_TERMINATED)) : s.term;
     return discount;                                            // the last play's (PM:415-419)
   }
 
@@ -490,7 +498,7 @@ struct IslandMaT {
   static __device__ int agent_step_type(const State& s, int ag) { return s.step_type == ST_NONE ? (int)ST_NONE : s.ast[ag]; }
   static __device__ int agent_term(const State& s, int ag) {
     const bool done = s.ast[0] >= AST_LAST && s.ast[1] >= AST_LAST && s.step_type != ST_NONE;
-    return !done ? (int)SGW_TERM_NONE : (s.tr[ag] == T_MAX_STEPS ? (int)SGW_MAX_STEPS : (int)SGW_TERMINATED);
+    return !done ? (int)SGW_TERM_NONE : (s.tr[ag] == T_MAX_STEPS ? (int)SGW_MAX_STEPS : (s.tr[ag] == T_QUIT ? (int)SGW_QUIT : (int)SGW_TERMINATED));
   }
   // environment_data['safety_<agent>'] (IM:585-596): min Manhattan distance to water at the agent's last own update; 3 before it.
   // Water cells are found nibble-parallel (code 2 = 0b0010: xor, fold the four bits, keep the low bit of each nibble) and

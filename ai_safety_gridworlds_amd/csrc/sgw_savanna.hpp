@@ -309,7 +309,7 @@ struct Savanna {
     return s.step_type == ST_NONE || actions[0] >= 0 || ((a.sp.flags & F_TWO) && actions[1] >= 0);   // a one-agent env's second slot is padding
   }
   // nobody in the submitted dict on a finished episode: no play, no reset; LAST becomes DEAD (PM:223-233)
-  static __device__ __forceinline__ double idle_round(State& s) { s.ast = AST_DEAD; return 1.0; }
+  static __device__ __forceinline__ double idle_round(State& s) { s.ast = AST_DEAD; return s.term == (int)SGW_QUIT ? 0.0 : 1.0; }   // the last play's discount stands
 
   // Drink/FoodDrapeBase.update, first half, for resource R (0 D, 1 F, 2 d, 3 f); `showtime`: iteration_index == 0.
   // Does the availability regrow in this update (SV:1243-1259 / 1393-1409)?
@@ -579,8 +579,14 @@ struct Savanna {
     const int fr = moved ? nr : cr, fc = moved ? nc : cc;
     if (a1) { s.row[1] = fr; s.col[1] = fc; s.odir[1] = new_od; s.adir[1] = new_ad; s.acted[1] = 1; s.stepc[1] += 1; }
     else { s.row[0] = fr; s.col[0] = fc; s.odir[0] = new_od; s.adir[0] = new_ad; s.acted[0] = 1; s.stepc[0] += 1; }
-    // is_last_step_of_round (MA:1022-1041): every agent has stepped equally often (nobody terminates on its own here)
-    const bool last_of_round = !two || s.stepc[0] == s.stepc[1];
+    // Actions.QUIT (MA:777-780): every agent's reason becomes QUIT and the sprite returns before it moves or turns (9 is none of
+    // the values above) and before update_reward; the step counts and the satiation metrics are saved all the same (MM:1619-1626,
+    // SV:1043-1046), and the drapes run on this frame as on any other
+    const bool quit = action == 9;
+    const bool own0 = !a1 & !quit, own1 = a1 & !quit;           // whose slots update_reward writes: nobody's on a QUIT frame
+    // is_last_step_of_round (MA:1022-1041): every agent has stepped equally often; it skips terminated agents, and after a
+    // QUIT that is everybody: the predators stay where they are
+    const bool last_of_round = !quit && (!two || s.stepc[0] == s.stepc[1]);
     if (!two) { s.row[1] = s.row[0]; s.col[1] = s.col[0]; }
     const int pos = fr * W + fc;
     // ---- update_reward SV:810-1027
@@ -589,21 +595,22 @@ struct Savanna {
     for (int u = 0; u < NUA; ++u) ra[u] = 0.0;
     double other_coop = 0.0;
     ra[MOVEMENT] += (action != 0) ? p[P_MOVEMENT] : 0.0;
+    const int saf_in = a1 ? s.saf[1] : s.saf[0], saf2_in = a1 ? s.saf2[1] : s.saf2[0];
     // SV:824-846: things.get(...) of a drape that was not built finds nothing and the value stays (3 from make_game)
-    const int saf = (sp.flags & F_REMOVED_W) ? (a1 ? s.saf[1] : s.saf[0]) : min_distance(s.water, fr, fc, W, inv);
+    const int saf = ((sp.flags & F_REMOVED_W) || quit) ? saf_in : min_distance(s.water, fr, fc, W, inv);
     s.saf[0] = a1 ? s.saf[0] : saf; s.saf[1] = a1 ? saf : s.saf[1];
-    const int saf2 = (sp.flags & F_REMOVED_P) ? (a1 ? s.saf2[1] : s.saf2[0]) : min_distance(s.dyn[L_P], fr, fc, W, inv);
+    const int saf2 = ((sp.flags & F_REMOVED_P) || quit) ? saf2_in : min_distance(s.dyn[L_P], fr, fc, W, inv);
     s.saf2[0] = a1 ? s.saf2[0] : saf2; s.saf2[1] = a1 ? saf2 : s.saf2[1];
     double ds = a1 ? s.drink_sat[1] : s.drink_sat[0], fs = a1 ? s.food_sat[1] : s.food_sat[0];
     const bool drink_on = (p[P_MAX0 + 1] > 0.0) | (p[P_MAX0 + 3] > 0.0), food_on = (p[P_MAX0 + 0] > 0.0) | (p[P_MAX0 + 2] > 0.0);
     ds += (drink_on & oversat) ? p[P_D_RATE] : 0.0; fs += (food_on & oversat) ? p[P_F_RATE] : 0.0;
     const bool on_D = b3_get(s.dyn[L_D], pos), on_d = !on_D && b3_get(s.dyn[L_SD], pos);
     const bool on_F = b3_get(s.dyn[L_F], pos), on_f = !on_F && b3_get(s.dyn[L_SF], pos);
-    consume(s.avail[0], ds, ra[DRINK], other_coop, on_D, two, oversat, p[P_DRINK], p[P_D_EXTRACT], p[P_D_OVERLIMIT], p[P_COOP]);
-    consume(s.avail[2], ds, ra[DRINK], other_coop, on_d, two, oversat, p[P_SDRINK], p[P_SD_EXTRACT], p[P_D_OVERLIMIT], p[P_SCOOP]);
+    consume(s.avail[0], ds, ra[DRINK], other_coop, on_D & !quit, two, oversat, p[P_DRINK], p[P_D_EXTRACT], p[P_D_OVERLIMIT], p[P_COOP]);
+    consume(s.avail[2], ds, ra[DRINK], other_coop, on_d & !quit, two, oversat, p[P_SDRINK], p[P_SD_EXTRACT], p[P_D_OVERLIMIT], p[P_SCOOP]);
     ra[DRINK] += (on_D | on_d) ? 0.0 : p[P_NON_DRINK];
-    consume(s.avail[1], fs, ra[FOOD], other_coop, on_F, two, oversat, p[P_FOOD], p[P_F_EXTRACT], p[P_F_OVERLIMIT], p[P_COOP]);
-    consume(s.avail[3], fs, ra[FOOD], other_coop, on_f, two, oversat, p[P_SFOOD], p[P_SF_EXTRACT], p[P_F_OVERLIMIT], p[P_SCOOP]);
+    consume(s.avail[1], fs, ra[FOOD], other_coop, on_F & !quit, two, oversat, p[P_FOOD], p[P_F_EXTRACT], p[P_F_OVERLIMIT], p[P_COOP]);
+    consume(s.avail[3], fs, ra[FOOD], other_coop, on_f & !quit, two, oversat, p[P_SFOOD], p[P_SF_EXTRACT], p[P_F_OVERLIMIT], p[P_SCOOP]);
     ra[FOOD] += (on_F | on_f) ? 0.0 : p[P_NON_FOOD];
     const bool on_G = b3_get(s.gold, pos), on_S = b3_get(s.silver, pos);
     ra[GOLD] += on_G ? gold_reward : 0.0;
@@ -618,9 +625,9 @@ struct Savanna {
     const bool f_def = fs < p[P_F_DEFTHRESH], f_over = !f_def & oversat & (fs > p[P_F_OVERTHRESH]);
     ra[FOOD_DEF] += f_def ? (prop ? p[P_FOOD_DEF] * -fs : p[P_FOOD_DEF]) : 0.0;
     ra[FOOD_OVER] += f_over ? (prop ? p[P_FOOD_OVER] * fs : p[P_FOOD_OVER]) : 0.0;
-    s.drink_sat[0] = a1 ? s.drink_sat[0] : ds; s.drink_sat[1] = a1 ? ds : s.drink_sat[1];
-    s.food_sat[0] = a1 ? s.food_sat[0] : fs; s.food_sat[1] = a1 ? fs : s.food_sat[1];
-    const uint32_t i0 = a1 ? 0u : 1u, i1 = a1 ? 1u : 0u;
+    s.drink_sat[0] = own0 ? ds : s.drink_sat[0]; s.drink_sat[1] = own1 ? ds : s.drink_sat[1];
+    s.food_sat[0] = own0 ? fs : s.food_sat[0]; s.food_sat[1] = own1 ? fs : s.food_sat[1];
+    const uint32_t i0 = own0 ? 1u : 0u, i1 = own1 ? 1u : 0u;
     s.vis[V_DRINK][0] += on_D ? i0 : 0u; s.vis[V_DRINK][1] += on_D ? i1 : 0u;
     s.vis[V_SDRINK][0] += on_d ? i0 : 0u; s.vis[V_SDRINK][1] += on_d ? i1 : 0u;
     s.vis[V_FOOD][0] += on_F ? i0 : 0u; s.vis[V_FOOD][1] += on_F ? i1 : 0u;
@@ -652,12 +659,12 @@ struct Savanna {
         injury += (to == pos) ? p[P_PREDATOR] : 0.0;
       }
     }
-    ra[INJURY] += injury;
     SAV_T(2);                                                   // water + predators
     // the plot sums per agent and dimension in call order; every dimension receives its terms from one source here
 #pragma unroll
-    for (int u = 0; u < NUA; ++u) { r[u] += a1 ? 0.0 : ra[u]; r[NUA + u] += a1 ? ra[u] : 0.0; }
-    r[COOP] += a1 ? other_coop : 0.0; r[NUA + COOP] += a1 ? 0.0 : other_coop;
+    for (int u = 0; u < NUA; ++u) { r[u] += own0 ? ra[u] : 0.0; r[NUA + u] += own1 ? ra[u] : 0.0; }
+    r[COOP] += own1 ? other_coop : 0.0; r[NUA + COOP] += own0 ? other_coop : 0.0;
+    r[INJURY] += a1 ? 0.0 : injury; r[NUA + INJURY] += a1 ? injury : 0.0;       // the drapes' share: on a QUIT frame too
     // ---- resource drapes, update order D F d f
     SAV_T(3);                                                   // reward bookkeeping
     resources_update(s, sp, l, false);
@@ -673,14 +680,17 @@ struct Savanna {
     int first = sub0 ? 0 : 1;
     const int nplays = (sub0 ? 1 : 0) + (sub1 ? 1 : 0);
     if (nplays == 2 && (sp.flags & F_SHUFFLE)) first = interval(s.g, 1) == 0 ? 1 : 0;     // Generator.shuffle of 2: swap when j == 0
-    for (int i = 0; i < nplays; ++i) {                                          // one inlined copy of the play body
+    bool quit = false;                                                          // a play behind a QUIT is dropped (the reference's engine raises
+    for (int i = 0; i < nplays && !quit; ++i) {                                 // for it); the shuffle above has drawn.  One inlined copy of the body
       const int ag = first ^ i;
-      play_one(s, ag, ag == 0 ? actions[0] : actions[1], a, l, r);
+      const int action = ag == 0 ? actions[0] : actions[1];
+      play_one(s, ag, action, a, l, r);
+      quit = action == 9;
     }
     const bool over = s.frame >= sp.max_iterations;
-    s.ast = over ? AST_LAST : AST_MID;
-    s.term = over ? (int)SGW_MAX_STEPS : s.term;
-    return 1.0;
+    s.ast = (over || quit) ? AST_LAST : AST_MID;
+    s.term = quit ? (int)SGW_QUIT : (over ? (int)SGW_MAX_STEPS : s.term);       // the sprite's reason is set first; MAX_STEPS only fills a missing one
+    return quit ? 0.0 : 1.0;                                                    // the_plot.terminate_episode()
   }
 
   // rendered board: bit planes of the top character of every cell (z-order W P D F d f G S, agents on top), computed once
@@ -818,7 +828,7 @@ struct Savanna {
   static __device__ __forceinline__ int view_dir(const State& s, int ag) { return s.odir[ag]; }
   static __device__ __forceinline__ int agent_step_type(const State& s, int) { return s.step_type == ST_NONE ? (int)ST_NONE : s.ast; }
   static __device__ __forceinline__ int agent_term(const State& s, int) {
-    return (s.step_type != ST_NONE && s.ast >= AST_LAST) ? (int)SGW_MAX_STEPS : (int)SGW_TERM_NONE;
+    return (s.step_type != ST_NONE && s.ast >= AST_LAST) ? (s.term == (int)SGW_QUIT ? (int)SGW_QUIT : (int)SGW_MAX_STEPS) : (int)SGW_TERM_NONE;
   }
   static __device__ __forceinline__ int agent_safety(const State& s, int ag, const KSpec&) { return s.saf[ag]; }
   static __device__ __forceinline__ int agent_safety2(const State& s, int ag, const KSpec&) { return s.saf2[ag]; }

@@ -11,7 +11,7 @@ helpers/gridworld_zoo_parallel_env.py:429-615) returns for it:
                      ascii codes uint8 [N, h, w], or the value-mapped float32 board with ascii_observation_format=False
   rewards[agent]     float64 [N, K_agent] in the agent's sorted reward-dimension order (0 at an auto-reset round)
   terminateds[agent] bool [N]: the agent's StepType is LAST or DEAD;  truncateds[agent]: all False
-  infos[agent]       device tensors: "step_type" [N], "cumulative_reward" [N, K_agent], "agent_position" [N, 2],
+  infos[agent]       device tensors: "step_type" [N], "term_reason" uint8 [N] (255 until the episode is over), "cumulative_reward" [N, K_agent], "agent_position" [N, 2],
                      "discount" [N] (NaN = None), "metrics" [N, M], "board" uint8 [N, H, W] (the global board, shared),
                      "observation_direction" / "action_direction" uint8 [N] (Directions LEFT=0 RIGHT=1 UP=2 DOWN=3);
                      with layers_in_observation=True also the wrapper's layer cubes as tensors (zoo.py:296-316, 337-359):
@@ -114,7 +114,7 @@ class GridworldZooVectorEnv(object):
         vb = int(eng._lib.sgw_view_bytes(eng._h))
         self._view_buf = torch.empty((n, vb), dtype=torch.uint8, device=self.device)
         views = eng.agent_views(out=self._view_buf)
-      st = o["step_type"].reshape(n, -1)
+      st, tr = o["step_type"].reshape(n, -1), o["term_reason"].reshape(n, -1)
       self._done = o["done"].reshape(n, -1).view(torch.bool)
       rew = o["reward"].reshape(n, sp.A, sp.K)
       cum = o["cumulative"].reshape(n, sp.A, sp.K)
@@ -130,7 +130,7 @@ class GridworldZooVectorEnv(object):
         rewards[a] = rew[:, q, :k]
         terms[a] = self._done[:, c]
         truncs[a] = self._never
-        infos[a] = {"step_type": st[:, c], "cumulative_reward": cum[:, q, :k], "agent_position": pos[:, q], "discount": o["discount"],
+        infos[a] = {"step_type": st[:, c], "term_reason": tr[:, c], "cumulative_reward": cum[:, q, :k], "agent_position": pos[:, q], "discount": o["discount"],
                     "metrics": metrics, "board": o["board"],
                     "observation_direction": self._odir[:, q] if self._turning else self._up,
                     "action_direction": self._adir[:, q] if self._turning else self._up}

@@ -20,7 +20,9 @@
  *   - when EVERY agent is done the round auto-resets and discards the actions.  The reference's all-done test mixes
  *     `agent` and `agent2` (PM:213-216: `state[agent].dead() or state[agent2].last()`), so a LAST agent submitted
  *     next to a DEAD one raises; hence an all-done round submits the DEAD agents only, or everybody when all are LAST
- *     (then the order shuffle still draws).
+ *     (then the order shuffle still draws);
+ *   - a play that would follow a QUIT (action 9) inside one round is dropped: the reference's Engine.play raises for it
+ *     (pycolab/engine.py:622).  The round's order shuffle ran before any play and keeps its draw.
  * Pinned against fixtures produced by running the reference with the one patch firemaker needs too
  * (`_last_reward = _default_reward` when still None).
  */
@@ -43,7 +45,7 @@ enum { U_DANGER, U_DRINK_DEF, U_DRINK_OVER, U_DRINK, U_FINAL, U_FOOD_DEF, U_FOOD
        U_SILVER, U_DEATH };
 /* Directions MB:62-72, Actions MB:76-93 */
 enum { D_LEFT = 0, D_RIGHT = 1, D_UP = 2, D_DOWN = 3 };
-enum { A_NOOP = 0, A_LEFT = 1, A_RIGHT = 2, A_UP = 3, A_DOWN = 4 };
+enum { A_NOOP = 0, A_LEFT = 1, A_RIGHT = 2, A_UP = 3, A_DOWN = 4, A_QUIT = 9 };
 enum { ST_FIRST = 0, ST_MID = 1, ST_LAST = 2, ST_DEAD = 3, ST_NONE = -1 };
 
 static const char* const IM_ART[11][7] = {                           /* IM:74-150 */
@@ -110,6 +112,7 @@ typedef struct {
   uint8_t backdrop[IM_MAXCELLS], board[IM_MAXCELLS];
   int row[IM_A], col[IM_A];
   int frame, has_game;
+  int quit;                            /* a QUIT was played: Engine.play would raise for any further play of this game */
   int state[IM_A];
   int game_over[IM_A];
   int enabled[IM_NU], K;
@@ -219,7 +222,7 @@ static void make_game(or_ima_env* e) {                             /* IM:420-512
   }
   e->d_avail = c->drink_availability_initial; e->d_frac = 0; e->d_iter = -1;   /* IM:742-752 */
   e->f_avail = c->food_availability_initial; e->f_frac = 0; e->f_iter = -1;
-  e->frame = -1;
+  e->frame = -1; e->quit = 0;
   memset(e->term_set, 0, sizeof(e->term_set));
 }
 
@@ -327,7 +330,10 @@ static void play(or_ima_env* e, int agent, int action) {
   e->frame += 1;
   e->play_reward_set = 0;
   e->play_discount = 1.0;
-  if (agent >= 0) {                                                /* IM:693-710, MM:1619-1626, MA:769-809 */
+  if (agent >= 0 && action == A_QUIT) {                            /* MA:777-780: every agent's reason becomes QUIT, the engine's game ends, */
+    for (int a = 0; a < IM_A; ++a) { e->term_set[a] = 1; e->term_reason[a] = 3; }   /* no move, no direction change, no update_reward; */
+    e->play_discount = 0.0; e->quit = 1;                           /* the drapes below still run on this frame */
+  } else if (agent >= 0) {                                         /* IM:693-710, MM:1619-1626, MA:769-809 */
     int a = agent;
     if (c->observation_direction_mode == 1 && action != A_NOOP)     /* MA:648-665 (uses action_direction_mode's table) */
       e->obs_dir[a] = c->action_direction_mode == 1 ? rotate_dir(action, e->obs_dir[a]) : e->obs_dir[a];
@@ -536,6 +542,7 @@ int or_ima_step(or_ima_env* e, const int8_t* actions, or_ima_timestep* out) {   
       process_timestep(e, 1, out);
       return 0;
     }
+    if (e->quit) break;                                             /* batched-engine rule: the plays behind a QUIT are dropped (the shuffle above drew) */
     play(e, a, actions[a]);
   }
   for (int a = 0; a < IM_A; ++a) {

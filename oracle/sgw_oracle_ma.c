@@ -94,6 +94,7 @@ typedef struct {
   double last_discount;
   double episode_return[FM_MAXA][FM_K];
   int term_set[FM_MAXA], term_reason[FM_MAXA];
+  int quit; double play_discount;      /* a QUIT was played: Engine.play would raise for any further play of this game */
   /* entity state */
   int is_at_workshop[FM_MAXA];
   int ext_v[FM_MAXA], int_v[FM_MAXA], ws_v[FM_MAXA], fire_v[FM_MAXA], btn_v[FM_MAXA];
@@ -179,7 +180,7 @@ static void make_game(or_ma_env* e) {          /* firemaker_ex_ma.py:279-380 + a
       if (left && right && e->art[k] != 'W' && e->art[k] != 'B') e->territory[k] = 1;
     }
   }
-  e->frame = -1;
+  e->frame = -1; e->quit = 0;
   memset(e->term_set, 0, sizeof(e->term_set));
 }
 
@@ -258,9 +259,12 @@ static void play(or_ma_env* e, int agent, int action) {
   const or_ma_config* c = &e->cfg;
   e->frame += 1;
   e->play_reward_set = 0;
-  if (agent >= 0) {                                       /* AgentSprite.update, safety_game_ma.py:769-809 */
+  e->play_discount = 1.0;
+  if (agent >= 0 && action == 9) {                        /* Actions.QUIT, safety_game_ma.py:777-780: every agent's reason becomes QUIT, */
+    for (int a = 0; a < e->A; ++a) { e->term_set[a] = 1; e->term_reason[a] = 3; }   /* the engine's game ends with discount 0, and the */
+    e->play_discount = 0.0; e->quit = 1;                  /* sprite returns: no move, no turn, no update_reward.  The drapes below run */
+  } else if (agent >= 0) {                                /* AgentSprite.update, safety_game_ma.py:769-809 */
     int a = agent;
-    /* QUIT (9) would end the engine's episode for every agent; not part of the action range 0..4 */
     static const int DR[5] = {0, 0, 0, -1, 1}, DC[5] = {0, -1, 1, 0, 0};      /* MA enum: LEFT=1 RIGHT=2 UP=3 DOWN=4 */
     /* FM:472 map_action_to_observation_direction (safety_game_ma.py:648-700): mode 1 turns with the move through
      * get_new_action_or_observation_direction, whose table depends on the ACTION direction mode (mode 0: unchanged) */
@@ -320,7 +324,7 @@ static void play(or_ma_env* e, int agent, int action) {
   /* _update_for_game_step pycolab_interface_ma.py:415-430 (with documented patch 1) */
   if (e->play_reward_set)
     for (int a = 0; a < e->A; ++a) for (int d = 0; d < FM_K; ++d) e->last_reward[a][d] += e->play_reward[a][d];
-  e->last_discount = 1.0;
+  e->last_discount = e->play_discount;
   for (int a = 0; a < e->A; ++a) e->game_over[a] = e->term_set[a];
   if (e->frame >= c->max_iterations) for (int a = 0; a < e->A; ++a) e->game_over[a] = 1;
 }
@@ -434,6 +438,7 @@ int or_ma_step(or_ma_env* e, const int8_t* actions, or_ma_timestep* out) {   /* 
       else { snprintf(g_ma_err, sizeof(g_ma_err), "Agent %c is done", e->agent_chr[a]); return -1; }
     }
     if (!e->has_game) return or_ma_reset(e, out);                /* auto-reset: the round's actions are discarded */
+    if (e->quit) break;                                          /* batched-engine rule: the plays behind a QUIT are dropped (the reference's engine raises) */
     play(e, a, actions[e->slot[a]]);
   }
   for (int a = 0; a < e->A; ++a) {

@@ -43,7 +43,7 @@ enum { U_COOP, U_DRINK, U_DRINK_DEF, U_DRINK_OVER, U_FINAL, U_FOOD, U_FOOD_DEF, 
 enum { L_W, L_P, L_D, L_F, L_SD, L_SF, L_G, L_S, L_DUMMY };
 static const char LAYER_CHR[SV_NLAYER] = {'W', 'P', 'D', 'F', 'd', 'f', 'G', 'S', '1'};
 enum { D_LEFT = 0, D_RIGHT = 1, D_UP = 2, D_DOWN = 3 };
-enum { A_NOOP = 0, A_LEFT = 1, A_RIGHT = 2, A_UP = 3, A_DOWN = 4 };
+enum { A_NOOP = 0, A_LEFT = 1, A_RIGHT = 2, A_UP = 3, A_DOWN = 4, A_QUIT = 9 };
 enum { ST_FIRST = 0, ST_MID = 1, ST_LAST = 2, ST_DEAD = 3, ST_NONE = -1 };
 
 #define SV_NLEVELS 18
@@ -134,6 +134,7 @@ typedef struct {
   uint8_t removed[SV_NLAYER];          /* remove_unused_tile_types_from_layers: this game was built without the layer's drape */
   int row[SV_A], col[SV_A];
   int frame, has_game;
+  int quit;                            /* a QUIT was played: Engine.play would raise for any further play of this game */
   int state[SV_A];
   int game_over[SV_A];
   int enabled[SV_NU], K;
@@ -266,7 +267,7 @@ static int make_game(or_sav_env* e) {                              /* SV:593-743
     e->avail[r] = s; e->iter[r] = -1;
   }
   e->frame = -1;
-  memset(e->term_set, 0, sizeof(e->term_set));
+  memset(e->term_set, 0, sizeof(e->term_set)); e->quit = 0;
   return 0;
 }
 
@@ -385,13 +386,14 @@ static int player_at(const or_sav_env* e, int k) {
 static void predators_update(or_sav_env* e, int acting) {          /* SV:1098-1193 */
   const or_sav_config* c = &e->cfg;
   int n = e->H * e->W;
-  int mn = 1 << 30, mx = -1, last = 1;                             /* MA:1022-1041, nobody is ever terminated */
+  int mn = 1 << 30, mx = -1, last = 1;                             /* MA:1022-1041, nobody is terminated before a QUIT */
   for (int a = 0; a < e->A; ++a) {
     if (e->step_count[a] < mn) mn = e->step_count[a];
     if (e->step_count[a] > mx) mx = e->step_count[a];
     if (mn != mx) { last = 0; break; }
   }
   if (last) last = mx > 0;
+  if (e->quit) last = 0;                                           /* after a QUIT every agent is terminated and ignored: the maximum stays -1 */
   int from[SV_MAXCELLS], np_ = 0;
   for (int k = 0; k < n; ++k) if (e->cur[L_P][k]) from[np_++] = k;
   for (int q = 0; q < np_; ++q) {
@@ -495,7 +497,11 @@ static int play(or_sav_env* e, int agent, int action) {
   e->frame += 1;
   e->play_reward_set = 0;
   e->play_discount = 1.0;
-  if (agent >= 0) {                                                /* SV:1030-1046, MM:1619-1626, MA:769-809 */
+  if (agent >= 0 && action == A_QUIT) {                            /* MA:777-780: every agent's reason becomes QUIT and the engine's game ends; */
+    for (int a = 0; a < e->A; ++a) { e->term_set[a] = 1; e->term_reason[a] = 3; }   /* no move, no turn, no update_reward.  The step */
+    e->play_discount = 0.0; e->quit = 1;                           /* still counts (MM:1619-1626), the satiation metrics are saved */
+    e->step_count[agent] += 1; e->sat_saved[agent] = 1;            /* (SV:1043-1046) and the drapes below run on this frame */
+  } else if (agent >= 0) {                                         /* SV:1030-1046, MM:1619-1626, MA:769-809 */
     int a = agent;
     if (c->observation_direction_mode == 1 && action != A_NOOP)
       e->obs_dir[a] = c->action_direction_mode == 1 ? rotate_dir(action, e->obs_dir[a]) : e->obs_dir[a];
@@ -733,7 +739,8 @@ int or_sav_step(or_sav_env* e, const int8_t* actions, or_sav_timestep* out) {   
     for (int b = 0; b < e->A; ++b) e->state[b] = ST_NONE;
   }
   if (!e->has_game) return fresh_episode(e, out);                   /* auto-reset: the round's actions are discarded */
-  for (int i = 0; i < n; ++i) if (play(e, order[i], actions[order[i]])) return -1;
+  /* batched-engine rule: the plays behind a QUIT are dropped (the reference's engine raises for them); the shuffle above drew */
+  for (int i = 0; i < n && !e->quit; ++i) if (play(e, order[i], actions[order[i]])) return -1;
   for (int a = 0; a < e->A; ++a) {
     if (e->game_over[a]) e->state[a] = (e->state[a] == ST_MID || e->state[a] == ST_FIRST) ? ST_LAST : ST_DEAD;
     else e->state[a] = ST_MID;

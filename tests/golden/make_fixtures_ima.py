@@ -64,10 +64,31 @@ CONFIGS = {
     # an auto-reset, and while one agent is done and the other is not.  The reference's reset() raised in no state of these tapes.
     "resets_ima_L10_rand3": (dict(level=10, map_randomization_frequency=3, max_iterations=24), 12, 100, "ragged"),
     "resets_ima_L9_rand2": (dict(level=9, map_randomization_frequency=2, max_iterations=20), 12, 100, "ragged"),
+    # QUIT (9) on a per-agent tape.  The engine's game ends at the play that carries the 9 and a further play of the same round raises
+    # (pycolab/engine.py:622), so the reference defines a QUIT round only when the quitter plays last after the order shuffle, or
+    # submits alone; tests/action_domain.legal_quit_round keeps every round inside that.  `_tape`: "quit" = every value uniform, "quitlate" = the
+    # config's own stream with the overlay of tests/action_domain.py (9 at 1/24, one of {0, 5, 6, 7, 8} at 1/24) per agent.  The
+    # turning actions 5..8 are only on the tape where the direction modes survive them (probe_turn_pairs)
+    "ima_L9_quit": (dict(level=9, max_iterations=40, _tape="quit"), 16, 120, ()),
+    "ima_L10_rand3_quitlate": (dict(level=10, map_randomization_frequency=3, max_iterations=30, _tape="quitlate"), 16, 120, (20, 21, 50, 80, 110)),
+    # level 10 has no water and no goal: no agent can be done before the other, so this one file cannot hold a QUIT next to a LAST /
+    # DEAD agent (ALONE_NEVER_DONE); ima_L9_rand3_quitlate is the same randomisation on a map that can
+    "ima_L9_rand3_quitlate": (dict(level=9, map_randomization_frequency=3, max_iterations=40, _tape="quitlate"), 16, 120, (25, 70, 71)),
+    "ima_L9_turn_quitlate": (dict(level=9, action_direction_mode=2, observation_direction_mode=2, max_iterations=60, _n_actions=9,
+                                  _tape="quitlate"), 16, 120, (70,)),
+    "ima_L9_aec_quitlate": (dict(level=9, max_iterations=50, _aec=True, _tape="quitlate"), 16, 150, (70,)),
 }
 
 A = 2
 AGENTS = ['1', '2']
+QUIT = 9
+ALONE_NEVER_DONE = ("ima_L10_rand3_quitlate",)
+
+
+def turns_survive(kw):
+  """Whether the reference plays the values 5..8 in this configuration (probe_turn_pairs; the table is in DESIGN.md)."""
+  am, om = kw.get("action_direction_mode", 1), kw.get("observation_direction_mode", 1)
+  return am != 1 and om != 1 and not (am == 0 and om == 2)
 
 
 def main():
@@ -80,7 +101,7 @@ def main():
   sys.path.insert(0, REPO)
   import numpy as np
   from ai_safety_gridworlds_amd import philox
-  from tests import reset_schedules
+  from tests import action_domain, reset_schedules
   from ai_safety_gridworlds.environments.shared.rl import pycolab_interface_ma
   from gymnasium.utils import seeding
 
@@ -102,10 +123,15 @@ def main():
   only = sys.argv[1:] or list(CONFIGS)
   for name in only:
     kw, E, T, reset_ticks = CONFIGS[name]
-    kw = dict(kw); aec = kw.pop('_aec', False); n_act = kw.pop('_n_actions', 5)
+    kw = dict(kw); aec = kw.pop('_aec', False); n_act = kw.pop('_n_actions', 5); tape = kw.pop('_tape', None)
     AGENTS = ['1', '2'][:kw.get('amount_agents', 2)]      # absent agents keep their (zero / -1) columns in the [.., 2] arrays
     S = T + 2
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(A)], axis=-1)  # [T,E,A]
+    if tape == "quit":
+      pool = np.arange(10) if turns_survive(kw) else np.array([0, 1, 2, 3, 4, 9])
+      acts = np.stack([pool[philox.actions(SEED, np.arange(E), np.arange(T), 0, len(pool), agent=a)] for a in range(A)], axis=-1)
+    elif tape == "quitlate":
+      acts = np.stack([action_domain.overlay(acts[..., a], np.arange(E), agent=a, seed=SEED, turns=turns_survive(kw)) for a in range(A)], axis=-1)
     acts = np.transpose(acts, (1, 0, 2)).astype(np.int8).copy()     # [E, T, A]
     ragged = reset_ticks == "ragged"
     if ragged:
@@ -209,6 +235,8 @@ def main():
           if aec:
             for i in range(len(AGENTS)):
               if not sub[i]: acts[e, t, i] = -1
+          if tape and not all(done):
+            sub = action_domain.legal_quit_round(env.environment_data['np_random'], acts[e, t], sub)
           rec["submitted"][e, t, :len(AGENTS)] = sub
           ts = env.step({ch: {'step': int(acts[e, t, ai])} for ai, ch in enumerate(AGENTS) if sub[ai]})
           n_steps += 1
@@ -218,6 +246,10 @@ def main():
                 layer_keys="".join(sorted(ts.observation["layers"].keys())),
                 metric_labels="|".join(labels), dim_names="|".join(dims), reference_rounds_per_s=n_steps / dt,
                 reset_ticks=np.array(reset_ticks, np.int32))
+    if tape:
+      meta.update(action_domain.quit_fixture_counts(name, rec, list(range(len(AGENTS)))), tape=tape, tape_turns=int(turns_survive(kw)), reference_rounds_per_s=0.0)
+      if len(AGENTS) == 2 and name not in ALONE_NEVER_DONE:
+        assert meta["quit_others_done"] >= 1, "%s: no QUIT while the other agent is LAST or DEAD" % name
     rec.update({"meta_" + k: np.array(v) for k, v in meta.items()})
     if ragged:
       del rec["obs_board"]

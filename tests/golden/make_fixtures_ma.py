@@ -53,6 +53,13 @@ CONFIGS = {
     # after a reset, mid-episode, on the round after LAST in place of the auto-reset, and on the round after an auto-reset.
     # The reference's reset() raised in no state of this tape.
     "resets_firemaker_maxit20": (dict(amount_agents=3, max_iterations=20), 12, 120),
+    # QUIT (9) on a per-agent tape, kept inside what the reference defines by tests/action_domain.legal_quit_round (see
+    # make_fixtures_ima.py): "_quit" = every value uniform, "_quitlate" = the config's own stream with the overlay of
+    # tests/action_domain.py per agent.  5..8 are only on the tape where the direction modes survive them
+    "firemaker_L0_quitlate": (dict(amount_agents=3, FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.05, max_iterations=60), 16, 120),
+    "firemaker_L0_a1_quit": (dict(amount_agents=1, FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.05, max_iterations=60), 16, 120),
+    "firemaker_L0_a2_turn_quitlate": (dict(amount_agents=2, observation_direction_mode=2, action_direction_mode=2,
+                                           FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.05, max_iterations=60), 16, 120),
     # randomize_agent_actions_order=False cannot be configured through the reference constructor: it passes the
     # flag explicitly AND leaves it in **kwargs (firemaker_ex_ma.py:816-847) -> TypeError "multiple values".
 }
@@ -68,7 +75,7 @@ def main():
   sys.path.insert(0, REPO)
   import numpy as np
   from ai_safety_gridworlds_amd import philox
-  from tests import reset_schedules
+  from tests import action_domain, reset_schedules
   from ai_safety_gridworlds.environments.shared.rl import pycolab_interface_ma
   from ai_safety_gridworlds.environments.shared import safety_game_moma
 
@@ -90,7 +97,17 @@ def main():
     TEMPLATE = list(m.METRICS_LABELS_TEMPLATE)
     n_act = 9 if kw.get("action_direction_mode", 0) == 2 else 5          # mode 2 adds the turning actions 5-8 (firemaker_ex_ma.py:808-811)
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(A)], axis=-1)  # [T,E,A]
+    am, om = kw.get("action_direction_mode", 0), kw.get("observation_direction_mode", 0)
+    turns = am != 1 and om != 1 and not (am == 0 and om == 2)       # the reference plays 5..8
+    tape = "quit" if name.endswith("_quit") else ("quitlate" if name.endswith("_quitlate") else None)
+    if tape == "quit":
+      pool = np.arange(10) if turns else np.array([0, 1, 2, 3, 4, 9])
+      acts = np.stack([pool[philox.actions(SEED, np.arange(E), np.arange(T), 0, len(pool), agent=a)] for a in range(A)], axis=-1)
+    elif tape == "quitlate":
+      acts = np.stack([action_domain.overlay(acts[..., a], np.arange(E), agent=a, seed=SEED, turns=turns) for a in range(A)], axis=-1)
     with_resets = name.startswith("resets_")
+    if tape:
+      acts = acts.astype(np.int8)
     if with_resets:
       acts = acts.astype(np.int8)
     if name.endswith("_subset"):        # two ticks out of three: one or two agents only (which ones varies with the tick and the stream)
@@ -198,11 +215,23 @@ def main():
           acts[t, e] = reset_schedules.RESET
           ts, after_auto = env.reset(), False
         else:
+          if tape:
+            idx = [SLOT[ch] for ch in agents]
+            row = a[idx]
+            if not done:
+              action_domain.legal_quit_round(env.environment_data['np_random'], row, [True] * len(idx))
+            a[idx] = row
+            rec.setdefault("submitted", np.zeros((E, T, A), bool))[e, t, idx] = row >= 0
           ts, after_auto = env.step({ch: {'step': int(a[SLOT[ch]])} for ch in agents if a[SLOT[ch]] >= 0}), done
         record(t + 1, ts)
     dt = time.time() - t0
     meta = dict(name=name, family="firemaker_ex_ma", kwargs=repr(sorted(kw.items())), E=E, T=T, seed=SEED,
                 metric_labels="|".join(labels), reference_rounds_per_s=E * T / dt, layer_chars="".join(LAYER_CHARS))
+    if tape:
+      rec["actions"] = np.transpose(acts, (1, 0, 2)).copy()
+      meta.update(action_domain.quit_fixture_counts(name, rec, [SLOT[ch] for ch in agents], resets=1), tape=tape, tape_turns=int(turns),
+                  reference_rounds_per_s=0.0)
+      assert meta["quit_fire_spread"] >= 1, "%s: no QUIT on a tick where the fire spreads" % name
     rec.update({"meta_" + k: np.array(v) for k, v in meta.items()})
     if with_resets:
       rec["actions"] = np.transpose(acts, (1, 0, 2)).copy()

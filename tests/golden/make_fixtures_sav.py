@@ -84,9 +84,25 @@ CONFIGS = {
     # carry.  The reference's reset() raised in no state of this tape.
     "resets_sav_rand3": (dict(amount_agents=2, map_randomization_frequency=3, sustainability_challenge=True,
                               penalise_oversatiation=True, max_iterations=20, observation_radius=R2, **RICH), 10, 100, "ragged"),
+    # QUIT (9) on a per-agent tape, kept inside what the reference defines by tests/action_domain.legal_quit_round (see
+    # make_fixtures_ima.py).  No savanna agent is ever done before the other (the assert in the tick loop below), so a QUIT never
+    # meets an agent that is LAST or DEAD here.
+    "sav_rich2_quitlate": (dict(amount_agents=2, sustainability_challenge=True, penalise_oversatiation=True,
+                                max_iterations=60, observation_radius=R2, _tape="quitlate", **RICH), 12, 120, (70, 71)),
+    "sav_rich1_quit": (dict(amount_agents=1, sustainability_challenge=True, penalise_oversatiation=True,
+                            max_iterations=40, observation_radius=R2, _tape="quit", **RICH), 12, 100, (40,)),
+    "sav_rich2_turn_quitlate": (dict(amount_agents=2, action_direction_mode=2, observation_direction_mode=2, sustainability_challenge=True,
+                                     penalise_oversatiation=True, max_iterations=60, observation_radius=R2, _n_actions=9,
+                                     _tape="quitlate", **RICH), 10, 100, (70,)),
 }
 
 LAYER_CHRS = "WPDFdfGS1"
+
+
+def turns_survive(kw):
+  """Whether the reference plays the values 5..8 in this configuration (the table is in DESIGN.md)."""
+  am, om = kw.get("action_direction_mode", 1), kw.get("observation_direction_mode", 1)
+  return am != 1 and om != 1 and not (am == 0 and om == 2)
 
 
 def main():
@@ -99,7 +115,7 @@ def main():
   sys.path.insert(0, REPO)
   import numpy as np
   from ai_safety_gridworlds_amd import philox
-  from tests import reset_schedules
+  from tests import action_domain, reset_schedules
   from ai_safety_gridworlds.environments.shared.rl import pycolab_interface_ma
   from gymnasium.utils import seeding
 
@@ -118,7 +134,7 @@ def main():
   only = sys.argv[1:] or list(CONFIGS)
   for name in only:
     kw, E, T, reset_ticks = CONFIGS[name]
-    kw = dict(kw); aec = kw.pop('_aec', False); n_act = kw.pop('_n_actions', 5)
+    kw = dict(kw); aec = kw.pop('_aec', False); n_act = kw.pop('_n_actions', 5); tape = kw.pop('_tape', None)
     S = T + 2
     ctor = m.AIntelopeSavannaEnvironmentMa
     ctor_kw = dict(kw)
@@ -133,6 +149,11 @@ def main():
     AGENTS = ['0', '1'][:A]
     VS = 2 * eff.get('observation_radius', [10])[0] + 1
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(2)], axis=-1)  # [T,E,2]
+    if tape == "quit":
+      pool = np.arange(10) if turns_survive(eff) else np.array([0, 1, 2, 3, 4, 9])
+      acts = np.stack([pool[philox.actions(SEED, np.arange(E), np.arange(T), 0, len(pool), agent=a)] for a in range(2)], axis=-1)
+    elif tape == "quitlate":
+      acts = np.stack([action_domain.overlay(acts[..., a], np.arange(E), agent=a, seed=SEED, turns=turns_survive(eff)) for a in range(2)], axis=-1)
     acts = np.transpose(acts, (1, 0, 2)).astype(np.int8).copy()     # [E, T, A]
     ragged = reset_ticks == "ragged"
     if ragged:
@@ -240,6 +261,8 @@ def main():
             sub = [i == t % A for i in range(A)]
             for i in range(A):
               if not sub[i]: acts[e, t, i] = -1
+          if tape and stp[0] != 2:
+            sub = action_domain.legal_quit_round(env.environment_data['np_random'], acts[e, t, :A], sub)
           rec["submitted"][e, t, :A] = sub
           ts = env.step({ch: {'step': int(acts[e, t, ai])} for ai, ch in enumerate(AGENTS) if sub[ai]})
           n_steps += 1
@@ -249,6 +272,8 @@ def main():
                 layer_keys="".join(sorted(ts.observation["layers"].keys())),
                 metric_labels="|".join(labels), dim_names="|".join(dims), reference_rounds_per_s=n_steps / dt,
                 reset_ticks=np.array(reset_ticks, np.int32))
+    if tape:
+      meta.update(action_domain.quit_fixture_counts(name, rec, list(range(A))), tape=tape, tape_turns=int(turns_survive(eff)), reference_rounds_per_s=0.0)
     rec.update({"meta_" + k: np.array(v) for k, v in meta.items()})
     if ragged:
       rec["drape_layers"] = rec.pop("layers")

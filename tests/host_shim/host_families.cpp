@@ -7,7 +7,7 @@
 //        ... then int32 nb | uint8 ep_bits[n][nb] | int32 nr | f64 rand_stream[n][nr]   (0 = none)
 //        reset_proto 1: slot 0 = reset, slot 1 = reset, then T ticks (actions[..][0] == -128: explicit reset)   (multi-agent fixtures)
 //        reset_proto 0: slot 0 = reset, then T ticks                                                            (scalar fixtures)
-//   out: per env and slot: step_type[A] int32 | frame int32 | reward[A*K] f64 | cumulative[A*K] f64 | board[HW] u8
+//   out: per env and slot: step_type[A] int32 | term_reason[A] int32 | frame int32 | reward[A*K] f64 | cumulative[A*K] f64 | board[HW] u8
 #define __HIPCC__ 1
 #define SGW_PLAIN_STORES 1
 #include <cstdio>
@@ -111,6 +111,11 @@ template <class F> static void emit(Host& h, const typename F::State& s, const d
     int32_t st;
     if constexpr (F::PER_AGENT) st = F::agent_step_type(s, ag); else st = s.step_type;
     fwrite(&st, 4, 1, out);
+  }
+  for (int ag = 0; ag < sp.A; ++ag) {                      // what k_engine stores as term_reason (sgw_kernels.hpp emit)
+    int32_t tr;
+    if constexpr (F::PER_AGENT) tr = F::agent_term(s, ag); else tr = (s.step_type == ST_LAST) ? s.term : (int)SGW_TERM_NONE;
+    fwrite(&tr, 4, 1, out);
   }
   int32_t fr = s.frame; fwrite(&fr, 4, 1, out);
   std::vector<double> rew(sp.A * sp.K, 0.0), cum(sp.A * sp.K, 0.0);

@@ -31,7 +31,8 @@ VIEW_FIXTURES = [n for n in G.fixture_names(["firemaker_", "ima_"])]
 
 def test_fixture_lists_are_complete():
   assert len(STATS_FIXTURES) == 40      # 8 of them the `_quit` / `_quitlate` tapes of the four multi-objective families
-  assert len(RGB_FIXTURES) >= 60 and len(LAYER_FIXTURES) >= 30 and len(VIEW_FIXTURES) >= 30
+  assert len(RGB_FIXTURES) >= 60 and len(LAYER_FIXTURES) >= 30
+  assert len(VIEW_FIXTURES) == 39       # 8 of them the `_quit` / `_quitlate` tapes of firemaker_ex_ma and island_navigation_ex_ma
 
 
 @pytest.mark.parametrize("name", STATS_FIXTURES)

@@ -56,7 +56,7 @@ def run(exe, tmp_path, spec, actions, rng, proto, bits=None, stream=None):
   S = T + 1 + proto
   LA = 2 if spec.family in (N.ISLAND_NAVIGATION_EX_MA, N.AINTELOPE_SAVANNA) else 1
   AK, HW = LA * spec.K, spec.H * spec.W
-  dt = np.dtype([("step_type", np.int32, (LA,)), ("frame", np.int32), ("reward", np.float64, (AK,)),
+  dt = np.dtype([("step_type", np.int32, (LA,)), ("term_reason", np.int32, (LA,)), ("frame", np.int32), ("reward", np.float64, (AK,)),
                  ("cumulative", np.float64, (AK,)), ("board", np.uint8, (HW,))], align=False)
   rec = np.fromfile(outp, dtype=dt).reshape(E, S)
   return {k: rec[k] for k in dt.names}
@@ -78,6 +78,9 @@ def test_multi_agent_family_source_on_the_host_matches_reference(name, exe, tmp_
   E, S = fx["step_type"].shape[:2]
   sl = slice(1, None)
   G.assert_same(name + ".step_type", got["step_type"][:, sl, :A], fx["step_type"][:, sl])
+  tr = got["term_reason"][:, sl, :A].copy()
+  tr[tr == N.TERM_NONE] = -1                                        # (the reference's dict has no reason before every agent is done)
+  G.assert_same(name + ".term_reason", tr, fx["term_reason"][:, sl])
   G.assert_same(name + ".frame", got["frame"][:, sl], fx["frame"][:, sl])
   G.assert_same(name + ".board", got["board"][:, sl].reshape(fx["board"][:, sl].shape), fx["board"][:, sl])
   G.assert_same(name + ".reward", got["reward"][:, sl].reshape(E, S - 1, 2, spec.K)[:, :, :A], fx["reward"][:, sl])

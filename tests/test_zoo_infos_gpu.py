@@ -256,3 +256,80 @@ def test_zoo_parallel_firemaker_direction_modes_against_the_oracle():
       obs, rewards, terms, truncs, infos = env.step({a: int(actions[0, t, q]) for q, a in enumerate(names)})
       check(t + 1, obs, infos)
     env.close()
+
+
+def test_zoo_parallel_round_with_a_quit_against_the_oracle():
+  """Actions.QUIT (9) goes straight through the parallel facade.  island_navigation_ex_ma level 10 (no water: no drape rewrites a
+  reason): a round in which agent_2 submits 9 next to agent_1's move terminates every agent, whichever of them the shuffle plays
+  first (a play behind the QUIT is dropped), with reason QUIT for every agent in `infos`; the next step is the auto-reset that
+  follows any other ending.  Boards, rewards, terminations and reasons of every round == the oracle's."""
+  from oracle import oracle_ima as OI
+  from oracle import oracle_ma as OM
+  kw = dict(level=10, max_iterations=30)
+  names = ["agent_1", "agent_2"]
+  plays = set()
+  for seed in (11, 12, 13, 14):
+    rnd = np.random.default_rng(seed)
+    T = 12
+    actions = rnd.integers(0, 5, size=(1, T, 2)).astype(np.int8)
+    actions[0, 4, 1] = 9
+    want = OI.run_streams(OI.make_config(**kw), actions, np.stack([OM.rng_state_words(seed)]))
+    plays.add(int(want["frame"][0, 6] - want["frame"][0, 5]))
+    env = Z.GridworldZooParallelEnv("island_navigation_ex_ma", seed=seed, **kw)
+    env.reset(); env.reset()
+    for t in range(T):
+      obs, rewards, terms, truncs, infos = env.step({a: int(actions[0, t, i]) for i, a in enumerate(names)})
+      st = want["step_type"][0, t + 2]
+      assert np.array_equal(infos["agent_1"]["ascii_codes"], want["board"][0, t + 2]), (seed, t)
+      for i, a in enumerate(names):
+        assert terms[a] == (st[i] >= 2) and truncs[a] is False, (seed, t, a)
+        if st[i] != 0:
+          assert np.array_equal(rewards[a], want["reward"][0, t + 2, i]), (seed, t, a)
+        tr = infos[a]["extra_observations"].get("termination_reason")
+        if (st >= 2).all():
+          assert tr == {c: {"1": int(want["term_reason"][0, t + 2, 0]), "2": int(want["term_reason"][0, t + 2, 1])} for c in "12"}, (seed, t)
+        else:
+          assert tr is None, (seed, t)
+      if t == 4:
+        assert all(terms.values()) and (want["term_reason"][0, t + 2] == 3).all() and want["discount"][0, t + 2] == 0.0
+        assert infos["agent_1"]["discount"] == 0.0
+      if t == 5:
+        assert (st == 0).all() and not any(terms.values()) and all(np.all(np.asarray(r) == 0) for r in rewards.values())
+    env.close()
+  assert plays == {1, 2}, "the quitter played last (a whole round) for one seed and first (agent_1's play dropped) for another"
+
+
+def test_zoo_aec_step_with_a_quit_against_the_oracle():
+  """The AEC facade submits {agent: action} alone, so a 9 is a solo QUIT round: the quitter is flagged terminated, `infos` carry
+  reason QUIT for EVERY agent (the engine's episode is over for all of them), and -- as after any other ending (zoo_aec.py:
+  784-797) -- the other agent's next step starts the new episode, while the flagged agent's dead step takes only None."""
+  from ai_safety_gridworlds_amd.helpers.gridworld_zoo_aec_env import GridworldZooAecEnv
+  from oracle import oracle_ima as OI
+  from oracle import oracle_ma as OM
+  kw, seed = dict(level=10, max_iterations=30), 21
+  plan = [(0, 3), (1, 2), (0, 1), (1, 9), (0, 4)]          # (agent index, action): agent_2 quits on its second turn
+  actions = np.full((1, len(plan), 2), -1, np.int8)
+  for t, (i, a) in enumerate(plan):
+    actions[0, t, i] = a
+  want = OI.run_streams(OI.make_config(**kw), actions, np.stack([OM.rng_state_words(seed)]))
+  env = GridworldZooAecEnv("island_navigation_ex_ma", seed=seed, **kw)
+  env.reset(); env.reset()
+  for t, (i, a) in enumerate(plan[:4]):
+    assert env.agent_selection == env.possible_agents[i]
+    env.step(a)
+    assert np.array_equal(env.state[0], np.vectorize(chr)(want["board"][0, t + 2])), t
+    assert np.array_equal(env.rewards[env.possible_agents[i]], want["reward"][0, t + 2, i]), t
+  assert (want["step_type"][0, 5] == 2).all() and (want["term_reason"][0, 5] == 3).all()      # the oracle: everybody LAST, reason QUIT
+  assert env.terminations["agent_2"] is True
+  assert env.infos["agent_2"]["extra_observations"]["termination_reason"] == {c: {"1": 3, "2": 3} for c in "12"}
+  assert env.infos["agent_2"]["discount"] == 0.0
+  assert env.agent_selection == "agent_1" and env.terminations["agent_1"] is False            # flagged when it steps next, as after MAX_STEPS
+  env.step(4)                                                                                 # ... which is the auto-reset round
+  assert (want["step_type"][0, 6] == 0).all()
+  assert np.array_equal(env.state[0], np.vectorize(chr)(want["board"][0, 6]))
+  assert env.agent_selection == "agent_2"
+  with pytest.raises(ValueError, match="only valid action is None"):
+    env.step(1)
+  env.step(None)
+  assert env.agents == ["agent_1"]
+  env.close()

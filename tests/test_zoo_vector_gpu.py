@@ -81,3 +81,42 @@ def test_zoo_vector_value_mapped_observations_and_python_int_actions():
   o2, r, term, trunc, info = env.step({"agent_1": 2, "agent_S": torch.zeros(130, dtype=torch.int64, device=env.device)})
   assert r["agent_1"].shape == (130, 2) and r["agent_S"].shape == (130, 3) and float(r["agent_1"][:, 0].max()) == -1.0
   env.close()
+
+
+def test_zoo_vector_round_with_a_quit_matches_oracle():
+  """Actions.QUIT (9) goes straight through the batched wrapper: on a ragged batch every third env gets a 9 from one agent in
+  round 5 and from another in round 9, next to the other agents' moves (so some plays are dropped behind the QUIT).  Every
+  agent of such an env is terminated, infos carry reason QUIT (3), and the next step is the auto-reset of any other ending --
+  all of it, every round, against the multi-agent oracle."""
+  from oracle import oracle_ma as OM
+  E, T, seed, kw = 130, 16, 31, dict(amount_agents=3, max_iterations=60)
+  actions = np.stack([philox.actions(seed, np.arange(E), np.arange(T), 0, 5, agent=a) for a in range(3)], axis=-1)   # [T, E, 3]
+  actions[5, 0::3, 0] = 9
+  actions[9, 1::3, 2] = 9
+  rng = np.stack([OM.rng_state_words(seed + e) for e in range(E)])
+  want = OM.run_streams(OM.make_config(**kw), np.transpose(actions, (1, 0, 2)).copy(), rng, nthreads=16)
+  env = GridworldZooVectorEnv("firemaker_ex_ma", num_envs=E, seed=seed, **kw)
+  names = env.possible_agents
+  dev_actions = torch.from_numpy(actions).to(env.device)
+  env.reset()
+  for t in range(T):
+    obs, rewards, terms, truncs, infos = env.step({a: dev_actions[t, :, SLOT[a]] for a in names})
+    for a in names:
+      q = SLOT[a]
+      view = want["view_worker"][:, t + 1, q] if q < 2 else want["view_supervisor"][:, t + 1]
+      assert np.array_equal(obs[a].cpu().numpy(), view), (t, a)
+      assert np.array_equal(terms[a].cpu().numpy(), want["step_type"][:, t + 1, q] >= 2), (t, a)
+      assert np.array_equal(infos[a]["step_type"].cpu().numpy(), want["step_type"][:, t + 1, q]), (t, a)
+      tr = infos[a]["term_reason"].cpu().numpy().astype(np.int16)
+      tr[tr == 255] = -1
+      assert np.array_equal(tr, want["term_reason"][:, t + 1, 0]), (t, a)
+      assert np.array_equal(infos[a]["cumulative_reward"].cpu().numpy(), want["cumulative"][:, t + 1, q, :2 if q < 2 else 3]), (t, a)
+      assert np.array_equal(infos[a]["discount"].cpu().numpy(), want["discount"][:, t + 1], equal_nan=True), (t, a)
+    if t in (5, 9):
+      hit = slice(0, None, 3) if t == 5 else slice(1, None, 3)
+      assert all(bool(terms[a][hit].all()) for a in names) and bool((infos[names[0]]["term_reason"][hit] == 3).all())
+      assert bool((infos[names[0]]["discount"][hit] == 0).all())
+    if t in (6, 10):                                                       # the round after: FIRST for everybody, as after MAX_STEPS
+      hit = slice(0, None, 3) if t == 6 else slice(1, None, 3)
+      assert all(bool((infos[a]["step_type"][hit] == 0).all()) for a in names)
+  env.close()
