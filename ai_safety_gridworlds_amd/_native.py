@@ -12,6 +12,7 @@ ABI_VERSION = 8
 ISLAND_NAVIGATION_EX, BOAT_RACE_EX, BOAT_RACE, SAFE_INTERRUPTIBILITY, FIREMAKER_EX_MA, ISLAND_NAVIGATION_EX_MA, TILE_EVENTS, SIDE_EFFECTS_SOKOBAN, CONVEYOR_BELT, TOMATO_WATERING, FRIEND_FOE, WHISKY_GOLD, ROCKS_DIAMONDS, AINTELOPE_SAVANNA = range(14)
 FIRST, MID, LAST, DEAD = 0, 1, 2, 3
 TERM_NONE = 255
+SEED_LOW32 = 1
 
 
 class SgwError(RuntimeError):
@@ -102,6 +103,9 @@ def lib():
     L.sgw_step_lds_bytes.restype = C.c_int64
   L.sgw_set_episode_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
   L.sgw_set_rng_state.argtypes = [C.c_void_p, C.c_void_p]
+  if hasattr(L, "sgw_seed_rng"):                            # (an SGW_LIBRARY build from before the symbols)
+    L.sgw_seed_rng.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.sgw_pcg64_from_seeds.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
   L.sgw_set_random_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
   L.sgw_set_family_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
   L.sgw_pow_selfcheck.restype = C.c_int64
@@ -161,7 +165,8 @@ EXPORTS = [
     "sgw_set_rng_state", "sgw_set_random_stream", "sgw_set_family_table", "sgw_pow_f64", "sgw_pow_selfcheck", "sgw_reset", "sgw_step", "sgw_step_n", "sgw_rollout", "sgw_replay", "sgw_group_create", "sgw_group_destroy", "sgw_group_step_n", "sgw_group_rollout", "sgw_read_returns", "sgw_fill_actions",
     "sgw_accumulate_returns", "sgw_observe", "sgw_derived_stats", "sgw_observe_layers", "sgw_state_layers", "sgw_view_bytes", "sgw_agent_views", "sgw_agent_layer_views", "sgw_state_words", "sgw_get_state", "sgw_set_state",
     "sgw_step_shape", "sgw_layer_coords", "sgw_agent_layer_coords", "sgw_step_lds_bytes",
-    "sgw_sizeof_episodes", "sgw_episode_scratch_bytes", "sgw_log_episodes"]
+    "sgw_sizeof_episodes", "sgw_episode_scratch_bytes", "sgw_log_episodes",
+    "sgw_seed_rng", "sgw_pcg64_from_seeds"]
 
 
 def check(rc, what=""):

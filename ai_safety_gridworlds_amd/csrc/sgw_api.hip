@@ -29,6 +29,7 @@
 #include "sgw_savanna_layers.hpp"
 #include "sgw_coords.hpp"
 #include "sgw_episodes.hpp"
+#include "sgw_seed.hpp"
 
 using namespace sgw;
 
@@ -313,6 +314,36 @@ int sgw_set_rng_state(sgw_engine* e, const uint64_t* pcg_state_dev) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(0));
   e->rng_set = 1;
+  return SGW_OK;
+}
+
+int sgw_seed_rng(sgw_engine* e, const uint64_t* seeds_dev, uint64_t seed_base, const uint32_t* layout_seeds_dev,
+                 const uint8_t* mask_dev, int flags, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_seed_rng: null engine");
+  if (flags & ~SEED_FLAGS_ALL) return fail(SGW_ERR_ARG, "sgw_seed_rng: unknown flag bits");
+  if (e->spec.family != SGW_FIREMAKER_EX_MA && e->spec.family != SGW_ISLAND_NAVIGATION_EX_MA &&
+      e->spec.family != SGW_AINTELOPE_SAVANNA)
+    return fail(SGW_ERR_UNSUPPORTED, "sgw_seed_rng: this game family has no env-side RNG stream");
+  if (mask_dev && !e->rng_set)
+    return fail(SGW_ERR_ARG, "sgw_seed_rng: a masked call reseeds some envs of a seeded engine; seed every env first (mask_dev == NULL, "
+                "sgw_set_rng_state or sgw_set_state)");
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_seed_rng, dim3((unsigned)((e->n_pad + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->state_dev, e->n_pad,
+                     e->n_envs, e->ks.words, seeds_dev, seed_base + (uint64_t)e->env_id_base, layout_seeds_dev, mask_dev, flags);
+  HIP_TRY(hipGetLastError());
+  if (!mask_dev) e->rng_set = 1;
+  return SGW_OK;
+}
+
+int sgw_pcg64_from_seeds(const uint64_t* seeds_dev, uint64_t seed_base, int64_t id_base, const uint32_t* layout_seeds_dev, int flags,
+                         int64_t n, uint64_t* pcg_state_dev, int device, void* stream) {
+  if (!pcg_state_dev || n < 0 || (flags & ~SEED_FLAGS_ALL))
+    return fail(SGW_ERR_ARG, "sgw_pcg64_from_seeds: null output, negative n or unknown flag bits");
+  if (n == 0) return SGW_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(k_pcg64_from_seeds, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seeds_dev,
+                     seed_base + (uint64_t)id_base, layout_seeds_dev, flags, (long long)n, pcg_state_dev);
+  HIP_TRY(hipGetLastError());
   return SGW_OK;
 }
 

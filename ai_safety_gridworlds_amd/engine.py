@@ -413,6 +413,50 @@ class BatchedEngine(object):
       words[i] = (st["state"] >> 64, st["state"] & m, st["inc"] >> 64, st["inc"] & m)
     self.set_rng_state(words)
 
+  def _seed_words(self, v, what, bits):
+    """v -> a device tensor [N] whose bytes are the values mod 2^bits (int64 for 64, int32 for 32): a device tensor stays on the
+    device, a host int (every env the same) or array is uploaded once."""
+    dt, ndt, udt = (torch.int64, np.int64, np.uint64) if bits == 64 else (torch.int32, np.int32, np.uint32)
+    if torch.is_tensor(v):
+      t = v.reshape(-1)
+      if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError("%s must be integers" % what)
+      if bits == 32 and t.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        t = t.to(torch.int64) & 0xFFFFFFFF
+        t = (t - ((t >> 31) << 32)).to(torch.int32)              # the low 32 bits as the int32 with the same bytes
+      elif t.dtype != dt:
+        t = t.view(dt) if t.dtype.itemsize == dt.itemsize else t.to(dt)
+      t = t.to(self.device).contiguous()
+    else:
+      a = np.asarray(v, dtype=object).reshape(-1)
+      if a.size == 1:
+        a = np.repeat(a, self.n_envs)
+      a = np.array([int(x) & ((1 << bits) - 1) for x in a], dtype=udt).view(ndt)
+      t = torch.from_numpy(a).to(self.device)
+    if t.numel() != self.n_envs:
+      raise ValueError("%s must have n_envs entries" % what)
+    return t
+
+  def seed_rng(self, seeds=None, base=0, layout_seeds=None, mask=None, low32=False):
+    """The env generators seeded on the device (sgw_seed_rng): one launch on the current stream, no synchronisation.  Env i
+    gets Generator(PCG64(SeedSequence(s_i))) with s_i = seeds[i], or base + global env id with seeds=None; low32: s_i & 0xFFFFFFFF
+    first (the reference's reset(seed=)); layout_seeds: s_i = crc32(be32(s_i) + be32(layout_seeds[i]) + be32(17122023)), the
+    reference's stream of a new env layout.  mask [N]: only those envs, the others keep every byte of their state (the
+    generators must have been set before).  seeds / layout_seeds / mask: device tensors, or host ints / arrays (uploaded once)."""
+    keep = []
+    sptr = lptr = mptr = None
+    if seeds is not None:
+      keep.append(self._seed_words(seeds, "seeds", 64)); sptr = keep[-1].data_ptr()
+    if layout_seeds is not None:
+      keep.append(self._seed_words(layout_seeds, "layout_seeds", 32)); lptr = keep[-1].data_ptr()
+    if mask is not None:
+      mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).contiguous()
+      if mask.numel() != self.n_envs:
+        raise ValueError("mask must have n_envs entries")
+      mptr = mask.data_ptr()
+    N.check(self._lib.sgw_seed_rng(self._h, sptr, int(base) & ((1 << 64) - 1), lptr, mptr, N.SEED_LOW32 if low32 else 0, self._stream()),
+            "sgw_seed_rng")
+
   def set_rng_state(self, words):
     """uint64 [N, 4] = PCG64 (state_hi, state_lo, inc_hi, inc_lo) per env."""
     t = torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint64).view(np.int64)).to(self.device)

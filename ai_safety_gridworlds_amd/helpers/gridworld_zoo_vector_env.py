@@ -80,10 +80,13 @@ class GridworldZooVectorEnv(object):
     self._acts = torch.zeros((self.num_envs, sp.A), dtype=torch.int8, device=self.device)
     self._never = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)            # truncated: always False
     self._up = torch.full((self.num_envs,), 2, dtype=torch.uint8, device=self.device)         # Directions.UP: the fixed-direction envs
-    if sp.family == N.FIREMAKER_EX_MA or getattr(sp, "needs_rng", False):
-      # env i draws from Generator(PCG64(SeedSequence(seed + global id))): what seeding.np_random gives N separately seeded envs
-      base = 0 if seed is None else int(seed)
-      self._env.engine.set_rng_seeds(base + env_id_base + np.arange(self.num_envs))
+    # the original seed of env i (environment_data[SEED] of the reference) is (seed or 0) + its global id
+    self._seed_base, self._env_id_base = (0 if seed is None else int(seed)), int(env_id_base)
+    self._has_rng = bool(sp.family == N.FIREMAKER_EX_MA or getattr(sp, "needs_rng", False))
+    if self._has_rng:
+      # env i draws from Generator(PCG64(SeedSequence(seed + global id))): what seeding.np_random gives N separately seeded envs;
+      # seeded by one launch (sgw_seed_rng: the engine adds env_id_base itself)
+      self._env.engine.seed_rng(base=self._seed_base)
 
   @property
   def agents(self):
@@ -158,7 +161,41 @@ class GridworldZooVectorEnv(object):
         infos[a]["info_agent_observation_layers_cube"] = agent_cubes[self._slots[i]]
     return obs, dict(rewards), dict(terms), dict(truncs), infos
 
-  def reset(self, mask=None):
+  def _reseed(self, mask, seed, layout):
+    """The reference's reseeding at a reset that names a seed or an env layout (safety_game_moma.py:822-864), for the masked envs:
+    one launch (sgw_seed_rng) in front of the engine reset."""
+    if not self._has_rng:
+      raise N.SgwError("reset(seed= / env_layout_seed=): this env configuration draws from no env generator")
+    if seed is not None:                                         # new_seed = int(seed) & 0xFFFFFFFF; the layout seed plays no part
+      if torch.is_tensor(seed):
+        self._env.engine.seed_rng(seeds=seed, mask=mask, low32=True)
+      else:
+        self._env.engine.seed_rng(base=int(seed), mask=mask, low32=True)
+      return
+    # new_seed = zlib.crc32(b''.join(x.to_bytes(4, 'big') for x in (original_seed, env_layout_seed, 17122023)))
+    lo, hi = self._seed_base + self._env_id_base, self._seed_base + self._env_id_base + self.num_envs - 1
+    if lo < 0 or hi >= 1 << 32:
+      raise OverflowError("int too big to convert" if hi >= 1 << 32 else "can't convert negative int to unsigned")
+    if not torch.is_tensor(layout):
+      vals = [int(x) for x in np.asarray(layout, dtype=object).reshape(-1)]
+      if any(x < 0 for x in vals):
+        raise OverflowError("can't convert negative int to unsigned")
+      if any(x >= 1 << 32 for x in vals):
+        raise OverflowError("int too big to convert")
+    self._env.engine.seed_rng(base=self._seed_base, layout_seeds=layout, mask=mask)
+
+  def reset(self, mask=None, seed=None, options=None):
+    """New episode in every env (or where mask[n] != 0).  seed (an int: env i gets (seed + global id) & 0xFFFFFFFF; or an [N]
+    tensor: seed[i] & 0xFFFFFFFF) and options={"env_layout_seed": L} (an int or an [N] tensor; "trial_no" is its alias; env i gets
+    crc32(original seed of env i, L, 17122023)) first give those envs a new generator stream, as the reference's reset does; naming
+    a layout seed always reseeds."""
+    layout = None
+    if options:
+      layout = options.get("env_layout_seed")
+      if options.get("trial_no") is not None:
+        layout = options["trial_no"]
+    if seed is not None or layout is not None:
+      self._reseed(mask, seed, layout)
     o = self._env.engine.reset(mask)             # straight to the engine: the L4 TimeStep bookkeeping is a dozen torch launches
     self._env._last = o
     obs, _, _, _, infos = self._pack(o)

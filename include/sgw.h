@@ -183,6 +183,25 @@ int sgw_set_random_stream(sgw_engine* e, const double* u_dev, int n_per_env, uin
  * advances the streams exactly like numpy (random(), buffered next_uint32, shuffle, random_interval). */
 int sgw_set_rng_state(sgw_engine* e, const uint64_t* pcg_state_dev);
 
+/* The same generators seeded ON THE DEVICE, per env and under a mask: one launch on the caller's stream, no synchronisation, no
+ * allocation, capturable.  The seed of env n is seeds_dev[n] (uint64 [N]), or with seeds_dev == NULL seed_base + env_id_base + n
+ * mod 2^64 (the global env id: results do not depend on the GPU count).  With SGW_SEED_LOW32 it is then cut to its low 32 bits.
+ * With layout_seeds_dev != NULL (uint32 [N]) it becomes zlib.crc32(be32(low 32 bits of the seed) + be32(layout_seeds[n]) +
+ * be32(17122023)): the reference's stream for a new env layout (safety_game_moma.py:845-852).  The generator of env n is then
+ * np.random.PCG64(np.random.SeedSequence(seed)) with its buffered next_uint32 cleared, as sgw_set_rng_state leaves it.
+ * mask_dev uint8 [N] or NULL: with a mask only the envs with mask_dev[n] != 0 are written, no byte of another env's state is
+ * touched, and the engine's generators must have been set before (SGW_ERR_ARG otherwise); NULL seeds every env and counts as
+ * sgw_set_rng_state.  To start a reseeded env over, follow with sgw_reset under the same mask on the same stream.
+ * SGW_ERR_UNSUPPORTED for the families sgw_set_rng_state refuses; SGW_ERR_ARG for a null engine or unknown flag bits. */
+#define SGW_SEED_LOW32 1   /* seeds are cut to their low 32 bits first: the reference's reset(seed=) (safety_game_moma.py:859) */
+int sgw_seed_rng(sgw_engine* e, const uint64_t* seeds_dev, uint64_t seed_base, const uint32_t* layout_seeds_dev,
+                 const uint8_t* mask_dev, int flags, void* stream);
+/* The same arithmetic without an engine: pcg_state_dev uint64 [n, 4] = (state_hi, state_lo, inc_hi, inc_lo) of the generator of
+ * seed n, the seeds as above with id_base in the place of env_id_base.  Exposed so that callers and tests can check the device
+ * against their numpy.  SGW_ERR_ARG for a null output, n < 0 or unknown flag bits. */
+int sgw_pcg64_from_seeds(const uint64_t* seeds_dev, uint64_t seed_base, int64_t id_base, const uint32_t* layout_seeds_dev,
+                         int flags, int64_t n, uint64_t* pcg_state_dev, int device, void* stream);
+
 /* Family lookup table in device memory, copied from the host: aintelope_savanna's visit-count rewards
  * [gold_reward[0 .. max_iterations + 1], silver_reward[0 .. max_iterations + 1]], entry v = SCORE * (log(v + 2, base) -
  * log(v + 1, base)) evaluated by the caller with the reference's own math.log (aintelope_savanna.py:956-983), so the
