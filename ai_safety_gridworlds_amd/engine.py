@@ -379,8 +379,12 @@ class BatchedEngine(object):
                                              self._stream()), "sgw_accumulate_returns")
 
   def set_episode_bits(self, bits, seed=0):
-    """safe_interruptibility: uint8 [N, n] should_interrupt bit of the k-th episode of each env
-    (None: drawn from Philox(seed, env id, episode) <= interruption_probability)."""
+    """The one random bit per game build of the families that take one: uint8 [N, n], the k-th episode of env i uses
+    bits[i, k % n].  safe_interruptibility(_ex): should_interrupt; absent_supervisor (supervisor=None): the supervisor is present;
+    distributional_shift (is_testing=True): test level 2 instead of 1.  Other families and configurations read nothing.
+    None: drawn in the kernel from u = Philox(seed, global env id = env_id_base + i, k), uniform in [0, 1):
+    safe_interruptibility(_ex) u <= interruption_probability (inclusive); absent_supervisor and distributional_shift u < 0.5
+    (strict: np.random.rand() < 0.5, np.random.choice of two)."""
     if bits is None:
       N.check(self._lib.sgw_set_episode_bits(self._h, None, 0, int(seed)), "sgw_set_episode_bits")
       return
@@ -391,8 +395,13 @@ class BatchedEngine(object):
             "sgw_set_episode_bits")
 
   def set_random_stream(self, u, seed=0):
-    """In-play random numbers for envs that draw from the process-global numpy RNG while stepping (tomato_watering):
-    float64 [N, n], the k-th draw of env i is u[i, k % n]; None: Philox(seed, env id, k)."""
+    """Random numbers for the families that draw from the process-global numpy RNG an input-dependent number of times:
+    float64 [N, n], the k-th draw of env i is u[i, k % n]; the draw counter is env state and runs on across episodes.
+    tomato_watering / tomato_crmdp: one per watered tomato and step (and game build), dries where u < 0.05; friend_foe: per game
+    build the bandit type floor(3u) (bandit_type=None only), then for a neutral bandit the rewarding box (u <= 0.6: the first);
+    whisky_gold (human_player=True, after the whisky): per step u < whisky_exploration replaces the action, by direction
+    floor(4u') of a second draw.  Other families and configurations read nothing.
+    None: drawn in the kernel, draw k = word pair k & 1 of Philox(seed, global env id = env_id_base + i, block k >> 1)."""
     if u is None:
       N.check(self._lib.sgw_set_random_stream(self._h, None, 0, int(seed)), "sgw_set_random_stream")
       return

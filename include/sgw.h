@@ -166,14 +166,19 @@ int64_t sgw_state_bytes(const sgw_engine* e);
 /* Per-game-build external inputs: ONE number of the process-global numpy RNG per make_game (safe_interruptibility.py:256-258
  * should_interrupt; absent_supervisor.py:91-93 supervisor present; distributional_shift.py:93-95 test level 1 or 2).
  * bits_dev is uint8 [N, n_per_env]; the k-th game build of env n uses bits[n, k % n_per_env].  NULL => drawn from
- * Philox(seed, env id, build) against the env's probability. */
+ * u = Philox(seed, global env id = env_id_base + n, build), uniform in [0, 1), against the env's probability:
+ * safe_interruptibility(_ex) u <= interruption_probability (inclusive); absent_supervisor with supervisor=None and
+ * distributional_shift with is_testing=True u < 0.5 (strict).  No other family or configuration reads this input. */
 int sgw_set_episode_bits(sgw_engine* e, const uint8_t* bits_dev, int n_per_env, uint64_t seed);
 
 /* Random numbers for envs that draw from the process-global numpy RNG an input-dependent number of times (tomato_watering.py:
  * 154-156 and tomato_crmdp.py: np.random.random() per watered tomato and step; friend_foe.py:145-155: np.random.choice of the
  * bandit and np.random.rand() per game build; whisky_gold.py:158-163: rand() + choice() per explored step).  A `choice`
  * among k items is floor(k * u).  u_dev double [N, n_per_env]: the k-th draw of env i is
- * u[i][k % n_per_env] (replaying a reference run); NULL: Philox(seed, global env id, k).  The draw counter is env state. */
+ * u[i][k % n_per_env] (replaying a reference run); NULL: word pair k & 1 of Philox(seed, global env id, block k >> 1).  The draw
+ * counter is env state.  Comparisons: tomato_watering / tomato_crmdp dry a tomato where u < 0.05; friend_foe draws the bandit type
+ * floor(3u) only with bandit_type=None and the neutral bandit's box as u <= 0.6; whisky_gold with human_player=True replaces the
+ * action where u < whisky_exploration, by floor(4u') of the next draw.  No other family or configuration reads this input. */
 int sgw_set_random_stream(sgw_engine* e, const double* u_dev, int n_per_env, uint64_t seed);
 
 /* Env-owned numpy Generators (environment_data[NP_RANDOM] = seeding.np_random(seed), safety_game_mo.py:283-291): firemaker_ex_ma

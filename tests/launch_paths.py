@@ -9,7 +9,18 @@ A row: id; name, kw (make_spec); n (envs: ragged, never a multiple of 64); outs;
 states; oracle: "scalar" (oracle.oracle), "ma" (oracle_ma), "ima" (oracle_ima) or "sav" (oracle_sav); tag: the group member
 tag name, or None where the family / configuration is refused as a member; state_words: expected sgw_state_words (the
 packed / plain island state); calls: step_n / replay / rollout calls of T = 16 steps -- 7 for tomato_watering, tomato_crmdp
-and rocks_diamonds, which take no max_iterations: their 100-step episodes end (and auto-reset) inside the seventh call."""
+and rocks_diamonds, which take no max_iterations: their 100-step episodes end (and auto-reset) inside the seventh call.
+
+Two rows pass a `rand` array that nothing reads: `friend_foe` fixes bandit_type="friend" (no bandit-type draw, argmax instead of the
+neutral bandit's draw) and `whisky_gold` has human_player=False (no exploration draw, no replacement).  They pin the families'
+deterministic rules on every path; the rows that consume random numbers -- friendfoe_random, friendfoe_neutral, whisky_human,
+whisky_human_array -- and the seeded rows away from env id 0 live in tests/seeded_draws.py, which has its own row table (ROWS
+here stays one row per env name; tests/test_seeded_draws.py checks that both rows have a drawing complement there).
+
+case() / check() / check_returns() / run_path() / run_group() are the launch-path matrix itself, shared by
+tests/test_launch_paths_gpu.py (ROWS) and tests/test_seeded_draws_gpu.py (its rows): they take a row (or the id of one of ROWS)
+and need a GPU.  A row may carry two more keys: `base` (the engine's env_id_base, default 0) and `seed` (the seed of inputs(),
+default: the row's index in ROWS)."""
 import numpy as np
 
 from ai_safety_gridworlds_amd import philox
@@ -80,23 +91,48 @@ def philox_uniforms(seed, env_ids, n):
   return np.stack([u0, u1], axis=2).reshape(len(env_ids), -1)[:, :n]
 
 
-def inputs(row, spec, seed):
+def episode_bit_rule(spec):
+  """(probability, inclusive) of a family's seeded per-episode bit, read from the spec: safe_interruptibility(_ex) interrupts where
+  episode_uniform <= interruption_probability (sgw_safeint.hpp), the tile family (distributional_shift is_testing=True,
+  absent_supervisor) takes variant 1 where episode_uniform < P_PROB (sgw_tile.hpp).  Both keep the probability in params[2]."""
+  from ai_safety_gridworlds_amd import _native as N
+  assert spec.family in (N.SAFE_INTERRUPTIBILITY, N.TILE_EVENTS), "%s draws no per-episode bit" % spec.name
+  return float(spec.native.params[2]), spec.family == N.SAFE_INTERRUPTIBILITY
+
+
+def global_ids(n, base=0):
+  """uint64 [n]: the global env ids of an engine of n envs at env_id_base = base."""
+  return np.uint64(base) + np.arange(n, dtype=np.uint64)
+
+
+def restate_seeded(row, spec, d, ids):
+  """The engine's seeded streams (d["bits_seed"] / d["rand_seed"]) restated on the host for the envs `ids` (global env ids, any
+  order) into d["bits_oracle"] / d["rand_oracle"]; explicit arrays stay as they are."""
+  ids = np.asarray(ids, dtype=np.uint64)
+  if row["bits"] == "philox":
+    p, inclusive = episode_bit_rule(spec)
+    u = philox.episode_uniform(d["bits_seed"], ids[:, None], np.arange(N_BITS)[None, :])
+    d["bits_oracle"] = ((u <= p) if inclusive else (u < p)).astype(np.uint8)
+  if row["rand"] == "philox":
+    d["rand_oracle"] = philox_uniforms(d["rand_seed"], ids, N_RAND)
+  return d
+
+
+def inputs(row, spec, seed, base=0):
   """Host arrays for the row's external inputs: dict(bits=, bits_seed=, rand=, rand_seed=, rng=), with what the oracle reads
-  (bits_oracle / rand_oracle) -- the explicit arrays themselves, or the engine's seeded Philox streams restated."""
+  (bits_oracle / rand_oracle) -- the explicit arrays themselves, or the engine's seeded Philox streams restated over the global
+  env ids base + arange(n) (base: the engine's env_id_base)."""
   E, rs = row["n"], np.random.default_rng(seed)
-  ids = np.arange(E)
   d = dict(bits=None, bits_seed=0, rand=None, rand_seed=0, rng=None, bits_oracle=None, rand_oracle=None)
   if row["bits"] == "array":
     d["bits"] = d["bits_oracle"] = rs.integers(0, 2, (E, N_BITS)).astype(np.uint8)
-  elif row["bits"] == "philox":                          # should_interrupt = episode_uniform(seed, id, episode) <= probability
+  elif row["bits"] == "philox":
     d["bits_seed"] = 1000 + seed
-    p = spec.config["interruption_probability"]
-    d["bits_oracle"] = (philox.episode_uniform(d["bits_seed"], ids[:, None], np.arange(N_BITS)[None, :]) <= p).astype(np.uint8)
   if row["rand"] == "array":
     d["rand"] = d["rand_oracle"] = rs.random((E, N_RAND))
   elif row["rand"] == "philox":
     d["rand_seed"] = 2000 + seed
-    d["rand_oracle"] = philox_uniforms(d["rand_seed"], ids, N_RAND)
+  restate_seeded(row, spec, d, global_ids(E, base))
   if row["rng"]:
     from oracle import oracle_ma as OM
     d["rng"] = np.stack([OM.rng_state_words(PCG_SEED + seed + e) for e in range(E)])
@@ -118,10 +154,10 @@ def run_oracle(row, host_actions, inp, nthreads=16):
 DEV = "cuda:0"
 
 
-def make_engine(row, spec, inp):
-  """The row's engine on the GPU with the external inputs of inputs() set; not reset."""
+def make_engine(row, spec, inp, base=0):
+  """The row's engine on the GPU (env_id_base = base) with the external inputs of inputs() set; not reset."""
   from ai_safety_gridworlds_amd.engine import BatchedEngine
-  eng = BatchedEngine(spec, row["n"], device=DEV, outputs=row["outs"])
+  eng = BatchedEngine(spec, row["n"], device=DEV, env_id_base=base, outputs=row["outs"])
   if inp["bits"] is not None or inp["bits_seed"]:
     eng.set_episode_bits(inp["bits"], seed=inp["bits_seed"])
   if inp["rand"] is not None or inp["rand_seed"]:
@@ -235,3 +271,159 @@ def finished_returns(step_type, cumulative):
   acc[:-1] = (cumulative[:, 1:] * last[..., None]).sum(axis=(0, 1))
   acc[-1] = last.sum()
   return acc
+
+
+# ---- the launch-path matrix (GPU): shared by tests/test_launch_paths_gpu.py and tests/test_seeded_draws_gpu.py ----------------------
+T, CALLS, SEED = 16, 3, 0x1A7C        # T >= step_graphs_min_T (8): the second call of a buffer is captured
+AFTER = 3                             # setter tests: calls after the setter (the stale graph's direct launch, capture, replay)
+PATHS = ("step_n", "step_n_side", "replay", "rollout")
+
+
+def steps_of(row):
+  """Steps a row's action stream covers: its step_n / replay / rollout calls; groups: CALLS step_n calls, then one rollout;
+  setter tests: CALLS calls, then AFTER more."""
+  return max(row["calls"], CALLS + 1, CALLS + AFTER) * T
+
+
+def base_of(row):
+  return row.get("base", 0)
+
+
+def host_actions(spec, ids, steps, seed):
+  """int8 [len(steps), len(ids)(, A)]: the package's synthetic action stream of the global env ids `ids`, restated on the host."""
+  per = [philox.actions(seed, ids, steps, spec.action_lo, spec.n_actions, agent=a) for a in range(spec.A)]
+  return per[0] if spec.A == 1 else np.stack(per, axis=-1)
+
+
+_CASES = {}
+
+
+def case(row):
+  """Per row (cached by id; `row`: a row, or the id of one of ROWS): spec, inputs, the device action stream of steps_of(row) steps
+  (== the host's statement over the global env ids), the oracle's arrays, and a reference engine's outputs of every step (reset,
+  then one sgw_step per step) with its state after every multiple of T steps.  The reference engine itself is compared with the
+  oracle at every step, and its generator position with the oracle's at every multiple of T (the multi-agent families)."""
+  import torch
+  from ai_safety_gridworlds_amd.specs import make_spec
+  if isinstance(row, str):
+    row = BY_ID[row]
+  row_id = row["id"]
+  if row_id in _CASES:
+    return _CASES[row_id]
+  spec = make_spec(row["name"], **row["kw"])
+  base = base_of(row)
+  inp = inputs(row, spec, row["seed"] if "seed" in row else ROWS.index(row), base=base)
+  ref = make_engine(row, spec, inp, base=base)
+  S = steps_of(row)
+  acts = ref.fill_actions(S, SEED).clone()
+  assert np.array_equal(acts.cpu().numpy(), host_actions(spec, global_ids(row["n"], base), np.arange(S), SEED)), \
+      "%s: sgw_fill_actions differs from philox.actions over the global env ids" % row_id
+  rec = {k: [v.clone()] for k, v in start(ref, row).items()}
+  states = {}
+  for t in range(S):
+    for k, v in ref.step(acts[t]).items():
+      rec[k].append(v.clone())
+    if (t + 1) % T == 0:
+      states[t + 1] = ref.get_state()[:, :row["n"]].clone()
+  torch.cuda.synchronize()
+  got = to_np({k: torch.stack(v) for k, v in rec.items()}, True)
+  want = run_oracle(row, acts.cpu().numpy(), inp)
+  c = dict(row=row, spec=spec, inp=inp, acts=acts, want=want, ref=got, states=states)
+  check(c, {k: v[:, 1:] for k, v in got.items()}, 1, "sgw_step")
+  if row["rng"]:
+    for s, st in states.items():
+      assert not rng_mismatch(row, st.cpu().numpy(), want, s), "%s sgw_step: generator position after %d steps" % (row_id, s)
+  if row["oracle"] == "scalar":
+    st, cum = want["step_type"][..., None], want["cumulative"]
+  else:
+    st, cum = got["step_type"], got["cumulative"].reshape(row["n"], S + 1, -1)
+  # read_returns after the row's own calls and after the groups' CALLS step_n calls
+  c["returns"] = {s: finished_returns(st[:, :s + 1], cum[:, :s + 1]) for s in {row["calls"] * T, CALLS * T}}
+  assert c["returns"][row["calls"] * T][-1] > 0, "no episode ends inside the run: pick kwargs with shorter episodes"
+  ref.close()
+  _CASES[row_id] = c
+  return c
+
+
+def check(c, got, s0, label):
+  """got {field: [E, S, ...]} = the outputs of steps s0 .. s0 + S - 1: equal to the oracle and to the sgw_step engine."""
+  row, spec = c["row"], c["spec"]
+  S = next(iter(got.values())).shape[1]
+  views = split_views(spec, got["views"]) if "views" in got else None
+  bad = oracle_mismatches(row, spec, got, c["want"], s0, views=views)
+  assert not bad, "%s %s steps %d..%d differ from the oracle in %s" % (row["id"], label, s0, s0 + S - 1, bad)
+  if label != "sgw_step":
+    for k in row["outs"]:
+      g, w = got[k], c["ref"][k][:, s0:s0 + S]
+      assert _same(g, w), "%s %s steps %d..%d: %s differs from the sgw_step engine" % (row["id"], label, s0, s0 + S - 1, k)
+
+
+def check_returns(c, r, steps, label):
+  """read_returns after `steps` steps: the count of finished episodes exactly; the sums up to the order of the device's
+  float64 atomic adds."""
+  r, w = r.cpu().numpy(), c["returns"][steps]
+  assert r[-1] == w[-1], "%s %s: %d finished episodes, the oracle has %d" % (c["row"]["id"], label, r[-1], w[-1])
+  assert np.allclose(r[:-1], w[:-1], rtol=1e-12, atol=1e-9), "%s %s: returns %s, the oracle's %s" % (c["row"]["id"], label, r, w)
+
+
+def run_path(row, path):
+  """One of PATHS over the row's calls, from a reset: every call's outputs, the final state and read_returns."""
+  import torch
+  c = case(row)
+  row, spec, acts = c["row"], c["spec"], c["acts"]
+  row_id = row["id"]
+  eng = make_engine(row, spec, c["inp"], base=base_of(row))
+  start(eng, row)
+  buf = torch.empty_like(acts[:T])
+  torch.cuda.synchronize()
+  stream = torch.cuda.Stream(DEV) if path == "step_n_side" else torch.cuda.current_stream(DEV)
+  calls, n_calls = [], row["calls"]
+  with torch.cuda.stream(stream):
+    for k in range(n_calls):
+      if path.startswith("step_n"):               # call 0: direct launches, call 1: capture + replay, call 2: replay
+        buf.copy_(acts[k * T:(k + 1) * T])
+        o = eng.step_n(buf, write_every=True, accumulate=True)
+      elif path == "replay":
+        o = eng.replay(acts[k * T:(k + 1) * T], write_every=True, accumulate=True)
+      else:
+        o = eng.rollout(T, SEED, step0=k * T, write_every=True, accumulate=True)
+      calls.append({f: v.clone() for f, v in o.items()})
+    ret = eng.read_returns()
+    state = eng.get_state()[:, :row["n"]]
+  torch.cuda.synchronize()
+  for k, o in enumerate(calls):
+    check(c, to_np(o, True), 1 + k * T, "%s call %d" % (path, k))
+  assert torch.equal(state, c["states"][n_calls * T]), "%s %s: final state differs from the sgw_step engine" % (row_id, path)
+  check_returns(c, ret, n_calls * T, path)
+  eng.close()
+
+
+def run_group(gid, members):
+  """The member rows as one EngineGroup: CALLS sgw_group_step_n calls (direct, capture, replay), then one sgw_group_rollout."""
+  import torch
+  from ai_safety_gridworlds_amd.engine import EngineGroup
+  cs = [case(m) for m in members]
+  engines = [make_engine(c["row"], c["spec"], c["inp"], base=base_of(c["row"])) for c in cs]
+  for c, e in zip(cs, engines):
+    start(e, c["row"])
+  grp = EngineGroup(engines)
+  bufs = [torch.empty_like(c["acts"][:T]) for c in cs]
+  torch.cuda.synchronize()
+  for k in range(CALLS):                           # direct, capture, replay; the actions refilled in place
+    for b, c in zip(bufs, cs):
+      b.copy_(c["acts"][k * T:(k + 1) * T])
+    outs = grp.step_n(bufs, write_every=True, accumulate=True)
+    torch.cuda.synchronize()
+    for c, o in zip(cs, outs):
+      check(c, to_np(o, True), 1 + k * T, "%s group step_n call %d" % (gid, k))
+  for c, e in zip(cs, engines):
+    check_returns(c, e.read_returns(), CALLS * T, "%s group step_n" % gid)
+    assert torch.equal(e.get_state()[:, :c["row"]["n"]], c["states"][CALLS * T]), "%s %s: state" % (gid, c["row"]["id"])
+  outs = grp.rollout(T, SEED, step0=CALLS * T, write_every=True)
+  torch.cuda.synchronize()
+  for c, o, e in zip(cs, outs, engines):
+    check(c, to_np(o, True), 1 + CALLS * T, "%s group rollout" % gid)
+    assert torch.equal(e.get_state()[:, :c["row"]["n"]], c["states"][(CALLS + 1) * T]), "%s %s: state after the rollout" % (gid, c["row"]["id"])
+  grp.close()
+  for e in engines:
+    e.close()
