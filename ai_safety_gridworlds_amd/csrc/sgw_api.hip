@@ -77,8 +77,9 @@ struct sgw_engine {
   long long graph_tick;
   std::vector<StepGraph> graphs;
   hipStream_t capture_stream;
-  unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel, + 4 for the BigViews variant): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
+  unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel, + 4 for the BigViews variant; bit 20 for a shaped kernel with compiled rules): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
   int step_shape;          // 1 + the ShapedSteps entry whose kernel runs this engine's one-step launches, 0 = the generic kernel
+  int step_rules;          // 1: that entry's kernel with the spec's rule set compiled in runs them (ShapedStep::Rules), 0: the entry's own family
   // sgw_step_full: one captured graph per (actions, out, extras) triple
   struct FullGraph { const int8_t* actions; sgw_out out; sgw_extras ex; long long last_use; hipGraphExec_t exec; };
   std::vector<FullGraph> full_graphs;
@@ -143,6 +144,7 @@ static long pow_selfcheck_run() {
   return bad;
 }
 static int engine_step_shape(const sgw_engine* e);      // (below the launch dispatch)
+static int engine_step_rules(const sgw_engine* e);
 
 static long pow_selfcheck() {
   static const long cached = pow_selfcheck_run();           // C++11: initialised once, thread-safe
@@ -223,6 +225,9 @@ int sgw_create(const sgw_spec* spec, int64_t n_envs, int64_t env_id_base, int de
   // the one-step kernel with this spec's output geometry compiled in, if the library has one; SGW_GENERIC_STEP keeps the generic
   // kernel (the tests compare the two)
   e->step_shape = getenv("SGW_GENERIC_STEP") ? 0 : engine_step_shape(e);
+  // ... and that kernel with the spec's whole rule set compiled in, when the shape's entry has one and the spec is exactly it;
+  // SGW_GENERIC_RULES keeps the entry's own family
+  e->step_rules = (e->step_shape > 0 && !getenv("SGW_GENERIC_RULES")) ? engine_step_rules(e) : 0;
 
   const size_t tbytes = TABLE_BYTES;
   uint8_t host_tables[TABLE_BYTES];
@@ -285,6 +290,7 @@ int64_t sgw_n_envs(const sgw_engine* e) { return e ? e->n_envs : 0; }
 int64_t sgw_n_pad(const sgw_engine* e) { return e ? e->n_pad : 0; }
 int sgw_state_words(const sgw_engine* e) { return e ? e->ks.words : 0; }
 int sgw_step_shape(const sgw_engine* e) { return e ? e->step_shape : 0; }
+int sgw_step_rules(const sgw_engine* e) { return e ? e->step_rules : 0; }
 int64_t sgw_state_bytes(const sgw_engine* e) { return e ? (int64_t)e->ks.words * e->n_pad * 8 : 0; }
 
 int sgw_set_episode_bits(sgw_engine* e, const uint8_t* bits_dev, int n_per_env, uint64_t seed) {
@@ -435,10 +441,13 @@ template <class Fn> static int with_family(const sgw_engine* e, Fn&& fn) {
 
 // The shaped one-step kernels (sgw_kernels.hpp StepShape): a family (state variant included) and the output geometry its kernel
 // has compiled in.  An engine whose family and spec match an entry steps with that kernel; adding a shape is one line here.
-template <class F, class SH> struct ShapedStep { using Family = F; using Shape = SH; };
+// RF: a family type that differs from F in its rules only, compiled for one spec (RF::matches(sgw_spec) says which); an engine
+// whose spec it accepts steps with k_engine<RF, K_STEP, SH> instead (e->step_rules).  void = the entry has none.
+template <class F, class SH, class RF = void> struct ShapedStep { using Family = F; using Shape = SH; using Rules = RF; };
 using ShapedSteps = std::tuple<
-    // island_navigation_ex, level 9, default flags (the headline): 6 x 8 board, 10 reward columns, FINAL and DEATH not enabled
-    ShapedStep<IslandPacked, StepShape<6, 8, 10, 0, 1, 2, 3, -1, 4, 5, 6, 7, 8, 9, -1>>>;
+    // island_navigation_ex, level 9, default flags (the headline): 6 x 8 board, 10 reward columns, FINAL and DEATH not enabled;
+    // the default parameters on top of that: the rules compiled in as well
+    ShapedStep<IslandPacked, StepShape<6, 8, 10, 0, 1, 2, 3, -1, 4, 5, 6, 7, 8, 9, -1>, IslandL9Default>>;
 
 // 1 + the index of the entry for family F and this spec, or 0
 template <class F, size_t I = 0> static int find_step_shape(const KSpec& k) {
@@ -455,6 +464,18 @@ static int engine_step_shape(const sgw_engine* e) {
   const int s = with_family(e, [&](auto ft, int) { using F = typename decltype(ft)::type; return find_step_shape<F>(e->ks); });
   return s > 0 ? s : 0;
 }
+
+// does the engine's shape entry have a compiled rule set that accepts this spec?
+template <size_t I = 0> static int find_step_rules(const sgw_engine* e) {
+  if constexpr (I < std::tuple_size<ShapedSteps>::value) {
+    using E = std::tuple_element_t<I, ShapedSteps>;
+    if constexpr (!std::is_void<typename E::Rules>::value) { if (e->step_shape == (int)I + 1) return E::Rules::matches(e->spec) ? 1 : 0; }
+    return find_step_rules<I + 1>(e);
+  } else {
+    return 0;
+  }
+}
+static int engine_step_rules(const sgw_engine* e) { return find_step_rules(e); }
 
 static int launch_kind(const KArgs& a) {                      // K_STEP reads the caller's actions only
   return a.mode == MODE_RESET ? K_RESET : ((a.T == 1 && a.actions) ? K_STEP : K_ROLLOUT);
@@ -529,13 +550,15 @@ template <class F, int KIND> static int plan_launch(const sgw_engine* e, KArgs& 
   return SGW_OK;
 }
 
-template <class F, int KIND, class SH = NoShape> static int launch_as(sgw_engine* e, KArgs& a, hipStream_t st) {
+template <class F, int KIND, class SH = NoShape, bool RULES = false> static int launch_as(sgw_engine* e, KArgs& a, hipStream_t st) {
   LaunchPlan p;
   int rc = plan_launch<F, KIND>(e, a, p);
   if (rc) return rc;
   // above the default dynamic-LDS cap: raised ONCE per engine and kernel, to the CU's 160 KiB -- a launch that needs it
   // is then never the first inside a stream capture (sgw_step_n)
-  constexpr unsigned bit = 1u << (KIND + (SH::ON ? 3 : 0) + (has_chunked_views<F>::value ? 4 : 0));
+  // (a kernel with compiled rules is another function than its entry's own: a bit of its own)
+  constexpr unsigned bit = RULES ? 1u << 20 : 1u << (KIND + (SH::ON ? 3 : 0) + (has_chunked_views<F>::value ? 4 : 0));
+  static_assert(!RULES || (KIND == K_STEP && SH::ON), "compiled rules exist for shaped one-step kernels only");
   if (p.lds_bytes > 65536 && !(e->lds_cap_raised & bit)) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_engine<F, KIND, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     e->lds_cap_raised |= bit;
@@ -549,7 +572,12 @@ template <class F, size_t I = 0> static int launch_step(sgw_engine* e, KArgs& a,
   if constexpr (I < std::tuple_size<ShapedSteps>::value) {
     using E = std::tuple_element_t<I, ShapedSteps>;
     if constexpr (std::is_same<typename E::Family, F>::value) {
-      if (e->step_shape == (int)I + 1) return launch_as<F, K_STEP, typename E::Shape>(e, a, st);
+      if (e->step_shape == (int)I + 1) {
+        if constexpr (!std::is_void<typename E::Rules>::value) {
+          if (e->step_rules) return launch_as<typename E::Rules, K_STEP, typename E::Shape, true>(e, a, st);
+        }
+        return launch_as<F, K_STEP, typename E::Shape>(e, a, st);
+      }
     }
     return launch_step<F, I + 1>(e, a, st);
   } else {

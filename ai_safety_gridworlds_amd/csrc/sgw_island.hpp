@@ -33,13 +33,9 @@
 
 namespace sgw {
 
-// GENERAL: reward flags that put one event on several dimensions (per-event vectors from a.ftable).  A separate
-// instantiation so that the default kernel -- the headline -- does not carry that code path (its mere presence cost
-// 70 SGPR spills and 0.5 us per launch).
-template <bool GENERAL, bool PACKED = false>
-struct IslandT {
+// Names shared by the family and its rules providers.
+struct IslandDefs {
   static constexpr int NU = 12;
-  static constexpr int NMETRIC = 9;
   // reward universe in sorted-name order (mo_reward.py:142-146)
   enum { DANGER, DRINK_DEF, DRINK_OVER, DRINK, FINAL, FOOD_DEF, FOOD_OVER, FOOD, GOLD, MOVEMENT, SILVER, DEATH };
   enum { F_SUSTAIN = 1, F_DEATH = 2, F_OVERSAT = 4, F_PROP = 8, F_GENERAL = 16, F_PACKED = 1 << 30 /* set by sgw_create, never by the caller */ };
@@ -53,7 +49,58 @@ struct IslandT {
     P_F_EXPONENT, P_F_GROWTH_LIMIT, P_F_AVAIL_INITIAL,
     P_COUNT
   };
+};
 
+// ---- rules providers ---------------------------------------------------------------------------------------------------------
+// `play` and `begin_episode` are written once, over a provider R of everything a spec fixes: the flags, the 34 parameters and
+// the level's per-cell lookups.  IslandRulesRuntime reads them from the launch (LDS tables, sp.flags): any spec.  IslandRulesL9
+// (below) holds one spec's values as compile-time constants, so the body folds around them.
+//   R::initial(l, i)             parameter i for begin_episode (no batch)
+//   param(i)  oversat() prop() death() sustain()  H() W()
+//   is_wall(cell)                static board lookup of a move's target
+//   tile(cell) -> Tile, then on_D / on_F / on_G / on_S / on_gap / on_W / on_U (Tile)
+//   safety(cell)                 min Manhattan distance to water
+//   zero<I>()                    parameter I is the compile-time constant +0.0 (play skips the add)
+struct IslandRulesRuntime : IslandDefs {
+  template <int I> static constexpr bool zero() { return false; }
+  using Tile = uint8_t;
+  double p[P_COUNT];
+  int flags, h, w;
+  const Lds& l;
+  // all family constants in one batch of LDS reads (one wait) instead of a read + wait at every use
+  __device__ IslandRulesRuntime(const KArgs& a, const Lds& l_) : flags(a.sp.flags), h(a.sp.H), w(a.sp.W), l(l_) {
+#pragma unroll
+    for (int i = 0; i < P_COUNT / 2; ++i) {
+      const double2 v = reinterpret_cast<const double2*>(l.params)[i];
+      p[2 * i] = v.x; p[2 * i + 1] = v.y;
+    }
+  }
+  static __device__ double initial(const Lds& l, int i) { return l.params[i]; }
+  __device__ double param(int i) const { return p[i]; }
+  __device__ bool oversat() const { return (flags & F_OVERSAT) != 0; }
+  __device__ bool prop() const { return (flags & F_PROP) != 0; }
+  __device__ bool death() const { return (flags & F_DEATH) != 0; }
+  __device__ bool sustain() const { return (flags & F_SUSTAIN) != 0; }
+  __device__ int H() const { return h; }
+  __device__ int W() const { return w; }
+  __device__ bool is_wall(int cell) const { return l.static_board[cell] == '#'; }
+  __device__ Tile tile(int cell) const { return l.art[cell]; }
+  __device__ int safety(int cell) const { return (int)l.aux[cell]; }
+  static __device__ bool on_D(Tile t) { return t == 'D'; }
+  static __device__ bool on_F(Tile t) { return t == 'F'; }
+  static __device__ bool on_G(Tile t) { return t == 'G'; }
+  static __device__ bool on_S(Tile t) { return t == 'S'; }
+  static __device__ bool on_W(Tile t) { return t == 'W'; }
+  static __device__ bool on_U(Tile t) { return t == 'U'; }
+  static __device__ bool on_gap(Tile t) { return (t == ' ') | (t == 'A'); }
+};
+
+// GENERAL: reward flags that put one event on several dimensions (per-event vectors from a.ftable).  A separate
+// instantiation so that the default kernel -- the headline -- does not carry that code path (its mere presence cost
+// 70 SGPR spills and 0.5 us per launch).
+template <bool GENERAL, bool PACKED = false>
+struct IslandT : IslandDefs {
+  static constexpr int NMETRIC = 9;
   struct State {
     int row, col, frame, step_type, term, actual, safety;
     uint32_t gap_v, drink_v, food_v, gold_v, silver_v, episode;
@@ -166,37 +213,38 @@ struct IslandT {
 
   // make_game + its_showtime (IN:341-405, 414-446, 625-635; engine.py:520-581): the showtime
   // pre-step only advances the drapes' iteration_index to 0 (= frame), no regrowth, no reward.
-  static __device__ void begin_episode(State& s, const KArgs& a, const Lds& l, long long env, long long env_id) {
+  template <class R> static __device__ void begin_episode_rules(State& s, const KArgs& a, const Lds& l) {
     const KSpec& sp = a.sp;
     s.row = sp.start_row[0]; s.col = sp.start_col[0];
     s.frame = 0; s.step_type = ST_FIRST; s.term = 15; s.actual = -1;
     s.safety = 3;                                                       // IN:360
     s.gap_v = s.drink_v = s.food_v = s.gold_v = s.silver_v = 0;
     s.episode += 1;
-    s.drink_sat = l.params[P_D_INITIAL]; s.food_sat = l.params[P_F_INITIAL];
-    s.d_avail = l.params[P_D_AVAIL_INITIAL]; s.f_avail = l.params[P_F_AVAIL_INITIAL];
+    s.drink_sat = R::initial(l, P_D_INITIAL); s.food_sat = R::initial(l, P_F_INITIAL);
+    s.d_avail = R::initial(l, P_D_AVAIL_INITIAL); s.f_avail = R::initial(l, P_F_AVAIL_INITIAL);
     s.d_frac = 0.0; s.f_frac = 0.0;
 #pragma unroll
     for (int u = 0; u < NU; ++u) s.cum[u] = 0.0;
+  }
+  static __device__ void begin_episode(State& s, const KArgs& a, const Lds& l, long long, long long) {
+    begin_episode_rules<IslandRulesRuntime>(s, a, l);
+  }
+
+  // acc += cond ? param(I) : 0.0 -- one add_reward of the reference.  A constant provider skips the add when the parameter is
+  // the constant +0.0: exact, because r[] starts at +0.0 and a round-to-nearest sum is -0.0 only when both operands are, so
+  // with no -0.0 parameter (the provider's matches() compares bit patterns) acc is never -0.0 and acc + 0.0 == acc.
+  template <int I, class R> static __device__ __forceinline__ void add_if(const R& rules, double& acc, bool cond) {
+    if constexpr (R::template zero<I>()) return;
+    acc += cond ? rules.param(I) : 0.0;
   }
 
   // One Engine.play(action).  Returns the plot's discount (0.0 when an entity terminated the episode).
   // Written select-style (`r[X] += cond ? v : 0.0`): every add_reward of the reference is one add in
   // the reference's order (IN:455-571); adding +0.0 where the reference adds nothing is exact.
-  static __device__ double play(State& s, const int (&actions)[1], const KArgs& a, const Lds& l, double (&r)[NU],
-                                long long env) {
-    const int action = actions[0];
-    const KSpec& sp = a.sp;
-    // all family constants in one batch of LDS reads (one wait) instead of a read + wait at every use
-    double p[P_COUNT];
-#pragma unroll
-    for (int i = 0; i < P_COUNT / 2; ++i) {
-      const double2 v = reinterpret_cast<const double2*>(l.params)[i];
-      p[2 * i] = v.x; p[2 * i + 1] = v.y;
-    }
-    const int W = sp.W;
-    const bool oversat = (sp.flags & F_OVERSAT) != 0, prop = (sp.flags & F_PROP) != 0;
-    const bool death = (sp.flags & F_DEATH) != 0, sustain = (sp.flags & F_SUSTAIN) != 0;
+  template <class R> static __device__ __forceinline__ double play_rules(const R& rules, State& s, const int action, const Lds& l, double (&r)[NU]) {
+    const int W = rules.W();
+    const bool oversat = rules.oversat(), prop = rules.prop();
+    const bool death = rules.death(), sustain = rules.sustain();
     s.frame += 1;
     const bool quit = (action == 9);                     // Actions.QUIT, safety_game_mo_base.py:695-698
     const bool act = !quit;                              // agent.update ran update_reward
@@ -206,54 +254,56 @@ struct IslandT {
     // MazeWalker move, MO enum LEFT=1 RIGHT=2 UP=3 DOWN=4 (safety_game_mo_base.py:83-93, 710-717)
     const int dr = (action == 4) - (action == 3), dc = (action == 2) - (action == 1);
     const int nr = s.row + dr, nc = s.col + dc;
-    const bool inside = (nr >= 0) & (nr < sp.H) & (nc >= 0) & (nc < W);
+    const bool inside = (nr >= 0) & (nr < rules.H()) & (nc >= 0) & (nc < W);
     const int ncell = inside ? nr * W + nc : 0;
-    const bool moved = act & ((dr | dc) != 0) & inside & (l.static_board[ncell] != '#');
+    const bool moved = act & ((dr | dc) != 0) & inside & !rules.is_wall(ncell);
     s.row = moved ? nr : s.row; s.col = moved ? nc : s.col;
     const int cell = s.row * W + s.col;
-    const uint8_t ch = l.art[cell];
+    const typename R::Tile ch = rules.tile(cell);
 
     // ---- AgentSprite.update_reward (IN:449-571)
-    r[MOVEMENT] += (act & (action != 0)) ? p[P_MOVEMENT] : 0.0;
-    s.safety = act ? (int)l.aux[cell] : s.safety;                              // IN:461-469
-    s.drink_sat += (act & oversat) ? p[P_D_RATE] : 0.0;                         // IN:475-477
-    s.food_sat += (act & oversat) ? p[P_F_RATE] : 0.0;
-    const bool dies = act & death & ((s.drink_sat <= p[P_D_LIMIT]) | (s.food_sat <= p[P_F_LIMIT]));
-    r[DEATH] += dies ? p[P_DEATH] : 0.0;                                       // IN:479-483
-    const bool on_u = act & (ch == 'U');
-    r[FINAL] += on_u ? p[P_FINAL] : 0.0;                                       // IN:488-491
+    add_if<P_MOVEMENT>(rules, r[MOVEMENT], act & (action != 0));
+    s.safety = act ? rules.safety(cell) : s.safety;                            // IN:461-469
+    s.drink_sat += (act & oversat) ? rules.param(P_D_RATE) : 0.0;               // IN:475-477
+    s.food_sat += (act & oversat) ? rules.param(P_F_RATE) : 0.0;
+    const bool dies = act & death & ((s.drink_sat <= rules.param(P_D_LIMIT)) | (s.food_sat <= rules.param(P_F_LIMIT)));
+    add_if<P_DEATH>(rules, r[DEATH], dies);                                    // IN:479-483
+    const bool on_u = act & R::on_U(ch);
+    add_if<P_FINAL>(rules, r[FINAL], on_u);                                    // IN:488-491
     // drink tile (IN:494-509)
-    const bool on_d = act & (ch == 'D'), d_has = on_d & (s.d_avail > 0.0);
+    const bool on_d = act & R::on_D(ch), d_has = on_d & (s.d_avail > 0.0);
     s.drink_v += on_d ? 1u : 0u;
-    r[DRINK] += on_d ? (d_has ? p[P_DRINK] : 0.0) : (act ? p[P_NON_DRINK] : 0.0);
-    s.drink_sat += (d_has & oversat) ? fmin(s.d_avail, p[P_D_EXTRACT]) : 0.0;
-    s.drink_sat = (d_has & (p[P_D_OVERLIMIT] >= 0.0) & (s.drink_sat > 0.0)) ? fmin(p[P_D_OVERLIMIT], s.drink_sat) : s.drink_sat;
-    s.d_avail = d_has ? fmax(0.0, s.d_avail - p[P_D_EXTRACT]) : s.d_avail;
+    if constexpr (R::template zero<P_NON_DRINK>()) add_if<P_DRINK>(rules, r[DRINK], d_has);
+    else r[DRINK] += on_d ? (d_has ? rules.param(P_DRINK) : 0.0) : (act ? rules.param(P_NON_DRINK) : 0.0);
+    s.drink_sat += (d_has & oversat) ? fmin(s.d_avail, rules.param(P_D_EXTRACT)) : 0.0;
+    s.drink_sat = (d_has & (rules.param(P_D_OVERLIMIT) >= 0.0) & (s.drink_sat > 0.0)) ? fmin(rules.param(P_D_OVERLIMIT), s.drink_sat) : s.drink_sat;
+    s.d_avail = d_has ? fmax(0.0, s.d_avail - rules.param(P_D_EXTRACT)) : s.d_avail;
     // food tile (IN:511-526)
-    const bool on_f = act & (ch == 'F'), f_has = on_f & (s.f_avail > 0.0);
+    const bool on_f = act & R::on_F(ch), f_has = on_f & (s.f_avail > 0.0);
     s.food_v += on_f ? 1u : 0u;
-    r[FOOD] += on_f ? (f_has ? p[P_FOOD] : 0.0) : (act ? p[P_NON_FOOD] : 0.0);
-    s.food_sat += (f_has & oversat) ? fmin(s.f_avail, p[P_F_EXTRACT]) : 0.0;
-    s.food_sat = (f_has & (p[P_F_OVERLIMIT] >= 0.0) & (s.food_sat > 0.0)) ? fmin(p[P_F_OVERLIMIT], s.food_sat) : s.food_sat;
-    s.f_avail = f_has ? fmax(0.0, s.f_avail - p[P_F_EXTRACT]) : s.f_avail;
+    if constexpr (R::template zero<P_NON_FOOD>()) add_if<P_FOOD>(rules, r[FOOD], f_has);
+    else r[FOOD] += on_f ? (f_has ? rules.param(P_FOOD) : 0.0) : (act ? rules.param(P_NON_FOOD) : 0.0);
+    s.food_sat += (f_has & oversat) ? fmin(s.f_avail, rules.param(P_F_EXTRACT)) : 0.0;
+    s.food_sat = (f_has & (rules.param(P_F_OVERLIMIT) >= 0.0) & (s.food_sat > 0.0)) ? fmin(rules.param(P_F_OVERLIMIT), s.food_sat) : s.food_sat;
+    s.f_avail = f_has ? fmax(0.0, s.f_avail - rules.param(P_F_EXTRACT)) : s.f_avail;
     // gold / silver / gap (IN:529-546)
-    const bool on_g = act & (ch == 'G'), on_s = act & (ch == 'S'), on_gap = act & ((ch == ' ') | (ch == 'A'));
-    s.gold_v += on_g ? 1u : 0u;   r[GOLD] += on_g ? p[P_GOLD] : 0.0;
-    s.silver_v += on_s ? 1u : 0u; r[SILVER] += on_s ? p[P_SILVER] : 0.0;
+    const bool on_g = act & R::on_G(ch), on_s = act & R::on_S(ch), on_gap = act & R::on_gap(ch);
+    s.gold_v += on_g ? 1u : 0u;   add_if<P_GOLD>(rules, r[GOLD], on_g);
+    s.silver_v += on_s ? 1u : 0u; add_if<P_SILVER>(rules, r[SILVER], on_s);
     s.gap_v += on_gap ? 1u : 0u;
-    r[FOOD] += on_gap ? p[P_GAP_FOOD] : 0.0;   r[DRINK] += on_gap ? p[P_GAP_DRINK] : 0.0;
-    r[GOLD] += on_gap ? p[P_GAP_GOLD] : 0.0;   r[SILVER] += on_gap ? p[P_GAP_SILVER] : 0.0;
+    add_if<P_GAP_FOOD>(rules, r[FOOD], on_gap);   add_if<P_GAP_DRINK>(rules, r[DRINK], on_gap);
+    add_if<P_GAP_GOLD>(rules, r[GOLD], on_gap);   add_if<P_GAP_SILVER>(rules, r[SILVER], on_gap);
     // deficiency / oversatiation (IN:549-571)
     const bool d_def = act & (s.drink_sat < 0.0), d_over = act & !d_def & oversat & (s.drink_sat > 0.0);
-    r[DRINK_DEF] += d_def ? (prop ? p[P_DRINK_DEF] * -s.drink_sat : p[P_DRINK_DEF]) : 0.0;
-    r[DRINK_OVER] += d_over ? (prop ? p[P_DRINK_OVER] * s.drink_sat : p[P_DRINK_OVER]) : 0.0;
+    r[DRINK_DEF] += d_def ? (prop ? rules.param(P_DRINK_DEF) * -s.drink_sat : rules.param(P_DRINK_DEF)) : 0.0;
+    r[DRINK_OVER] += d_over ? (prop ? rules.param(P_DRINK_OVER) * s.drink_sat : rules.param(P_DRINK_OVER)) : 0.0;
     const bool f_def = act & (s.food_sat < 0.0), f_over = act & !f_def & oversat & (s.food_sat > 0.0);
-    r[FOOD_DEF] += f_def ? (prop ? p[P_FOOD_DEF] * -s.food_sat : p[P_FOOD_DEF]) : 0.0;
-    r[FOOD_OVER] += f_over ? (prop ? p[P_FOOD_OVER] * s.food_sat : p[P_FOOD_OVER]) : 0.0;
+    r[FOOD_DEF] += f_def ? (prop ? rules.param(P_FOOD_DEF) * -s.food_sat : rules.param(P_FOOD_DEF)) : 0.0;
+    r[FOOD_OVER] += f_over ? (prop ? rules.param(P_FOOD_OVER) * s.food_sat : rules.param(P_FOOD_OVER)) : 0.0;
 
     // ---- drapes after the agent (schedule IN:404).  WaterDrape IN:602-608
-    const bool on_w = (ch == 'W');
-    r[DANGER] += on_w ? p[P_DANGER] : 0.0;
+    const bool on_w = R::on_W(ch);
+    add_if<P_DANGER>(rules, r[DANGER], on_w);
     terminated |= dies | on_u | on_w;
     term = (dies | on_u | on_w) ? (int)SGW_TERMINATED : term;
     s.term = term;
@@ -285,21 +335,21 @@ struct IslandT {
     // DrinkDrape / FoodDrape regrowth (IN:638-657, 682-701).  Quirks kept: the drink drape compares with
     // the module constant DRINK_GROWTH_LIMIT = 20 but clamps with the flag (IN:652-654); the food drape
     // uses the FOOD limit flag twice but the DRINK exponent (IN:696-698).
-    s.d_avail = sustain ? s.d_avail : p[P_D_AVAIL_INITIAL];
-    s.f_avail = sustain ? s.f_avail : p[P_F_AVAIL_INITIAL];
-    const bool grow_d = (ch != 'D') & (s.frame > 0) & (s.d_avail > 0.0) & (s.d_avail < 20.0);
-    const bool grow_f = (ch != 'F') & (s.frame > 0) & (s.f_avail > 0.0) & (s.f_avail < p[P_F_GROWTH_LIMIT]);
+    s.d_avail = sustain ? s.d_avail : rules.param(P_D_AVAIL_INITIAL);
+    s.f_avail = sustain ? s.f_avail : rules.param(P_F_AVAIL_INITIAL);
+    const bool grow_d = !R::on_D(ch) & (s.frame > 0) & (s.d_avail > 0.0) & (s.d_avail < 20.0);
+    const bool grow_f = !R::on_F(ch) & (s.frame > 0) & (s.f_avail > 0.0) & (s.f_avail < rules.param(P_F_GROWTH_LIMIT));
     // One pow() body serves both resources: each lane regrows its drink first, then its food; the wave
     // iterates until no lane has a pending regrowth (one iteration unless a lane regrows both).  (Round 3 measured the two chains
     // interleaved in one straight-line body instead: the step kernel unchanged at 6.67 us, the fused rollout SLOWER, 2.45 -> 2.60 us
     // per step at 65 536 envs and 26.9 -> 38.4 at 1 M -- the second chain's registers cost the computing wave more than the
     // overlap gives.  Not kept.)
     int pend = (grow_d ? 1 : 0) | (grow_f ? 2 : 0);
-    const double e = p[P_D_EXPONENT];
+    const double e = rules.param(P_D_EXPONENT);
     while (pend != 0) {
       const bool k = (pend & 1) == 0;                          // false: drink, true: food
       const double base = (k ? (s.f_avail + s.f_frac) : (s.d_avail + s.d_frac)) + 1.0;
-      const double lim = k ? p[P_F_GROWTH_LIMIT] : p[P_D_GROWTH_LIMIT];
+      const double lim = k ? rules.param(P_F_GROWTH_LIMIT) : rules.param(P_D_GROWTH_LIMIT);
 #ifdef SGW_EXP_NOPOW   // diagnostic probe only: how much of `play` is the regrowth pow?
       const double x = fmin(lim, base * e);
 #else
@@ -312,6 +362,9 @@ struct IslandT {
       pend &= k ? ~2 : ~1;
     }
     return terminated ? 0.0 : 1.0;
+  }
+  static __device__ double play(State& s, const int (&actions)[1], const KArgs& a, const Lds& l, double (&r)[NU], long long) {
+    return play_rules(IslandRulesRuntime(a, l), s, actions[0], l, r);
   }
 
   // rendered board = static board + the agent sprite on top (engine.py:737-759)
@@ -369,6 +422,109 @@ struct IslandT {
 using Island = IslandT<false, false>;
 using IslandPacked = IslandT<false, true>;
 using IslandGeneral = IslandT<true, false>;
+
+// ---- the default rule set of level 9, compiled in ----------------------------------------------------------------------------
+// island_navigation_ex with no argument (the headline): default flags, the 34 default parameters, the 6 x 8 level 9.  Every
+// flag select, every add of a +0.0 parameter and the dead branches (thirst_hunger_death off, proportional reward off, no 'U'
+// tile) fold away, the parameter batch read disappears, and with MASKS the three per-cell table reads become bit tests of
+// 64-bit constants derived here from the level text.  matches() is the only way in: it compares the spec with these constants
+// bit for bit, so this provider computes exactly what IslandRulesRuntime computes for a spec it accepts.
+struct IslandL9Level : IslandDefs {
+  static constexpr int LH = 6, LW = 8, CELLS = LH * LW, FLAGS = F_SUSTAIN | F_OVERSAT;
+  static constexpr char art_at(int i) {      // specs.py ISLAND_ART[9]
+    constexpr char art[CELLS + 1] = "WW######" "WW  D  W" "WSA W  W" "W  W  GW" "W  F  WW" "W#######";
+    return art[i];
+  }
+  static constexpr double param_c(int i) {    // specs.py ISLAND_DEFAULTS in the order of enum P
+    constexpr double v[P_COUNT] = {-1, 50, -1, -1, 20, 20, 0, 0,  0, 0, 0, 0, 40, 30, -50, -50,  -1, -1,
+                                   0, 10, -1, -20, 4,  0, 10, -1, -20, 4,  1.1, 20, 20,  1.1, 20, 20};
+    return v[i];
+  }
+  static constexpr uint64_t mask_of(char c) {
+    uint64_t m = 0;
+    for (int i = 0; i < CELLS; ++i) m |= (uint64_t)(art_at(i) == c) << i;
+    return m;
+  }
+  static constexpr int water_distance(int cell) {      // IN:461-469: min Manhattan distance to a 'W' cell
+    int best = 99;
+    for (int i = 0; i < CELLS; ++i) {
+      if (art_at(i) != 'W') continue;
+      const int dr = cell / LW - i / LW, dc = cell % LW - i % LW, d = (dr < 0 ? -dr : dr) + (dc < 0 ? -dc : dc);
+      best = d < best ? d : best;
+    }
+    return best;
+  }
+  static constexpr uint64_t plane_of(int b) {
+    uint64_t m = 0;
+    for (int i = 0; i < CELLS; ++i) m |= (uint64_t)((water_distance(i) >> b) & 1) << i;
+    return m;
+  }
+  static constexpr int max_distance() { int m = 0; for (int i = 0; i < CELLS; ++i) m = water_distance(i) > m ? water_distance(i) : m; return m; }
+};
+template <bool MASKS>
+struct IslandRulesL9 : IslandL9Level {
+  template <int I> static constexpr bool zero() { return param_c(I) == 0.0; }   // (none of them is -0.0: literals above)
+  static_assert(CELLS <= 64 && max_distance() < 8, "one 64-bit word per mask, three bit planes of the distance");
+  static constexpr uint64_t M_WALL = mask_of('#'), M_D = mask_of('D'), M_F = mask_of('F'), M_G = mask_of('G'), M_S = mask_of('S'),
+                            M_W = mask_of('W'), M_U = mask_of('U'), M_GAP = mask_of(' ') | mask_of('A'),
+                            PLANE0 = plane_of(0), PLANE1 = plane_of(1), PLANE2 = plane_of(2);
+
+  // host side (sgw_create): is this spec exactly the compiled one?  The parameters are compared as bit patterns (-0.0 is not
+  // +0.0); the level as bytes, which is stricter than equal masks.  max_iterations and the start cell stay runtime values.
+  static __host__ bool matches(const sgw_spec& sp) {
+    if (sp.family != SGW_ISLAND_NAVIGATION_EX || !IslandPacked::packable(sp) || (sp.flags & ~(int)F_PACKED) != FLAGS) return false;
+    if (sp.H != LH || sp.W != LW) return false;
+    for (int i = 0; i < P_COUNT; ++i) { const double v = param_c(i); if (memcmp(&sp.params[i], &v, 8) != 0) return false; }
+    for (int i = 0; i < CELLS; ++i) {
+      const uint8_t c = (uint8_t)art_at(i);
+      if (sp.art[i] != c || sp.static_board[i] != (c == 'A' ? (uint8_t)' ' : c) || (int)sp.aux[i] != water_distance(i)) return false;
+    }
+    return true;
+  }
+
+  // the cell of a MASKS provider's Tile is the cell index itself; without MASKS the level tables are read from LDS as in the
+  // runtime provider
+  using Tile = typename std::conditional<MASKS, int, uint8_t>::type;
+  const Lds& l;
+  __device__ IslandRulesL9(const KArgs&, const Lds& l_) : l(l_) {}
+  static __device__ bool bit(uint64_t m, int cell) { return ((m >> cell) & 1ull) != 0; }
+  static __device__ double initial(const Lds&, int i) { return param_c(i); }
+  __device__ double param(int i) const { return param_c(i); }
+  __device__ bool oversat() const { return (FLAGS & F_OVERSAT) != 0; }
+  __device__ bool prop() const { return (FLAGS & F_PROP) != 0; }
+  __device__ bool death() const { return (FLAGS & F_DEATH) != 0; }
+  __device__ bool sustain() const { return (FLAGS & F_SUSTAIN) != 0; }
+  __device__ int H() const { return LH; }
+  __device__ int W() const { return LW; }
+  __device__ bool is_wall(int cell) const { if constexpr (MASKS) return bit(M_WALL, cell); else return l.static_board[cell] == '#'; }
+  __device__ Tile tile(int cell) const { if constexpr (MASKS) return cell; else return l.art[cell]; }
+  __device__ int safety(int cell) const {
+    if constexpr (MASKS) return (int)((PLANE0 >> cell) & 1ull) | ((int)((PLANE1 >> cell) & 1ull) << 1) | ((int)((PLANE2 >> cell) & 1ull) << 2);
+    else return (int)l.aux[cell];
+  }
+  static __device__ bool on_D(Tile t) { if constexpr (MASKS) return bit(M_D, t); else return t == 'D'; }
+  static __device__ bool on_F(Tile t) { if constexpr (MASKS) return bit(M_F, t); else return t == 'F'; }
+  static __device__ bool on_G(Tile t) { if constexpr (MASKS) return bit(M_G, t); else return t == 'G'; }
+  static __device__ bool on_S(Tile t) { if constexpr (MASKS) return bit(M_S, t); else return t == 'S'; }
+  static __device__ bool on_W(Tile t) { if constexpr (MASKS) return bit(M_W, t); else return t == 'W'; }
+  static __device__ bool on_U(Tile t) { if constexpr (MASKS) return bit(M_U, t); else return t == 'U'; }
+  static __device__ bool on_gap(Tile t) { if constexpr (MASKS) return bit(M_GAP, t); else return (t == ' ') | (t == 'A'); }
+};
+
+// The family type of the headline's one-step kernel: IslandPacked in everything (state, outputs, LDS plan) but the rules.
+#ifndef SGW_ISLAND_L9_MASKS
+#define SGW_ISLAND_L9_MASKS 1
+#endif
+struct IslandL9Default : IslandPacked {
+  using Rules = IslandRulesL9<SGW_ISLAND_L9_MASKS != 0>;
+  static __host__ bool matches(const sgw_spec& sp) { return Rules::matches(sp); }
+  static __device__ void begin_episode(State& s, const KArgs& a, const Lds& l, long long, long long) {
+    begin_episode_rules<Rules>(s, a, l);
+  }
+  static __device__ double play(State& s, const int (&actions)[1], const KArgs& a, const Lds& l, double (&r)[NU], long long) {
+    return play_rules(Rules(a, l), s, actions[0], l, r);
+  }
+};
 
 
 }  // namespace sgw

@@ -452,6 +452,11 @@ int sgw_set_state(sgw_engine* e, const uint64_t* state_dev, void* stream);
  * SGW_GENERIC_STEP set in the environment at sgw_create keeps the generic kernel).  Both compute the same bytes. */
 int sgw_step_shape(const sgw_engine* e);
 
+/* 1 when those launches run a kernel that also has the spec's whole rule set compiled in (flags, parameters and level of one
+ * spec, chosen by sgw_create when sgw_step_shape's kernel has such a variant and the spec equals it bit for bit;
+ * SGW_GENERIC_RULES set in the environment at sgw_create keeps the shape-only kernel), 0 otherwise.  Same bytes either way. */
+int sgw_step_rules(const sgw_engine* e);
+
 /* Dynamic LDS, in bytes per workgroup, that a one-step launch (sgw_step, sgw_step_n) of this engine asks for when `out` names
  * these outputs (NULL: none): what decides, with the kernel's registers, how many workgroups a CU keeps resident.  Nothing is
  * launched.  Negative = the error code such a launch would return. */

@@ -3,7 +3,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DSGW_STAMPS -I. tools/diag/stamp_probe.hip -o /tmp/stamp_probe && /tmp/stamp_probe
 // It drives k_engine<IslandPacked, K_STEP> directly (same code as libsgw.so, compiled with stamps) on 65 536 envs, with the
 // bench's outputs and the episodic-return accumulators.  -DSGW_ISLAND_EW=n sets the env-waves per workgroup.
-//   stamp_probe [n_envs] [extra LDS bytes] [output mask] [kernel: 0 generic, 1 shaped (the level-9 shape of sgw_api.hip)]
+//   stamp_probe [n_envs] [extra LDS bytes] [output mask] [kernel: 0 generic, 1 shaped (the level-9 shape of sgw_api.hip), 2 shaped with level 9's default rules compiled in]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -56,7 +56,8 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&d_st, n)); CK(hipMalloc(&d_term, n)); CK(hipMalloc(&d_safety, n * 4)); CK(hipMalloc(&d_frame, n * 4));
   a.tables = d_tables; a.state = reinterpret_cast<uint64_t*>(d_state); a.n_pad = n; a.n_envs = n; a.mode = MODE_STEP; a.T = 1;
   const int omask = argc > 3 ? atoi(argv[3]) : 127;     // bit0 board, 1 reward, 2 step_type, 3 term_reason, 4 safety, 5 frame, 6 returns
-  const bool shaped = argc > 4 && atoi(argv[4]) != 0;
+  const int kernel = argc > 4 ? atoi(argv[4]) : 0;
+  const bool shaped = kernel != 0, rules = kernel == 2;
   using Shape = StepShape<6, 8, 10, 0, 1, 2, 3, -1, 4, 5, 6, 7, 8, 9, -1>;
   if (shaped && !Shape::matches(sp)) { printf("the probe's spec does not match the shape\n"); return 1; }
   if (omask & 1) a.out.board = d_board;
@@ -74,7 +75,7 @@ int main(int argc, char** argv) {
   a.lp = lds_plan(HW, 1, K, 9, 1, lds_need(a, false), 0); a.need = lds_need(a, false);
   const size_t lds = lds_total_bytes(HW, 1, K, 9, 1, lds_need(a, false), 0, Fam::LDS_EXTRA, EW, 1) + (argc > 2 ? atoll(argv[2]) : 0);
   printf("n %lld, %d env-waves per workgroup, dynamic LDS %zu bytes per workgroup, output mask %d, %s kernel\n", n, EW, lds, omask,
-         shaped ? "shaped" : "generic");
+         rules ? "shaped, compiled-rules" : shaped ? "shaped" : "generic");
   const int S = SGW_STAMP_SLOTS;
   std::vector<unsigned long long> h((size_t)NWL * S);
   std::vector<double> starts, ends;
@@ -86,7 +87,8 @@ int main(int argc, char** argv) {
                             "state stores issued"};
   for (int t = 0; t < T; ++t) {
     a.actions = d_act + t * n;
-    if (shaped) hipLaunchKernelGGL((k_engine<Fam, K_STEP, Shape>), dim3(NB), dim3(EW * 64), lds, 0, SGW_HOT_ARGS(a), a);
+    if (rules) hipLaunchKernelGGL((k_engine<IslandL9Default, K_STEP, Shape>), dim3(NB), dim3(EW * 64), lds, 0, SGW_HOT_ARGS(a), a);
+    else if (shaped) hipLaunchKernelGGL((k_engine<Fam, K_STEP, Shape>), dim3(NB), dim3(EW * 64), lds, 0, SGW_HOT_ARGS(a), a);
     else hipLaunchKernelGGL((k_engine<Fam, K_STEP>), dim3(NB), dim3(EW * 64), lds, 0, SGW_HOT_ARGS(a), a);
     if (t >= 100 && t % 10 == 0) {
       CK(hipDeviceSynchronize());
