@@ -147,6 +147,10 @@ def lib():
   L.sgw_sizeof_extras.restype = C.c_int
   L.sgw_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
   L.sgw_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+  if hasattr(L, "sgw_copy_envs"):                           # (as above: an older SGW_LIBRARY build cannot fork envs)
+    L.sgw_copy_envs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Out), C.POINTER(Out), C.c_void_p]
+    L.sgw_out_row_bytes.argtypes = [C.c_void_p, C.c_int]
+    L.sgw_out_row_bytes.restype = C.c_int64
   if L.sgw_abi_version() != ABI_VERSION:
     raise SgwError("libsgw.so ABI %d != binding ABI %d" % (L.sgw_abi_version(), ABI_VERSION))
   if L.sgw_sizeof_spec() != C.sizeof(Spec) or L.sgw_sizeof_out() != C.sizeof(Out):
@@ -168,7 +172,8 @@ EXPORTS = [
     "sgw_accumulate_returns", "sgw_observe", "sgw_derived_stats", "sgw_observe_layers", "sgw_state_layers", "sgw_view_bytes", "sgw_agent_views", "sgw_agent_layer_views", "sgw_state_words", "sgw_get_state", "sgw_set_state",
     "sgw_step_shape", "sgw_step_rules", "sgw_layer_coords", "sgw_agent_layer_coords", "sgw_step_lds_bytes",
     "sgw_sizeof_episodes", "sgw_episode_scratch_bytes", "sgw_log_episodes",
-    "sgw_seed_rng", "sgw_pcg64_from_seeds"]
+    "sgw_seed_rng", "sgw_pcg64_from_seeds",
+    "sgw_copy_envs", "sgw_out_row_bytes"]
 
 
 def check(rc, what=""):

@@ -30,6 +30,7 @@
 #include "sgw_coords.hpp"
 #include "sgw_episodes.hpp"
 #include "sgw_seed.hpp"
+#include "sgw_copy.hpp"
 
 using namespace sgw;
 
@@ -1477,6 +1478,79 @@ int sgw_set_state(sgw_engine* e, const uint64_t* state_dev, void* stream) {
                      e->n_pad, e->ks.words, state_dev);
   HIP_TRY(hipGetLastError());
   e->rng_set = 1;          // a saved state carries its envs' generator streams (resume needs no sgw_set_rng_state)
+  return SGW_OK;
+}
+
+// Bytes of one env's row of the field-th output of struct sgw_out (0: the family has no such output): the strides of
+// offset_out, as bytes
+static long long out_row_bytes(const sgw_spec& sp, int field) {
+  const long long HW = sp.H * sp.W, AK = sp.A * sp.K, A = sp.A, M = sp.M, VB = kspec_view_total(sp);
+  const long long PA = (sp.family == SGW_ISLAND_NAVIGATION_EX_MA || sp.family == SGW_AINTELOPE_SAVANNA) ? A : 1;
+  switch (field) {
+    case 0: return HW;            // board
+    case 1: return HW * 4;        // obs_board
+    case 2: return AK * 8;        // reward
+    case 3: return AK * 8;        // cumulative
+    case 4: return A;             // step_type
+    case 5: return PA;            // term_reason
+    case 6: return A;             // actual_action
+    case 7: return 8;             // discount
+    case 8: return 8;             // hidden
+    case 9: return PA * 4;        // safety
+    case 10: return M * 8;        // metrics
+    case 11: return 4;            // frame
+    case 12: return A * 2;        // agent_pos
+    case 13: return A;            // agent_flags
+    case 14: return sp.family == SGW_AINTELOPE_SAVANNA ? PA * 4 : 0;   // safety2
+    case 15: return VB;           // views
+    case 16: return VB * 4;       // obs_views
+    case 17: case 18: case 19: return A;   // done, obs_dir, act_dir
+    default: return -1;
+  }
+}
+static_assert(sizeof(sgw_out) == COPY_PLANES * sizeof(void*), "sgw_out is COPY_PLANES pointers: sgw_copy_envs walks it as an array");
+
+int64_t sgw_out_row_bytes(const sgw_engine* e, int field) {
+  if (!e || field < 0 || field >= COPY_PLANES) { fail(SGW_ERR_ARG, "sgw_out_row_bytes: null engine or no such output"); return SGW_ERR_ARG; }
+  return (int64_t)out_row_bytes(e->spec, field);
+}
+
+int sgw_copy_envs(sgw_engine* dst, const sgw_engine* src, const int32_t* dst_idx_dev, const int32_t* src_idx_dev, int64_t n,
+                  const sgw_out* dst_out, const sgw_out* src_out, void* stream) {
+  if (!dst || !src) return fail(SGW_ERR_ARG, "sgw_copy_envs: null engine");
+  if (n < 0) return fail(SGW_ERR_ARG, "sgw_copy_envs: n < 0");
+  if (dst != src) {
+    if (dst->device != src->device) return fail(SGW_ERR_ARG, "sgw_copy_envs: the engines are on different devices");
+    if (memcmp(&dst->spec, &src->spec, sizeof(sgw_spec)) != 0 || dst->ks.words != src->ks.words)
+      return fail(SGW_ERR_ARG, "sgw_copy_envs: the engines' specs (or state layouts) differ");
+  }
+  const int fam = dst->spec.family;
+  if ((fam == SGW_FIREMAKER_EX_MA || fam == SGW_ISLAND_NAVIGATION_EX_MA || fam == SGW_AINTELOPE_SAVANNA) && !dst->rng_set)
+    return fail(SGW_ERR_ARG, "sgw_copy_envs: the destination's generators were never set (sgw_set_rng_state, sgw_seed_rng or "
+                "sgw_set_state first: its padding lanes need a working stream)");
+  if (((uintptr_t)dst_idx_dev | (uintptr_t)src_idx_dev) & 3) return fail(SGW_ERR_ARG, "sgw_copy_envs: index arrays must be 4-byte aligned");
+  CopyArgs a; memset(&a, 0, sizeof(a));
+  a.src_state = src->state_dev; a.dst_state = dst->state_dev; a.src_idx = src_idx_dev; a.dst_idx = dst_idx_dev;
+  a.n = n; a.src_n = src->n_envs; a.dst_n = dst->n_envs; a.words = dst->ks.words; a.same = dst == src ? 1 : 0;
+  if (dst_out) {
+    void* const* dp = reinterpret_cast<void* const*>(dst_out);
+    void* const* sp = reinterpret_cast<void* const*>(src_out);
+    for (int f = 0; f < COPY_PLANES; ++f) {
+      if (!dp[f]) continue;
+      if (!sp || !sp[f]) return fail(SGW_ERR_ARG, "sgw_copy_envs: an output is set in dst_out and NULL in src_out");
+      const long long rb = out_row_bytes(dst->spec, f);
+      if (rb <= 0) continue;                       // the family has no such output: nothing to move
+      CopyPlane& pl = a.planes[a.n_planes++];
+      pl.src = static_cast<const uint8_t*>(sp[f]); pl.dst = static_cast<uint8_t*>(dp[f]); pl.row_bytes = (int)rb;
+    }
+  }
+  if (n == 0) return SGW_OK;
+  const long long waves = copy_plan(a);
+  if (n > 0x7fffffffLL || waves > 0x7fffffffLL) return fail(SGW_ERR_ARG, "sgw_copy_envs: too many pairs for one launch (2^31 waves)");
+  HIP_TRY(hipSetDevice(dst->device));
+  hipLaunchKernelGGL(k_copy_envs, dim3((unsigned)((waves + COPY_THREADS / WAVE - 1) / (COPY_THREADS / WAVE))), dim3(COPY_THREADS), 0,
+                     (hipStream_t)stream, a, (unsigned)waves);
+  HIP_TRY(hipGetLastError());
   return SGW_OK;
 }
 

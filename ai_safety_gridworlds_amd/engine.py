@@ -24,6 +24,8 @@ ALL_OUTPUTS = tuple(f for f in N.OUT_FIELDS if f not in ("safety2", "views", "ob
 
 # families whose step launch can write the agent windows itself (sgw_out.views / obs_views)
 FUSED_VIEW_FAMILIES = (N.FIREMAKER_EX_MA, N.ISLAND_NAVIGATION_EX_MA, N.AINTELOPE_SAVANNA)
+# families whose envs own numpy generators (sgw_set_rng_state / sgw_seed_rng): the streams are state words
+GENERATOR_FAMILIES = (N.FIREMAKER_EX_MA, N.ISLAND_NAVIGATION_EX_MA, N.AINTELOPE_SAVANNA)
 
 
 def fused_views(spec):
@@ -165,6 +167,8 @@ class BatchedEngine(object):
     self._out = N.Out()
     self._alloc_outputs(1)
     self._keep = []          # tensors the library holds raw pointers to
+    self._inputs = {}        # what set_episode_bits / set_random_stream were given: (device tensor or None, seed), for fork()
+    self._look = None        # lookahead()'s cached fork and result tensors
     table = getattr(spec, "family_table", None)
     if table is not None:    # aintelope_savanna: host-evaluated visit-count rewards (sgw_set_family_table)
       table = np.ascontiguousarray(table, dtype=np.float64)
@@ -188,16 +192,19 @@ class BatchedEngine(object):
       return dict(self._views_cache)
     out = {}
     for name, t in self._bufs.items():
-      v = t[:, :self.n_envs] if self._T > 1 else t[:self.n_envs]
-      if name in ("board", "obs_board"):
-        v = v.reshape(v.shape[:-1] + (self.spec.H, self.spec.W))
-      elif name in ("reward", "cumulative") and self.spec.A > 1:
-        v = v.reshape(v.shape[:-1] + (self.spec.A, self.spec.K))
-      elif name == "agent_pos":
-        v = v.reshape(v.shape[:-1] + (self.spec.A, 2))
-      out[name] = v
+      out[name] = self._shaped(name, t[:, :self.n_envs] if self._T > 1 else t[:self.n_envs])
     self._views_cache = out
     return dict(out)
+
+  def _shaped(self, name, v):
+    """[..., N, row] of an output buffer in the shape the API hands out."""
+    if name in ("board", "obs_board"):
+      v = v.reshape(v.shape[:-1] + (self.spec.H, self.spec.W))
+    elif name in ("reward", "cumulative") and self.spec.A > 1:
+      v = v.reshape(v.shape[:-1] + (self.spec.A, self.spec.K))
+    elif name == "agent_pos":
+      v = v.reshape(v.shape[:-1] + (self.spec.A, 2))
+    return v
 
   def _stream(self):
     # the raw handle of torch's current stream on this device (torch.cuda.current_stream() builds a Stream object: 2 us per call)
@@ -385,14 +392,17 @@ class BatchedEngine(object):
     None: drawn in the kernel from u = Philox(seed, global env id = env_id_base + i, k), uniform in [0, 1):
     safe_interruptibility(_ex) u <= interruption_probability (inclusive); absent_supervisor and distributional_shift u < 0.5
     (strict: np.random.rand() < 0.5, np.random.choice of two)."""
+    self._drop_lookahead()
     if bits is None:
       N.check(self._lib.sgw_set_episode_bits(self._h, None, 0, int(seed)), "sgw_set_episode_bits")
+      self._inputs["episode_bits"] = (None, int(seed))
       return
     bits = torch.as_tensor(bits).to(device=self.device, dtype=torch.uint8).contiguous()
     assert bits.dim() == 2 and bits.shape[0] == self.n_envs
     self._keep.append(bits)
     N.check(self._lib.sgw_set_episode_bits(self._h, bits.data_ptr(), bits.shape[1], int(seed)),
             "sgw_set_episode_bits")
+    self._inputs["episode_bits"] = (bits, int(seed))
 
   def set_random_stream(self, u, seed=0):
     """Random numbers for the families that draw from the process-global numpy RNG an input-dependent number of times:
@@ -402,13 +412,18 @@ class BatchedEngine(object):
     whisky_gold (human_player=True, after the whisky): per step u < whisky_exploration replaces the action, by direction
     floor(4u') of a second draw.  Other families and configurations read nothing.
     None: drawn in the kernel, draw k = word pair k & 1 of Philox(seed, global env id = env_id_base + i, block k >> 1)."""
+    self._drop_lookahead()
     if u is None:
       N.check(self._lib.sgw_set_random_stream(self._h, None, 0, int(seed)), "sgw_set_random_stream")
+      self._inputs["random_stream"] = (None, int(seed))
       return
-    u = torch.as_tensor(np.ascontiguousarray(u, dtype=np.float64)).to(self.device).contiguous()
+    if not (torch.is_tensor(u) and u.dtype == torch.float64):
+      u = torch.as_tensor(np.ascontiguousarray(u, dtype=np.float64))
+    u = u.to(self.device).contiguous()
     assert u.dim() == 2 and u.shape[0] == self.n_envs
     self._keep.append(u)
     N.check(self._lib.sgw_set_random_stream(self._h, u.data_ptr(), u.shape[1], int(seed)), "sgw_set_random_stream")
+    self._inputs["random_stream"] = (u, int(seed))
 
   def set_rng_seeds(self, seeds):
     """firemaker_ex_ma / island_navigation_ex_ma: per-env numpy streams Generator(PCG64(SeedSequence(seed))) -- what
@@ -724,6 +739,111 @@ class BatchedEngine(object):
                                          pp, fp, hidx, out.data_ptr(), self._stream()), "sgw_observe_layers")
     return out
 
+  # -- forking ----------------------------------------------------------------------------------
+  def _pair_index(self, v, what):
+    """An index list of copy_envs -> a contiguous int32 tensor on this device (a host array is uploaded once)."""
+    if torch.is_tensor(v):
+      if v.dtype.is_floating_point or v.dtype == torch.bool:
+        raise TypeError("%s must be integers" % what)
+      return v.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=np.int32)).to(self.device)
+
+  def copy_envs(self, src, src_idx=None, dst_idx=None, outputs=True):
+    """Env dst_idx[i] of THIS engine becomes a bit-exact copy of env src_idx[i] of `src` (sgw_copy_envs: one launch on the current
+    stream, no synchronisation, capturable): every state word -- generator streams and draw counters included -- and, with
+    `outputs`, the env's row of every output both engines allocate, so this engine's current observation of the env is valid
+    without a step.  src: a BatchedEngine of the same spec on this device (it may be this engine).  src_idx / dst_idx: int32 device
+    tensors, or host arrays (uploaded once); None: i.  A pair with an index < 0 or >= its engine's n_envs is skipped (the mask:
+    dst_idx[i] = -1), and so is a copy of an env onto itself.  The destination indices must be distinct, and within one engine no
+    env may be both a source and a destination; repeated sources are fine.  outputs=True needs the plain [N_pad, ...] buffers
+    of both engines (after step_n / rollout with write_every: step or reset first).
+    Not copied: the episodic-return accumulators, and the engine's external inputs (set_episode_bits, set_random_stream, the
+    family table): the copy draws from THIS engine's inputs, keyed by this engine's global env id or array row."""
+    if not isinstance(src, BatchedEngine) or src._h is None or self._h is None:
+      raise N.SgwError("copy_envs: needs two open BatchedEngines (there is no CPU path)")
+    keep = []
+    sptr = dptr = None
+    if src_idx is not None:
+      keep.append(self._pair_index(src_idx, "src_idx")); sptr = keep[-1].data_ptr()
+    if dst_idx is not None:
+      keep.append(self._pair_index(dst_idx, "dst_idx")); dptr = keep[-1].data_ptr()
+    if len(keep) == 2 and keep[0].numel() != keep[1].numel():
+      raise ValueError("src_idx and dst_idx must have the same number of entries")
+    n = keep[0].numel() if keep else min(self.n_envs, src.n_envs)
+    dout = sout = None
+    if outputs:
+      if self._T != 1 or src._T != 1:
+        raise N.SgwError("copy_envs: output rows are copied between the [N_pad, ...] buffers of a single step; both engines "
+                         "hold [T, N_pad, ...] buffers only after step_n / rollout / replay with write_every")
+      d, sout = N.Out(), C.byref(src._out)
+      for name in self.outputs:
+        if name in src._bufs:
+          setattr(d, name, self._bufs[name].data_ptr())
+      dout = C.byref(d)
+    N.check(self._lib.sgw_copy_envs(self._h, src._h, dptr, sptr, n, dout, sout, self._stream()), "sgw_copy_envs")
+
+  def fork(self, n_envs=None, env_id_base=None, outputs=None):
+    """A new engine with this engine's spec, device and (by default) env_id_base, outputs and number of envs, and the external
+    inputs this one was given (set_episode_bits / set_random_stream; the family table comes from the spec): what copy.deepcopy(env)
+    is to the reference, for the whole batch.  The generator families are seeded first (seed_rng()), so that every lane of the new
+    engine, padding included, has a working stream.  With n_envs equal to this engine's the fork then becomes a copy of it: every
+    env's state and the rows of every output both allocate (copy_envs), so stepping both with the same actions gives the same
+    outputs from here on.  With another n_envs nothing is copied (fill it with copy_envs), and explicit per-env input arrays
+    cannot be re-applied: ValueError."""
+    n = self.n_envs if n_envs is None else int(n_envs)
+    if n != self.n_envs:
+      for name, (arr, _) in self._inputs.items():
+        if arr is not None:
+          raise ValueError("fork: the %s array has one row per env of this engine and cannot be re-applied to %d envs" % (name, n))
+    new = BatchedEngine(self.spec, n, device=self.device, env_id_base=self.env_id_base if env_id_base is None else int(env_id_base),
+                        outputs=self.outputs if outputs is None else outputs)
+    if "episode_bits" in self._inputs:
+      new.set_episode_bits(self._inputs["episode_bits"][0], seed=self._inputs["episode_bits"][1])
+    if "random_stream" in self._inputs:
+      new.set_random_stream(self._inputs["random_stream"][0], seed=self._inputs["random_stream"][1])
+    if self.spec.family in GENERATOR_FAMILIES:
+      new.seed_rng()
+    if n == self.n_envs:
+      new.copy_envs(self, outputs=self._T == 1)
+    return new
+
+  def _drop_lookahead(self):
+    look = getattr(self, "_look", None)
+    self._look = None
+    if look is not None:
+      look["engine"].close()
+
+  def lookahead(self, actions):
+    """What step(actions[b]) would return NOW, for each of B candidate action sets, without committing any of them: actions int8
+    [B, N(, A)] -> {output: [B, N, ...]}.  This engine's state, output buffers and accumulators do not change.  The work is done by
+    a cached fork with this engine's env_id_base and external inputs, so seeded draws are the ones a real step would take: per b
+    one state-only copy_envs into the fork and one step of the fork, whose launch writes its outputs straight into entry b of the
+    stacked result ([B, N_pad, ...] buffers: no copy afterwards).  The result tensors are persistent and rewritten by the next
+    call with the same B."""
+    actions = actions.to(device=self.device, dtype=torch.int8).contiguous()
+    B = int(actions.shape[0]) if actions.dim() >= 2 else 0
+    if B < 1 or actions.numel() != B * self.n_envs * self.spec.A:
+      raise ValueError("lookahead: actions must be int8 [B, N] (or [B, N, A])")
+    look = self._look
+    if look is None:
+      look = self._look = {"engine": self.fork(), "B": 0}
+    eng = look["engine"]
+    if look["B"] != B:
+      stack = {k: torch.zeros((B, eng.n_pad) + _dtype_shape(self.spec, k)[1], dtype=_dtype_shape(self.spec, k)[0], device=self.device)
+               for k in eng.outputs}
+      outs = []
+      for b in range(B):
+        o = N.Out()
+        for k, t in stack.items():
+          setattr(o, k, t[b].data_ptr())
+        outs.append(o)
+      look.update(B=B, stack=stack, outs=outs, res={k: self._shaped(k, t[:, :self.n_envs]) for k, t in stack.items()})
+    stream, per = self._stream(), self.n_envs * self.spec.A
+    for b in range(B):
+      eng.copy_envs(self, outputs=False)
+      N.check(self._lib.sgw_step(eng._h, actions.data_ptr() + b * per, C.byref(look["outs"][b]), stream), "sgw_step")
+    return dict(look["res"])
+
   def get_state(self):
     words = int(self._lib.sgw_state_words(self._h))
     st = torch.empty((words, self.n_pad), dtype=torch.int64, device=self.device)
@@ -735,6 +855,8 @@ class BatchedEngine(object):
     N.check(self._lib.sgw_set_state(self._h, st.data_ptr(), self._stream()), "sgw_set_state")
 
   def close(self):
+    if getattr(self, "_look", None) is not None:
+      self._drop_lookahead()
     if getattr(self, "_h", None):
       self._lib.sgw_destroy(self._h)
       self._h = None

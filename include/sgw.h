@@ -447,6 +447,34 @@ int sgw_state_words(const sgw_engine* e);
 int sgw_get_state(sgw_engine* e, uint64_t* state_dev, void* stream);
 int sgw_set_state(sgw_engine* e, const uint64_t* state_dev, void* stream);
 
+/* Fork envs: for every pair i < n, env dst_idx_dev[i] of `dst` becomes a bit-exact copy of env src_idx_dev[i] of `src` -- what
+ * copy.deepcopy(env) and pickling give the reference's users (safety_game_mo.py:406-419), batched.  Every state word is copied
+ * (generator streams, draw counters and cached maps are state words); an index array that is NULL means i.  With dst_out and
+ * src_out the env's ROW of every output that is non-NULL in dst_out is copied from src_out too, so the destination's current
+ * observation is valid without a step (non-NULL in dst_out and NULL in src_out: SGW_ERR_ARG; outputs set only in src_out are
+ * ignored; both NULL: the state only).  Rows are those of the [N_pad, ...] arrays of struct sgw_out for the engines' spec
+ * (sgw_out_row_bytes); step t of a [T, N_pad, ...] buffer is addressed by passing the pointers of that t.
+ * A pair is skipped -- nothing of it is read or written -- when either index is negative or >= n_envs of its engine (the mask:
+ * dst_idx_dev[i] = -1), or when dst == src and the two indices are equal.
+ * One plain launch on the caller's stream: no allocation, no synchronisation, no read-back; capturable.
+ * dst and src may be one engine; otherwise they must be on one device, with byte-identical sgw_spec and equal sgw_state_words
+ * (SGW_ERR_ARG otherwise); n_envs and env_id_base may differ.
+ * The CALLER guarantees, unchecked on the device: the destination indices are distinct; within one engine no env is the source
+ * of one pair and the destination of another.  Repeated sources (fan-out) are fine.
+ * NOT copied: the episodic-return accumulators (sgw_read_returns); captured graphs (none is invalidated: no launch argument
+ * moves); performance bookkeeping and episode logs (caller-owned); the engine-level external inputs (sgw_set_episode_bits,
+ * sgw_set_random_stream, sgw_set_family_table).  The copy carries the env's episode and draw counters, so a copied env draws
+ * from the DESTINATION engine's inputs, keyed by the destination's global env id (seeded streams) or array row; env-owned PCG64
+ * generators are state and continue identically wherever the copy lands.
+ * firemaker_ex_ma, island_navigation_ex_ma, aintelope_savanna: the destination's generators must have been set by one of its own
+ * setters before (sgw_set_rng_state, sgw_seed_rng, sgw_set_state), SGW_ERR_ARG otherwise: the padding lanes of a never-seeded
+ * engine hold no working stream, and this call never marks an engine as seeded. */
+int sgw_copy_envs(sgw_engine* dst, const sgw_engine* src, const int32_t* dst_idx_dev, const int32_t* src_idx_dev, int64_t n,
+                  const sgw_out* dst_out, const sgw_out* src_out, void* stream);
+/* Bytes of one env's row of an output: field = position in struct sgw_out, 0 = board ... 19 = act_dir; per family (term_reason /
+ * safety widths, the window bytes, safety2 for aintelope_savanna only).  0: the family has no such output; < 0: bad argument. */
+int64_t sgw_out_row_bytes(const sgw_engine* e, int field);
+
 /* Which kernel runs the engine's one-step launches (sgw_step, sgw_step_n): 0 = the generic kernel, k > 0 = the k-th kernel with
  * the output geometry of one spec compiled in (chosen by sgw_create when family, state variant and geometry match one exactly;
  * SGW_GENERIC_STEP set in the environment at sgw_create keeps the generic kernel).  Both compute the same bytes. */
