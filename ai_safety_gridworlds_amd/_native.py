@@ -151,6 +151,9 @@ def lib():
     L.sgw_copy_envs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Out), C.POINTER(Out), C.c_void_p]
     L.sgw_out_row_bytes.argtypes = [C.c_void_p, C.c_int]
     L.sgw_out_row_bytes.restype = C.c_int64
+  if hasattr(L, "sgw_scalarise"):                           # (as above: an older SGW_LIBRARY build has no scalar rewards)
+    L.sgw_scalarise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p]
   if L.sgw_abi_version() != ABI_VERSION:
     raise SgwError("libsgw.so ABI %d != binding ABI %d" % (L.sgw_abi_version(), ABI_VERSION))
   if L.sgw_sizeof_spec() != C.sizeof(Spec) or L.sgw_sizeof_out() != C.sizeof(Out):
@@ -173,7 +176,8 @@ EXPORTS = [
     "sgw_step_shape", "sgw_step_rules", "sgw_layer_coords", "sgw_agent_layer_coords", "sgw_step_lds_bytes",
     "sgw_sizeof_episodes", "sgw_episode_scratch_bytes", "sgw_log_episodes",
     "sgw_seed_rng", "sgw_pcg64_from_seeds",
-    "sgw_copy_envs", "sgw_out_row_bytes"]
+    "sgw_copy_envs", "sgw_out_row_bytes",
+    "sgw_scalarise"]
 
 
 def check(rc, what=""):

@@ -31,6 +31,7 @@
 #include "sgw_episodes.hpp"
 #include "sgw_seed.hpp"
 #include "sgw_copy.hpp"
+#include "sgw_scalarise.hpp"
 
 using namespace sgw;
 
@@ -1550,6 +1551,44 @@ int sgw_copy_envs(sgw_engine* dst, const sgw_engine* src, const int32_t* dst_idx
   HIP_TRY(hipSetDevice(dst->device));
   hipLaunchKernelGGL(k_copy_envs, dim3((unsigned)((waves + COPY_THREADS / WAVE - 1) / (COPY_THREADS / WAVE))), dim3(COPY_THREADS), 0,
                      (hipStream_t)stream, a, (unsigned)waves);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+int sgw_scalarise(sgw_engine* e, const double* reward_dev, const double* cumulative_dev, const int32_t* frame_dev, int T,
+                  const int32_t* k_agent, double* scalar_reward_dev, double* scalar_cumulative_dev, double* scalar_average_dev,
+                  void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_scalarise: null engine");
+  if (T < 1) return fail(SGW_ERR_ARG, "sgw_scalarise: T < 1");
+  if (!scalar_reward_dev && !scalar_cumulative_dev && !scalar_average_dev) return fail(SGW_ERR_ARG, "sgw_scalarise: no output");
+  if ((scalar_reward_dev && !reward_dev) || (scalar_cumulative_dev && !cumulative_dev) || (scalar_average_dev && (!cumulative_dev || !frame_dev)))
+    return fail(SGW_ERR_ARG, "sgw_scalarise: an output's source is NULL (scalar_reward: reward; scalar_cumulative: cumulative; "
+                "scalar_average: cumulative and frame)");
+  const int A = e->spec.A, K = e->spec.K;
+  static_assert(SGW_MAX_K == 16, "k_scalarise dispatches on 1..16 reward dimensions");
+  ScalariseArgs a; memset(&a, 0, sizeof(a));
+  for (int ag = 0; ag < A; ++ag) {
+    const int k = k_agent ? k_agent[ag] : K;
+    if (k < 0 || k > K) return fail(SGW_ERR_ARG, "sgw_scalarise: k_agent out of range");
+    a.k[ag] = k;
+  }
+  a.reward = scalar_reward_dev ? reward_dev : nullptr;               // a source nobody asks for is not read
+  a.cumulative = (scalar_cumulative_dev || scalar_average_dev) ? cumulative_dev : nullptr;
+  a.frame = scalar_average_dev ? frame_dev : nullptr;
+  if (((uintptr_t)a.reward | (uintptr_t)a.cumulative) & 15)
+    return fail(SGW_ERR_ARG, "sgw_scalarise: reward / cumulative must be 16-byte aligned (rows move as 16-byte accesses)");
+  if (((uintptr_t)scalar_reward_dev | (uintptr_t)scalar_cumulative_dev | (uintptr_t)scalar_average_dev) & 7 || ((uintptr_t)a.frame & 3))
+    return fail(SGW_ERR_ARG, "sgw_scalarise: misaligned output or frame pointer");
+  a.scalar_reward = scalar_reward_dev; a.scalar_cumulative = scalar_cumulative_dev; a.scalar_average = scalar_average_dev;
+  a.n = e->n_envs; a.n_pad = e->n_pad; a.A = A; a.K = K;
+  a.recip_AK = ((1 << 18) + A * K - 1) / (A * K);
+  const long long chunks = (e->n_envs + WAVE - 1) / WAVE;
+  if (chunks == 0) return SGW_OK;
+  if (chunks * T > 0x7fffffffLL) return fail(SGW_ERR_ARG, "sgw_scalarise: too many rows for one launch (2^31 waves)");
+  a.chunks = (unsigned)chunks;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t lds = (size_t)2 * A * K * WAVE * 8;                   // R | C (sgw_scalarise.hpp): <= 64 KiB for A K <= 64
+  hipLaunchKernelGGL(k_scalarise, dim3((unsigned)(chunks * T)), dim3(WAVE), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return SGW_OK;
 }

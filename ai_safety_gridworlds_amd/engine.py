@@ -703,6 +703,84 @@ class BatchedEngine(object):
     out["average_reward"] = stats[..., 5:]
     return out
 
+  # -- scalar rewards --------------------------------------------------------------------------
+  def _k_agent(self):
+    """The spec's reward dimensions per agent column as the HOST int32 array the library reads (built once)."""
+    karr = getattr(self, "_karr", None)
+    if karr is None:
+      ks = self._agent_ks()
+      karr = self._karr = (C.c_int32 * N.MAX_AGENTS)(*(ks + [0] * (N.MAX_AGENTS - len(ks))))
+    return karr
+
+  def _padded_source(self, name, t, T):
+    """Data pointer of `t` as the [T, N_pad, row] buffer of output `name`: the padded buffer itself, or the [T, N, ...] view of it
+    that a write_every call returned (same first byte, the padded strides)."""
+    dt, shp = _dtype_shape(self.spec, name)
+    row = int(np.prod(shp, dtype=np.int64))
+    ok = torch.is_tensor(t) and t.device == self.device and t.dtype == dt and t.dim() >= (2 if T > 1 else 1)
+    if ok and T > 1:
+      ok = (t.shape[0] == T and t.shape[1] in (self.n_envs, self.n_pad) and t.stride(0) == self.n_pad * row and t[0].is_contiguous()
+            and t[0].numel() == t.shape[1] * row)
+    elif ok:
+      ok = t.is_contiguous() and t.shape[0] in (self.n_envs, self.n_pad) and t.numel() == t.shape[0] * row
+    if not ok:
+      raise N.SgwError("scalarise: buffers[%r] must be the %s [%s%d or %d, ...] output buffer of this engine on %s (there is no CPU path)"
+                       % (name, dt, "%d, " % T if T > 1 else "", self.n_envs, self.n_pad, self.device))
+    return t.data_ptr()
+
+  def scalarise(self, T=1, buffers=None):
+    """scalarise=True of the reference's multi-objective environments (_process_timestep, safety_game_mo.py:1027-1066) for the
+    engine's current outputs, from ONE library call (sgw_scalarise: one launch, no synchronisation, capturable): dict of float64
+    tensors "scalar_reward", "scalar_cumulative", "scalar_average", [N] (or [N, A] with several agents), [T, N(, A)] for T > 1.
+    Each is the reference's Python sum() over the agent's reward dimensions -- an accumulator that starts at 0.0, one addition
+    per column, left to right -- of the `reward` row, of the `cumulative` row, and of cumulative[i] / (frame + 1) (the sum of
+    the quotients, not the quotient of the sum).
+    T == 1 reads the [N_pad, ...] buffers of a step / reset; T > 1 the [T, N_pad, ...] buffers of step_n / rollout / replay with
+    write_every.  buffers: {"reward", "cumulative", "frame"} to read instead of the engine's own, e.g. what an earlier
+    write_every call returned.  The result tensors are persistent per T and rewritten by the next call: a per-step call
+    allocates nothing.  Needs the 'reward', 'cumulative' and 'frame' outputs; there is no CPU path."""
+    T = int(T)
+    if T < 1:
+      raise ValueError("scalarise: T must be >= 1")
+    if self._h is None:
+      raise N.SgwError("scalarise: the engine has no device engine behind it (closed?); there is no CPU path")
+    if buffers is None:
+      if self._T != T or any(k not in self._bufs for k in ("reward", "cumulative", "frame")):
+        raise N.SgwError("scalarise(T=%d) needs the 'reward', 'cumulative' and 'frame' outputs of %s (the engine holds T=%d buffers of %s)"
+                         % (T, "a single step" if T == 1 else "a write_every call over %d steps" % T, self._T, sorted(self._bufs)))
+      ptrs = [self._bufs[k].data_ptr() for k in ("reward", "cumulative", "frame")]
+    else:
+      for k in ("reward", "cumulative", "frame"):
+        if k not in buffers:
+          raise N.SgwError("scalarise: buffers needs 'reward', 'cumulative' and 'frame'")
+      ptrs = [self._padded_source(k, buffers[k], T) for k in ("reward", "cumulative", "frame")]
+    cache = self.__dict__.setdefault("_scalars", {})
+    c = cache.get(T)
+    if c is None:
+      A = self.spec.A
+      bufs = [torch.zeros(((T, self.n_pad, A) if T > 1 else (self.n_pad, A)), dtype=torch.float64, device=self.device) for _ in range(3)]
+      res = {}
+      for name, b in zip(("scalar_reward", "scalar_cumulative", "scalar_average"), bufs):
+        v = b[:, :self.n_envs] if T > 1 else b[:self.n_envs]
+        res[name] = v[..., 0] if A == 1 else v
+      c = cache[T] = (bufs, res)
+    bufs, res = c
+    N.check(self._lib.sgw_scalarise(self._h, ptrs[0], ptrs[1], ptrs[2], T, self._k_agent(), bufs[0].data_ptr(), bufs[1].data_ptr(),
+                                    bufs[2].data_ptr(), self._stream()), "sgw_scalarise")
+    return dict(res)
+
+  def scalarise_rows(self, rows):
+    """The same left-to-right sum (sgw_scalarise) over the agents' reward dimensions of ANY float64 [N, A*K] device tensor laid
+    out like the `reward` output (a last performance, a mean of performances): a new [N] (or [N, A]) tensor."""
+    A, K = self.spec.A, self.spec.K
+    if (not torch.is_tensor(rows) or rows.device != self.device or rows.dtype != torch.float64 or rows.numel() != self.n_envs * A * K):
+      raise N.SgwError("scalarise_rows: needs a float64 [N, A*K] tensor on %s (there is no CPU path)" % (self.device,))
+    rows = rows.contiguous()
+    out = torch.empty((self.n_envs, A), dtype=torch.float64, device=self.device)
+    N.check(self._lib.sgw_scalarise(self._h, rows.data_ptr(), None, None, 1, self._k_agent(), out.data_ptr(), None, None, self._stream()),
+            "sgw_scalarise")
+    return out[:, 0] if A == 1 else out
+
   def observe_layers(self, board=None, agent_pos=None, agent_flags=None):
     """Unoccluded per-character layers with the gap correction: uint8 [N, L, H, W], L = len(spec.layer_chars)
     (what the MO/MA envs put in observation['layers']: rendering.py:188-302, observation_distiller_ex.py:164-178)."""

@@ -41,13 +41,21 @@ class TimeStep(collections.namedtuple("TimeStep", ["step_type", "reward", "disco
 class BatchedSafetyEnvironment(object):
 
   def __init__(self, env_name, num_envs=1, device="cuda:0", env_id_base=0, outputs=None, track_performance=True, episode_log=None,
-               **kwargs):
+               scalarise=False, **kwargs):
     self.env_name = env_name
     self._track_performance = bool(track_performance)     # get_last_performance bookkeeping: two more device ops per step
     self.spec = make_spec(env_name, **kwargs)
+    # scalarise=True (safety_game_mo.py:174, 276; safety_game_moma.py:177, 281): TimeStep.reward and the performance getters
+    # become the reference's left-to-right sum over the reward dimensions, from one more library call per step (sgw_scalarise).
+    # The constructors of the original scalar-reward envs take no such argument
+    self.scalarise = bool(scalarise)
+    if self.scalarise and self.spec.scalar:
+      raise TypeError("%s: unknown argument 'scalarise'" % env_name)
     self.num_envs = int(num_envs)
     if outputs is None:        # everything the family produces ('safety2_<agent>' exists in aintelope_savanna only)
       outputs = ALL_OUTPUTS + (("safety2",) if self.spec.name == "aintelope_savanna" else ())
+    if self.scalarise:         # what the sums read
+      outputs = tuple(dict.fromkeys(tuple(outputs) + ("reward", "cumulative", "frame")))
     if episode_log is not None:       # the log's sources are asked for too
       outputs = tuple(dict.fromkeys(tuple(outputs) + ("step_type",) + tuple(EpisodeLog.SOURCE.values())))
     self.engine = BatchedEngine(self.spec, self.num_envs, device=device, env_id_base=env_id_base,
@@ -83,7 +91,11 @@ class BatchedSafetyEnvironment(object):
       st = st[:, 0]                                           # all agents of an env share the step type
     if self._track_performance and ("cumulative" in o or "hidden" in o):      # _calculate_episode_performance (safety_game.py:253-263)
       self._track(o)
-    return TimeStep(step_type=st, reward=o.get("reward"), discount=o.get("discount"), observation=o)
+    reward = o.get("reward")
+    if self.scalarise:                                        # the vectors stay in the observation; FIRST rows sum to 0.0
+      o.update(self.engine.scalarise())
+      reward = o["scalar_reward"]
+    return TimeStep(step_type=st, reward=reward, discount=o.get("discount"), observation=o)
 
   def _perf_source(self, o):
     use_hidden = self.spec.scalar and getattr(self.spec, "performance", "hidden") == "hidden"   # distributional_shift keeps the default: episode return
@@ -134,7 +146,11 @@ class BatchedSafetyEnvironment(object):
 
   def get_last_performance(self, default=None):
     """Per env: performance of the last finished episode (safety_game.py:229-251); NaN rows = none yet."""
-    return default if self._last_performance is None else self._last_performance
+    if self._last_performance is None:
+      return default
+    if self.scalarise:                 # np.float64(sum(reward_dims)) per env (and agent: the reference's MoMa getter raises here)
+      return self.engine.scalarise_rows(self._last_performance)
+    return self._last_performance
 
   def get_overall_performance(self, default=None):
     """Per env: the mean of the performances of its finished episodes, sum(_episodic_performances) / len(...) in the reference's
@@ -142,7 +158,10 @@ class BatchedSafetyEnvironment(object):
     `episodes_finished()` gives the counts."""
     if self._last_performance is None:
       return default
-    return self._performance_sum / self._episodes.to(torch.float64)[:, None]      # 0 / 0 = NaN where none finished
+    mean = self._performance_sum / self._episodes.to(torch.float64)[:, None]      # 0 / 0 = NaN where none finished
+    if self.scalarise:                 # the sum of the per-dimension means, left to right (safety_game_mo.py:932-934); NaN stays NaN
+      return self.engine.scalarise_rows(mean)
+    return mean
 
   def episodes_finished(self):
     return None if self._last_performance is None else self._episodes

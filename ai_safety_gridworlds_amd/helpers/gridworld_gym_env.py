@@ -256,8 +256,12 @@ class GridworldGymEnv(_Base):
       # order (sgw_derived_stats); only the values come to the host
       ds = self._env.engine.derived_stats()
       pick = (lambda t: t[0, ai] if self._ma else t[0])
-      info["cumulative_reward"] = cum.copy()
-      info["average_reward"] = pick(ds["average_reward"]).cpu().numpy()[:len(names)].astype(np.float64)
+      if self._env.scalarise:                  # np.float64 sums of the dimensions (safety_game_mo.py:1031-1045), from the device
+        info["cumulative_reward"] = np.float64(o["scalar_cumulative"].reshape(-1)[ai])
+        info["average_reward"] = np.float64(o["scalar_average"].reshape(-1)[ai])
+      else:
+        info["cumulative_reward"] = cum.copy()
+        info["average_reward"] = pick(ds["average_reward"]).cpu().numpy()[:len(names)].astype(np.float64)
       for key in ("gini_index", "cumulative_gini_index", "mo_variance", "cumulative_mo_variance", "average_mo_variance"):
         info[key] = np.float64(pick(ds[key]).item())
       lay = None
@@ -374,6 +378,8 @@ class GridworldGymEnv(_Base):
     elif sp.scalar:
       r = float(o["reward"].reshape(-1)[0])
       reward = int(r) if r == int(r) else r
+    elif self._env.scalarise:                    # np.float64(sum(reward_dims)) (safety_game_mo.py:1056-1062)
+      reward = np.float64(o["scalar_reward"].reshape(-1)[ai])
     else:
       reward = o["reward"].reshape(-1)[ai * sp.K:ai * sp.K + len(self._dim_names())].astype(np.float64).copy()
     if sp.scalar:                                # gym_env.py:498-505
@@ -470,6 +476,7 @@ class GridworldVectorEnv(object):
     o = self._env.engine.step(actions)
     self._env._log_step()
     self._env._last = o
+    sc = self._env.engine.scalarise() if self._env.scalarise else None      # one more library call, into persistent tensors
     c = self._lean
     if c is None or c["_for"] is not o["step_type"]:
       st = o["step_type"].reshape(self.num_envs, -1)[:, 0]
@@ -478,6 +485,9 @@ class GridworldVectorEnv(object):
                         "done": o["done"].reshape(self.num_envs, -1)[:, 0].view(torch.bool),
                         "info": {"step_type": st, "term_reason": o.get("term_reason"), "board": o.get("board"),
                                  "cumulative": o.get("cumulative"), "hidden": o.get("hidden")}}
+      if sc is not None:                       # reward float64 [N]; the scalar cumulative / average rewards ride along
+        c["reward"] = sc["scalar_reward"]
+        c["info"].update(cumulative_reward=sc["scalar_cumulative"], average_reward=sc["scalar_average"])
     return c["obs"], c["reward"], c["done"], self._never, dict(c["info"])
 
   def _step_full(self, actions):
@@ -487,6 +497,7 @@ class GridworldVectorEnv(object):
                                    replay=self._replay)
     self._env._log_step()
     self._env._last = o
+    sc = self._env.engine.scalarise() if self._env.scalarise else None      # one more library call, into persistent tensors
     if self._coords:                         # one more launch into persistent buffers (the launch writes the lists only)
       self._coords_out = self._env.engine.layer_coords(layers=o.get("layers"), cap=self._coords_cap, out=self._coords_out)
     if self._info is None or self._info["_for"] is not o["step_type"]:
@@ -503,6 +514,9 @@ class GridworldVectorEnv(object):
         info["coordinates_count"], info["coordinates"] = self._coords_out
       self._info = {"_for": o["step_type"], "info": info, "done": o["done"], "obs": o["obs_board"].unsqueeze(1),
                     "reward": o["reward"] if not self.spec_.scalar else o["reward"].reshape(-1)}
+      if sc is not None:                       # scalarise=True: reward [N]; cumulative_reward / average_reward lose their K axis
+        self._info["reward"] = sc["scalar_reward"]
+        info.update(cumulative_reward=sc["scalar_cumulative"], average_reward=sc["scalar_average"])
     c = self._info
     return c["obs"], c["reward"], c["done"], self._never, dict(c["info"])
 

@@ -210,8 +210,12 @@ class GridworldZooParallelEnv(_Base):
     ds = {k: v[0].cpu().numpy() for k, v in self._env.engine.derived_stats().items()}    # computed on the device, numpy order
     cum = o["cumulative"].reshape(sp.A, sp.K)
     per = lambda f: {c: f(self._slots[i], len(sp.agent_dim_names[c])) for i, c in enumerate(sp.agent_chars)}
-    out["cumulative_reward"] = per(lambda q, k: cum[q, :k].astype(np.float64).copy())
-    out["average_reward"] = per(lambda q, k: ds["average_reward"][q, :k].astype(np.float64))
+    if self._env.scalarise:                  # np.float64 sums of each agent's dimensions (safety_game_moma.py:1253-1321), from the device
+      out["cumulative_reward"] = per(lambda q, k: np.float64(o["scalar_cumulative"].reshape(-1)[q]))
+      out["average_reward"] = per(lambda q, k: np.float64(o["scalar_average"].reshape(-1)[q]))
+    else:
+      out["cumulative_reward"] = per(lambda q, k: cum[q, :k].astype(np.float64).copy())
+      out["average_reward"] = per(lambda q, k: ds["average_reward"][q, :k].astype(np.float64))
     for key in ("gini_index", "cumulative_gini_index", "mo_variance", "cumulative_mo_variance", "average_mo_variance"):
       out[key] = per(lambda q, k, key=key: np.float64(ds[key][q]))
     metrics = o["metrics"].reshape(-1)[:sp.M]
@@ -344,7 +348,9 @@ class GridworldZooParallelEnv(_Base):
     rewards, dones = {}, {}
     for i, a in enumerate(self.possible_agents):
       done = int(st_all[self._slots[i] if per_agent else 0]) in (N.LAST, N.DEAD)
-      if self._ma:
+      if self._env.scalarise:                                                    # np.float64(sum(reward_dims)): what the Zoo API tester needs
+        r = 0.0 if first else np.float64(o["scalar_reward"].reshape(-1)[self._slots[i] if self._ma else 0])
+      elif self._ma:
         k = len(sp.agent_dim_names[sp.agent_chars[i]])
         r = 0.0 if first else o["reward"].reshape(sp.A, sp.K)[self._slots[i], :k].astype(np.float64).copy()
       elif sp.scalar:

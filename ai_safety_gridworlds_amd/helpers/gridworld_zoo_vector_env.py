@@ -9,7 +9,9 @@ What one env of the batch returns is what `GridworldZooParallelEnv` (the referen
 helpers/gridworld_zoo_parallel_env.py:429-615) returns for it:
   obs[agent]         the agent-centric window of the rendered board (get_agent_perspective, safety_game_moma.py:1996-2101):
                      ascii codes uint8 [N, h, w], or the value-mapped float32 board with ascii_observation_format=False
-  rewards[agent]     float64 [N, K_agent] in the agent's sorted reward-dimension order (0 at an auto-reset round)
+  rewards[agent]     float64 [N, K_agent] in the agent's sorted reward-dimension order (0 at an auto-reset round); with
+                     scalarise=True float64 [N], the reference's left-to-right sum over those dimensions (one more library call
+                     per round, sgw_scalarise), and infos[agent]["cumulative_reward"] / ["average_reward"] are [N] as well
   terminateds[agent] bool [N]: the agent's StepType is LAST or DEAD;  truncateds[agent]: all False
   infos[agent]       device tensors: "step_type" [N], "term_reason" uint8 [N] (255 until the episode is over), "cumulative_reward" [N, K_agent], "agent_position" [N, 2],
                      "discount" [N] (NaN = None), "metrics" [N, M], "board" uint8 [N, H, W] (the global board, shared),
@@ -45,7 +47,7 @@ class GridworldZooVectorEnv(object):
   metadata = {"name": "ai_safety_gridworlds_amd_vector"}
 
   def __init__(self, env_name, num_envs, ascii_observation_format=True, layers_in_observation=False, seed=None, device="cuda:0",
-               env_id_base=0, object_coordinates=False, coordinates_cap=None, episode_log=None, **kwargs):
+               env_id_base=0, object_coordinates=False, coordinates_cap=None, episode_log=None, scalarise=False, **kwargs):
     self._fused = fused_views(make_spec(env_name, **kwargs))
     self._ascii = bool(ascii_observation_format)
     cfg0 = getattr(make_spec(env_name, **kwargs), "config", None) or {}
@@ -53,7 +55,7 @@ class GridworldZooVectorEnv(object):
     # `terminated` and the decoded directions leave with the step launch (sgw_out.done / obs_dir / act_dir): no torch launch per step
     outs = OUTS + (("obs_dir", "act_dir") if self._turning else ()) + ((("views",) if self._ascii else ("obs_views",)) if self._fused else ())
     self._env = BatchedSafetyEnvironment(env_name, num_envs=num_envs, device=device, env_id_base=env_id_base, outputs=outs,
-                                         track_performance=False, episode_log=episode_log, **kwargs)
+                                         track_performance=False, episode_log=episode_log, scalarise=scalarise, **kwargs)
     self.episode_log = self._env.episode_log                   # episode_log=cap: an EpisodeLog every step appends to (None: no log)
     sp = self.spec_ = self._env.spec
     if sp.A < 2 and not getattr(sp, "per_agent", False):
@@ -109,6 +111,7 @@ class GridworldZooVectorEnv(object):
     sp = self.spec_
     n = self.num_envs
     eng = self._env.engine
+    sc = eng.scalarise() if self._env.scalarise else None      # scalarise=True: one more library call, into persistent tensors
     if getattr(self, "_packed_for", None) is not o.get("reward"):       # first call, or the engine reallocated its outputs
       self._packed_for = o.get("reward")
       if self._fused:                                              # the step launch wrote the windows (ascii or value-mapped)
@@ -137,6 +140,10 @@ class GridworldZooVectorEnv(object):
                     "metrics": metrics, "board": o["board"],
                     "observation_direction": self._odir[:, q] if self._turning else self._up,
                     "action_direction": self._adir[:, q] if self._turning else self._up}
+        if sc is not None:                                         # float64 [N] each: the sums over the agent's dimensions
+          rewards[a] = sc["scalar_reward"].reshape(n, sp.A)[:, q]
+          infos[a]["cumulative_reward"] = sc["scalar_cumulative"].reshape(n, sp.A)[:, q]
+          infos[a]["average_reward"] = sc["scalar_average"].reshape(n, sp.A)[:, q]
       self._cached = (obs, rewards, terms, truncs, infos)
     elif not self._fused:
       eng.agent_views(out=self._view_buf)

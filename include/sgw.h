@@ -312,6 +312,28 @@ int sgw_observe(sgw_engine* e, const uint8_t* board_dev, const uint8_t* rgb_lut_
 int sgw_derived_stats(sgw_engine* e, const double* reward_dev, const double* cumulative_dev, const int32_t* frame_dev,
                       const int32_t* k_agent, double* stats_dev, void* stream);
 
+/* scalarise=True of SafetyEnvironmentMo / SafetyEnvironmentMoMa (_process_timestep, safety_game_mo.py:1027-1066,
+ * safety_game_moma.py:1253-1321): the scalar reward, cumulative reward and average reward of a step's outputs, per env and agent,
+ * over the agent's k reward dimensions in the order of the output columns:
+ *   scalar_reward = sum(reward[0..k)), scalar_cumulative = sum(cumulative[0..k)),
+ *   scalar_average = sum(cumulative[i] / (double)(frame + 1)): the sum of k quotients, not the quotient of the sum.
+ * sum() is the reference's Python sum() over a list of floats as CPython <= 3.11 computes it: an accumulator that starts at +0.0,
+ * then one IEEE double addition per column, column 0 first (a row of -0.0 sums to +0.0; Python 3.12's compensated sum is NOT
+ * what this computes).  NaN and infinities pass through as IEEE arithmetic has them.
+ * Inputs: the `reward`, `cumulative` and `frame` outputs of a step, [T, N_pad, A, K], [T, N_pad, A, K] and [T, N_pad]; T == 1 is
+ * the plain layout, T > 1 the rollout-buffer layout of sgw_step_n / sgw_rollout / sgw_replay with write_every != 0.  Outputs:
+ * double [T, N_pad, A] each; any may be NULL.  Rows n >= N of each N_pad block are neither read nor written (the caller's bytes
+ * stay), so with T == 1 plain [N, ...] arrays do as well (the performance getters sum their [N, A, K] tensors this way).
+ * k_agent: HOST int32 [A], the number of reward dimensions of each agent (0 <= k <= K, as for sgw_derived_stats), read at call
+ * time; NULL = K for every agent.  An agent with k == 0 gets 0.0 in every output.
+ * SGW_ERR_ARG: a null engine; T < 1; a k_agent entry outside 0..K; all three outputs NULL; an output whose source is NULL
+ * (scalar_reward needs reward, scalar_cumulative needs cumulative, scalar_average needs cumulative and frame; a source that no
+ * requested output needs is not read and may be NULL); reward / cumulative not 16-byte aligned where they are read.
+ * One plain launch on the caller's stream: no allocation, no synchronisation, no read-back, capturable. */
+int sgw_scalarise(sgw_engine* e, const double* reward_dev, const double* cumulative_dev, const int32_t* frame_dev, int T,
+                  const int32_t* k_agent, double* scalar_reward_dev, double* scalar_cumulative_dev, double* scalar_average_dev,
+                  void* stream);
+
 /* Per-env performance bookkeeping of SafetyEnvironment{,Mo}: _episodic_performances.append(...) at every LAST timestep
  * (safety_game.py:253-263, 301-302; safety_game_mo.py:1015-1016), get_last_performance (229-251) and get_overall_performance =
  * sum(performances) / len(performances) (194-208, 234-244; safety_game_mo.py:917-938).  perf_dev double [N, C] is the step's
