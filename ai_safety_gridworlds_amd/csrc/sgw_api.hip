@@ -2,6 +2,7 @@
 // Thin by design: validates arguments, owns the engine's device state, launches k_engine<F>.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -57,6 +58,94 @@ static int fail(int code, const char* fmt, const char* detail = "") {
     }                                                                                    \
   } while (0)
 
+// ---- the graph cache of sgw_step_n, sgw_group_step_n and sgw_step_full ------------------------------------------------------
+// One host launch costs ~5 us of CPU on this runtime -- as much as the smaller families' whole step kernel, and three times
+// that for a mixed suite issued from one thread.  A caller that steps from the same device buffers again (the usual loop:
+// one actions buffer refilled in place) gets its launches captured into a hipGraph the second time the same arguments are
+// seen and replayed from then on.  SGW_STEP_GRAPHS=0 turns this off.
+static int step_graphs_min_T() {
+  static int v = -1;
+  if (v < 0) { const char* s = getenv("SGW_STEP_GRAPHS"); v = (s && atoi(s) == 0) ? (1 << 30) : 8; }
+  return v;
+}
+
+// What a call was made with, for N engines (1, or the members of a group).  epochs: the arg_epoch of every engine whose KArgs the
+// capture holds by value; they are no part of a key's identity (same()) but say whether the entry found under it is stale.
+template <int N> struct GraphKey {
+  const int8_t* actions[N];
+  sgw_out outs[N];
+  sgw_extras ex;                                // sgw_step_full
+  unsigned long long epochs[N];
+  int n, T, write_every, accumulate, has_out;
+  bool same(const GraphKey& o) const {
+    if (actions[0] != o.actions[0] || n != o.n || T != o.T || write_every != o.write_every || accumulate != o.accumulate ||
+        has_out != o.has_out) return false;
+    return memcmp(actions, o.actions, sizeof(actions[0]) * n) == 0 && memcmp(outs, o.outs, sizeof(sgw_out) * n) == 0 &&
+           memcmp(&ex, &o.ex, sizeof(ex)) == 0;
+  }
+};
+
+// what the caches of one owner (an engine, a group) share: the private stream captures are made on, the use counter
+struct GraphOwner { int device; hipStream_t capture_stream; long long tick; };
+
+template <int N> struct GraphCache {
+  struct Entry { GraphKey<N> key; long long nodes, last_use; hipGraphExec_t exec; };
+  size_t max_entries;
+  long long max_nodes;                          // kernel nodes of all entries together; 0: no such bound
+  const char* captured;                         // (error text) what a capture holds
+  std::vector<Entry> entries;
+
+  void clear() {
+    for (auto& g : entries) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    entries.clear();
+  }
+
+  // launches(stream) issues the call's launches; node_count: how many kernel nodes a capture of them holds
+  template <class L> int run(GraphOwner& own, const GraphKey<N>& key, long long node_count, L&& launches, hipStream_t st, const char* what) {
+    Entry* hit = nullptr;
+    for (auto& g : entries) if (g.key.same(key)) { hit = &g; break; }
+    if (!hit) {                                 // first sighting: remember the arguments, launch directly
+      // bounded: drop the least recently used captures
+      auto nodes = [&]() { long long n = node_count; for (auto& g : entries) n += g.nodes; return n; };
+      while (!entries.empty() && (entries.size() >= max_entries || (max_nodes && nodes() > max_nodes))) {
+        size_t worst = 0;
+        for (size_t i = 1; i < entries.size(); ++i) if (entries[i].last_use < entries[worst].last_use) worst = i;
+        if (entries[worst].exec) (void)hipGraphExecDestroy(entries[worst].exec);
+        entries.erase(entries.begin() + worst);
+      }
+      entries.push_back(Entry{key, node_count, ++own.tick, nullptr});
+      return launches(st);
+    }
+    hit->last_use = ++own.tick;
+    if (memcmp(hit->key.epochs, key.epochs, sizeof(key.epochs)) != 0) {      // a setter changed what the captured KArgs hold: seen anew, launch directly
+      if (hit->exec) (void)hipGraphExecDestroy(hit->exec);
+      hit->exec = nullptr;
+      memcpy(hit->key.epochs, key.epochs, sizeof(key.epochs));
+      return launches(st);
+    }
+    if (!hit->exec) {                           // second sighting: capture (on the owner's own stream; nothing executes) and instantiate
+      HIP_TRY(hipSetDevice(own.device));
+      if (!own.capture_stream) HIP_TRY(hipStreamCreateWithFlags(&own.capture_stream, hipStreamNonBlocking));
+      HIP_TRY(hipStreamBeginCapture(own.capture_stream, hipStreamCaptureModeThreadLocal));
+      const int rc = launches(own.capture_stream);
+      hipGraph_t graph = nullptr;
+      const hipError_t ec = hipStreamEndCapture(own.capture_stream, &graph);
+      if (rc || ec != hipSuccess || !graph) {
+        if (graph) (void)hipGraphDestroy(graph);
+        if (rc) return rc;
+        snprintf(g_err, sizeof(g_err), "%s: stream capture%s failed", what, captured);
+        return SGW_ERR_HIP;
+      }
+      const hipError_t ei = hipGraphInstantiate(&hit->exec, graph, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(graph);
+      if (ei != hipSuccess) { hit->exec = nullptr; return fail(SGW_ERR_HIP, "%s: hipGraphInstantiate failed", what); }
+    }
+    HIP_TRY(hipSetDevice(own.device));
+    HIP_TRY(hipGraphLaunch(hit->exec, st));
+    return SGW_OK;
+  }
+};
+
 struct sgw_engine {
   sgw_spec spec;
   KSpec ks;
@@ -74,28 +163,20 @@ struct sgw_engine {
   int rng_set;
   double* ftable_dev;      // sgw_set_family_table
   long long ftable_n;
-  // sgw_step_n: the T launches of one (actions, T, outputs) call, captured once and replayed as a hipGraph (see step_n_graph)
-  struct StepGraph { const int8_t* actions; int T, write_every, accumulate, has_out; long long last_use; sgw_out out; hipGraphExec_t exec; };
-  long long graph_tick;
-  std::vector<StepGraph> graphs;
-  hipStream_t capture_stream;
+  // sgw_step_n: the T launches of one (actions, T, outputs) call, captured once and replayed as a hipGraph: at most 256
+  // captures and 64 Ki kernel nodes in all.  sgw_step_full: one captured graph per (actions, out, extras) triple, at most 16
+  GraphOwner graph_owner;
+  GraphCache<1> graphs{256, 65536, " of the step launches"}, full_graphs{16, 0, ""};
   unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel, + 4 for the BigViews variant; bit 20 for a shaped kernel with compiled rules): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
   int step_shape;          // 1 + the ShapedSteps entry whose kernel runs this engine's one-step launches, 0 = the generic kernel
   int step_rules;          // 1: that entry's kernel with the spec's rule set compiled in runs them (ShapedStep::Rules), 0: the entry's own family
-  // sgw_step_full: one captured graph per (actions, out, extras) triple
-  struct FullGraph { const int8_t* actions; sgw_out out; sgw_extras ex; long long last_use; hipGraphExec_t exec; };
-  std::vector<FullGraph> full_graphs;
-  // bumped by drop_graphs: a group graph (sgw_group::Graph) records its members' epochs at capture and is stale once one moved
+  // bumped by drop_graphs: a cache entry records its engines' epochs when it is seen and is stale once one moved
   unsigned long long arg_epoch;
 };
 
-static void drop_graphs(sgw_engine* e) {      // any setter that changes what a launch's arguments hold invalidates the captures
-  ++e->arg_epoch;                             // (the groups' captures too: they hold this engine's KArgs by value)
-  for (auto& g : e->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  e->graphs.clear();
-  for (auto& g : e->full_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  e->full_graphs.clear();
-}
+// any setter that changes what a launch's arguments hold invalidates the captures, this engine's and those of the groups it is
+// a member of (they hold its KArgs by value): each is destroyed when its entry is next found (GraphCache::run)
+static void drop_graphs(sgw_engine* e) { ++e->arg_epoch; }
 
 static size_t acc_bytes(const sgw_engine* e) {              // [env-waves * parts][A*K+1] doubles
   return (size_t)(e->spec.A * e->spec.K + 1) * (size_t)(SGW_ACC_PER_ENV ? e->n_pad : e->n_pad / WAVE * SGW_ACC_PARTS) * 8;
@@ -122,6 +203,69 @@ static int family_words(const sgw_spec& sp) {
     case SGW_ROCKS_DIAMONDS: return Rocks::words();
     case SGW_AINTELOPE_SAVANNA: return Savanna::words(sp.K);
     default: return -1;
+  }
+}
+
+// step_type / term_reason / safety are [N_pad, A] for these families: the host's statement of the kernels' F::PER_AGENT
+static bool spec_per_agent(const sgw_spec& sp) { return sp.family == SGW_ISLAND_NAVIGATION_EX_MA || sp.family == SGW_AINTELOPE_SAVANNA; }
+static_assert(IslandMa::PER_AGENT && IslandMaWide::PER_AGENT && Savanna::PER_AGENT, "spec_per_agent names the families whose kernels write per-agent columns");
+static_assert(!Island::PER_AGENT && !Firemaker::PER_AGENT, "... and no other (firemaker_ex_ma has several agents and one column)");
+
+// The rows of the outputs, one entry per field of struct sgw_out in its order: the columns of one env's row (the element size
+// is the field's own).  offset_out and out_row_bytes (sgw_out_row_bytes, sgw_copy_envs) both evaluate it.
+//   HW board cells, AK reward columns, A agents, PA per-agent columns (spec_per_agent ? A : 1), A2 two per agent, M metrics,
+//   VB bytes of the agents' windows, ONE a scalar, SAV per-agent columns of aintelope_savanna and no such output elsewhere
+enum OutCols { OC_HW, OC_AK, OC_A, OC_PA, OC_A2, OC_M, OC_VB, OC_ONE, OC_SAV };
+#define SGW_OUT_FIELDS(X)                                                                                                    \
+  X(board, HW) X(obs_board, HW) X(reward, AK) X(cumulative, AK) X(step_type, A) X(term_reason, PA) X(actual_action, A)       \
+  X(discount, ONE) X(hidden, ONE) X(safety, PA) X(metrics, M) X(frame, ONE) X(agent_pos, A2) X(agent_flags, A)               \
+  X(safety2, SAV) X(views, VB) X(obs_views, VB) X(done, A) X(obs_dir, A) X(act_dir, A)
+struct OutField { int elem_bytes; OutCols cols; };
+#define SGW_OUT_ENTRY(name, cols) {(int)sizeof(*sgw_out{}.name), OC_##cols},
+static constexpr OutField OUT_FIELDS[] = {SGW_OUT_FIELDS(SGW_OUT_ENTRY)};
+#define SGW_OUT_INDEX(name, cols) OF_##name,
+enum { SGW_OUT_FIELDS(SGW_OUT_INDEX) OF_COUNT };
+#define SGW_OUT_PLACE(name, cols) static_assert(offsetof(sgw_out, name) == OF_##name * sizeof(void*), "OUT_FIELDS is in the order of struct sgw_out");
+SGW_OUT_FIELDS(SGW_OUT_PLACE)
+#undef SGW_OUT_ENTRY
+#undef SGW_OUT_INDEX
+#undef SGW_OUT_PLACE
+static_assert(OF_COUNT == COPY_PLANES && sizeof(sgw_out) == COPY_PLANES * sizeof(void*), "sgw_out is COPY_PLANES pointers: offset_out and sgw_copy_envs walk it as an array");
+
+static long long kspec_view_total(const sgw_spec& sp) {
+  long long off = 0;
+  for (int a = 0; a < sp.A; ++a) if (sp.view_radius[a][0] >= 0) off += (long long)(sp.view_radius[a][0] + sp.view_radius[a][1] + 1) * (sp.view_radius[a][2] + sp.view_radius[a][3] + 1);
+  return off;
+}
+
+// Bytes of one env's row of the field-th output of struct sgw_out (0: the family has no such output, negative: no such field)
+static long long out_row_bytes(const sgw_spec& sp, int field) {
+  if (field < 0 || field >= COPY_PLANES) return -1;
+  const long long A = sp.A, PA = spec_per_agent(sp) ? A : 1;
+  long long cols = 0;
+  switch (OUT_FIELDS[field].cols) {
+    case OC_HW: cols = sp.H * sp.W; break;
+    case OC_AK: cols = A * sp.K; break;
+    case OC_A: cols = A; break;
+    case OC_PA: cols = PA; break;
+    case OC_A2: cols = A * 2; break;
+    case OC_M: cols = sp.M; break;
+    case OC_VB: cols = kspec_view_total(sp); break;
+    case OC_ONE: cols = 1; break;
+    case OC_SAV: cols = sp.family == SGW_AINTELOPE_SAVANNA ? PA : 0; break;
+  }
+  return cols * OUT_FIELDS[field].elem_bytes;
+}
+
+// step t of a [T, N_pad, ...] buffer of every output that is set.  (safety2 outside aintelope_savanna does not move: its row is
+// 0 bytes there, and no launch sees it -- prepare_args refuses that output.)
+static void offset_out(sgw_out& o, const sgw_spec& sp, long long n_pad, long long t) {
+  for (int f = 0; f < COPY_PLANES; ++f) {
+    char* p;
+    memcpy(&p, reinterpret_cast<char*>(&o) + f * sizeof(p), sizeof(p));
+    if (!p) continue;
+    p += t * n_pad * out_row_bytes(sp, f);
+    memcpy(reinterpret_cast<char*>(&o) + f * sizeof(p), &p, sizeof(p));
   }
 }
 
@@ -208,7 +352,7 @@ int sgw_create(const sgw_spec* spec, int64_t n_envs, int64_t env_id_base, int de
   e->n_envs = n_envs;
   e->n_pad = (n_envs + SGW_ENV_ALIGN - 1) / SGW_ENV_ALIGN * SGW_ENV_ALIGN;
   e->env_id_base = env_id_base;
-  e->ep_bits = nullptr; e->ep_bits_n = 0; e->ep_seed = 0; e->rand_stream = nullptr; e->rand_n = 0; e->rand_seed = 0; e->acc_dev = nullptr; e->rng_set = 0; e->ftable_dev = nullptr; e->ftable_n = 0; e->capture_stream = nullptr; e->graph_tick = 0; e->lds_cap_raised = 0; e->arg_epoch = 0;
+  e->ep_bits = nullptr; e->ep_bits_n = 0; e->ep_seed = 0; e->rand_stream = nullptr; e->rand_n = 0; e->rand_seed = 0; e->acc_dev = nullptr; e->rng_set = 0; e->ftable_dev = nullptr; e->ftable_n = 0; e->graph_owner = GraphOwner{device, nullptr, 0}; e->lds_cap_raised = 0; e->arg_epoch = 0;
 
   KSpec& k = e->ks;
   memset(&k, 0, sizeof(k));
@@ -278,8 +422,9 @@ int sgw_create(const sgw_spec* spec, int64_t n_envs, int64_t env_id_base, int de
 
 int sgw_destroy(sgw_engine* e) {
   if (!e) return SGW_OK;
-  drop_graphs(e);
-  if (e->capture_stream) (void)hipStreamDestroy(e->capture_stream);
+  e->graphs.clear();
+  e->full_graphs.clear();
+  if (e->graph_owner.capture_stream) (void)hipStreamDestroy(e->graph_owner.capture_stream);
   if (e->tables_dev) (void)hipFree(e->tables_dev);
   if (e->state_dev) (void)hipFree(e->state_dev);
   if (e->acc_dev) (void)hipFree(e->acc_dev);
@@ -404,11 +549,6 @@ int sgw_pow_f64(const double* x_dev, double y, double* out_dev, int64_t n, int d
   return SGW_OK;
 }
 
-// (the accumulators are allocated and zeroed by sgw_create: nothing is allocated on the step path)
-static int ensure_acc(sgw_engine* e, hipStream_t) {
-  return e->acc_dev ? SGW_OK : fail(SGW_ERR_ARG, "the engine's return accumulators are missing");
-}
-
 }  // extern "C"
 
 // ---- launch planning: the same validation and LDS / grid arithmetic for a family's own launch and for a group member ------
@@ -506,6 +646,19 @@ static int prepare_args(sgw_engine* e, KArgs& a) {
   a.n_pad = e->n_pad; a.n_envs = e->n_envs; a.env_id_base = e->env_id_base;
   a.ep_bits = e->ep_bits; a.ep_bits_n = e->ep_bits_n; a.ep_seed = e->ep_seed;
   a.rand_stream = e->rand_stream; a.rand_n = e->rand_n; a.rand_seed = e->rand_seed;
+  return SGW_OK;
+}
+
+// The caller's part of the arguments of T steps in one launch: from `actions` ([T, N, A]), or, without, from the in-kernel
+// stream of (seed, step0).  accumulate: finished episodes' returns go to the engine's accumulators (allocated and zeroed by
+// sgw_create: nothing is allocated on the step path).
+static int step_args(sgw_engine* e, const int8_t* actions, int T, uint64_t seed, int64_t step0, int write_every, const sgw_out* out,
+                     int accumulate, KArgs& a) {
+  if (accumulate && !e->acc_dev) return fail(SGW_ERR_ARG, "the engine's return accumulators are missing");
+  memset(&a, 0, sizeof(a));
+  a.mode = MODE_STEP; a.actions = actions; a.T = T; a.seed = seed; a.step0 = step0;
+  a.write_every = write_every; a.ep_acc = accumulate ? e->acc_dev : nullptr;
+  if (out) a.out = *out;
   return SGW_OK;
 }
 
@@ -622,17 +775,17 @@ extern "C" {
 
 int sgw_reset(sgw_engine* e, const uint8_t* mask_dev, const sgw_out* out, void* stream) {
   if (!e) return fail(SGW_ERR_ARG, "sgw_reset: null engine");
-  KArgs a; memset(&a, 0, sizeof(a));
-  a.mode = MODE_RESET; a.mask = mask_dev; a.T = 1;
-  if (out) a.out = *out;
+  KArgs a;
+  (void)step_args(e, nullptr, 1, 0, 0, 0, out, 0, a);
+  a.mode = MODE_RESET; a.mask = mask_dev;
   return launch(e, a, (hipStream_t)stream);
 }
 
 int64_t sgw_step_lds_bytes(sgw_engine* e, const sgw_out* out) {
   if (!e) return fail(SGW_ERR_ARG, "sgw_step_lds_bytes: null engine");
-  KArgs a; memset(&a, 0, sizeof(a));
-  a.mode = MODE_STEP; a.T = 1; a.sp = e->ks;
-  if (out) a.out = *out;
+  KArgs a;
+  (void)step_args(e, nullptr, 1, 0, 0, 0, out, 0, a);
+  a.sp = e->ks;
   const bool big = (a.out.views || a.out.obs_views) && e->ks.view_prefill;
   LaunchPlan p{};
   const int rc = with_family(e, [&](auto ft, int) {
@@ -647,64 +800,22 @@ int64_t sgw_step_lds_bytes(sgw_engine* e, const sgw_out* out) {
 int sgw_step(sgw_engine* e, const int8_t* actions_dev, const sgw_out* out, void* stream) {
   if (!e) return fail(SGW_ERR_ARG, "sgw_step: null engine");
   if (!actions_dev) return fail(SGW_ERR_ARG, "sgw_step: null actions");
-  KArgs a; memset(&a, 0, sizeof(a));
-  a.mode = MODE_STEP; a.actions = actions_dev; a.T = 1;
-  if (out) a.out = *out;
+  KArgs a;
+  (void)step_args(e, actions_dev, 1, 0, 0, 0, out, 0, a);
   return launch(e, a, (hipStream_t)stream);
-}
-
-static long long kspec_view_total(const sgw_spec& sp) {
-  long long off = 0;
-  for (int a = 0; a < sp.A; ++a) if (sp.view_radius[a][0] >= 0) off += (long long)(sp.view_radius[a][0] + sp.view_radius[a][1] + 1) * (sp.view_radius[a][2] + sp.view_radius[a][3] + 1);
-  return off;
-}
-static void offset_out(sgw_out& o, const sgw_spec& sp, long long n_pad, long long t) {
-  const long long HW = sp.H * sp.W, AK = sp.A * sp.K, A = sp.A, M = sp.M, r = t * n_pad;
-  const long long PA = (sp.family == SGW_ISLAND_NAVIGATION_EX_MA || sp.family == SGW_AINTELOPE_SAVANNA) ? A : 1;   // term_reason / safety are [N_pad, A] there (IslandMa::PER_AGENT)
-  if (o.board) o.board += r * HW;
-  if (o.obs_board) o.obs_board += r * HW;
-  if (o.reward) o.reward += r * AK;
-  if (o.cumulative) o.cumulative += r * AK;
-  if (o.step_type) o.step_type += r * A;
-  if (o.term_reason) o.term_reason += r * PA;
-  if (o.actual_action) o.actual_action += r * A;
-  if (o.discount) o.discount += r;
-  if (o.hidden) o.hidden += r;
-  if (o.safety) o.safety += r * PA;
-  if (o.safety2) o.safety2 += r * PA;
-  if (o.metrics) o.metrics += r * M;
-  if (o.frame) o.frame += r;
-  if (o.agent_pos) o.agent_pos += r * A * 2;
-  if (o.agent_flags) o.agent_flags += r * A;
-  if (o.done) o.done += r * A;
-  if (o.obs_dir) o.obs_dir += r * A;
-  if (o.act_dir) o.act_dir += r * A;
-  const long long VB = kspec_view_total(sp);
-  if (o.views) o.views += r * VB;
-  if (o.obs_views) o.obs_views += r * VB;
 }
 
 static int step_n_launches(sgw_engine* e, const int8_t* actions_dev, int T, int write_every, const sgw_out* out,
                            int accumulate, hipStream_t st) {
   for (int t = 0; t < T; ++t) {
-    KArgs a; memset(&a, 0, sizeof(a));
-    a.mode = MODE_STEP; a.T = 1; a.ep_acc = accumulate ? e->acc_dev : nullptr;
-    a.actions = actions_dev + (long long)t * e->n_envs * e->spec.A;
-    if (out) { a.out = *out; if (write_every) offset_out(a.out, e->spec, e->n_pad, t); }
-    int rc = launch(e, a, st);
+    KArgs a;
+    int rc = step_args(e, actions_dev + (long long)t * e->n_envs * e->spec.A, 1, 0, 0, 0, out, accumulate, a);
+    if (rc) return rc;
+    if (out && write_every) offset_out(a.out, e->spec, e->n_pad, t);
+    rc = launch(e, a, st);
     if (rc) return rc;
   }
   return SGW_OK;
-}
-
-// One host launch costs ~5 us of CPU on this runtime -- as much as the smaller families' whole step kernel, and three times
-// that for a mixed suite issued from one thread.  A caller that steps from the same device buffers again (the usual loop:
-// one actions buffer refilled in place) gets its T launches captured into a hipGraph the second time the same arguments are
-// seen and replayed from then on.  SGW_STEP_GRAPHS=0 turns this off.
-static int step_graphs_min_T() {
-  static int v = -1;
-  if (v < 0) { const char* s = getenv("SGW_STEP_GRAPHS"); v = (s && atoi(s) == 0) ? (1 << 30) : 8; }
-  return v;
 }
 
 int sgw_step_n(sgw_engine* e, const int8_t* actions_dev, int T, int write_every, const sgw_out* out,
@@ -712,49 +823,13 @@ int sgw_step_n(sgw_engine* e, const int8_t* actions_dev, int T, int write_every,
   if (!e) return fail(SGW_ERR_ARG, "sgw_step_n: null engine");
   if (!actions_dev || T < 1) return fail(SGW_ERR_ARG, "sgw_step_n: bad argument");
   const hipStream_t st = (hipStream_t)stream;
-  if (accumulate) { int rc = ensure_acc(e, st); if (rc) return rc; }
-  if (T < step_graphs_min_T()) return step_n_launches(e, actions_dev, T, write_every, out, accumulate, st);
-  sgw_out key_out; memset(&key_out, 0, sizeof(key_out));
-  if (out) key_out = *out;
-  sgw_engine::StepGraph* hit = nullptr;
-  for (auto& g : e->graphs)
-    if (g.actions == actions_dev && g.T == T && g.write_every == (write_every != 0) && g.accumulate == (accumulate != 0) &&
-        g.has_out == (out != nullptr) && memcmp(&g.out, &key_out, sizeof(key_out)) == 0) { hit = &g; break; }
-  if (!hit) {                                   // first sighting: remember the arguments, launch directly
-    // bounded (256 captures, 64 Ki kernel nodes in all): drop the least recently used captures
-    auto nodes = [&]() { long long n = T; for (auto& g : e->graphs) n += g.T; return n; };
-    while (!e->graphs.empty() && (e->graphs.size() >= 256 || nodes() > 65536)) {
-      size_t worst = 0;
-      for (size_t i = 1; i < e->graphs.size(); ++i) if (e->graphs[i].last_use < e->graphs[worst].last_use) worst = i;
-      if (e->graphs[worst].exec) (void)hipGraphExecDestroy(e->graphs[worst].exec);
-      e->graphs.erase(e->graphs.begin() + worst);
-    }
-    sgw_engine::StepGraph g; memset(&g, 0, sizeof(g));
-    g.actions = actions_dev; g.T = T; g.write_every = write_every != 0; g.accumulate = accumulate != 0; g.has_out = out != nullptr;
-    g.out = key_out; g.exec = nullptr; g.last_use = ++e->graph_tick;
-    e->graphs.push_back(g);
-    return step_n_launches(e, actions_dev, T, write_every, out, accumulate, st);
-  }
-  hit->last_use = ++e->graph_tick;
-  if (!hit->exec) {                             // second sighting: capture (on the engine's own stream; nothing executes) and instantiate
-    HIP_TRY(hipSetDevice(e->device));
-    if (!e->capture_stream) HIP_TRY(hipStreamCreateWithFlags(&e->capture_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamBeginCapture(e->capture_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = step_n_launches(e, actions_dev, T, write_every, out, accumulate, e->capture_stream);
-    hipGraph_t graph = nullptr;
-    const hipError_t ec = hipStreamEndCapture(e->capture_stream, &graph);
-    if (rc || ec != hipSuccess || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      if (rc) return rc;
-      return fail(SGW_ERR_HIP, "sgw_step_n: stream capture of the step launches failed");
-    }
-    const hipError_t ei = hipGraphInstantiate(&hit->exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ei != hipSuccess) { hit->exec = nullptr; return fail(SGW_ERR_HIP, "sgw_step_n: hipGraphInstantiate failed"); }
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipGraphLaunch(hit->exec, st));
-  return SGW_OK;
+  auto launches = [&](hipStream_t s) { return step_n_launches(e, actions_dev, T, write_every, out, accumulate, s); };
+  if (T < step_graphs_min_T()) return launches(st);
+  GraphKey<1> key; memset(&key, 0, sizeof(key));
+  key.actions[0] = actions_dev; key.epochs[0] = e->arg_epoch;
+  key.n = 1; key.T = T; key.write_every = write_every != 0; key.accumulate = accumulate != 0; key.has_out = out != nullptr;
+  if (out) key.outs[0] = *out;
+  return e->graphs.run(e->graph_owner, key, T, launches, st, "sgw_step_n");
 }
 
 }  // extern "C"
@@ -764,11 +839,9 @@ struct sgw_group {
   std::vector<sgw_engine*> members;
   int device;
   unsigned lds_cap_raised;
-  // epochs: the members' arg_epoch when the graph was seen; a member setter since then makes the capture stale
-  struct Graph { std::vector<const int8_t*> actions; std::vector<sgw_out> outs; std::vector<unsigned long long> epochs; int T, write_every, accumulate, has_out; long long last_use; hipGraphExec_t exec; };
-  std::vector<Graph> graphs;
-  long long graph_tick;
-  hipStream_t capture_stream;
+  // sgw_group_step_n: at most 64 captures (a key records every member's arg_epoch: a member setter makes them stale)
+  GraphOwner graph_owner;
+  GraphCache<GROUP_MAX> graphs{64, 0, " of the step launches"};
 };
 
 static bool group_tag(int tag) {
@@ -822,10 +895,9 @@ static int group_step_launches(sgw_group* g, const int8_t* const* actions, int T
   for (int t = 0; t < T; ++t) {
     for (size_t m = 0; m < n; ++m) {
       sgw_engine* e = g->members[m];
-      memset(&a[m], 0, sizeof(KArgs));
-      a[m].mode = MODE_STEP; a[m].T = 1; a[m].ep_acc = accumulate ? e->acc_dev : nullptr;
-      a[m].actions = actions[m] + (long long)t * e->n_envs * e->spec.A;
-      if (outs) { a[m].out = outs[m]; if (write_every) offset_out(a[m].out, e->spec, e->n_pad, t); }
+      int rc = step_args(e, actions[m] + (long long)t * e->n_envs * e->spec.A, 1, 0, 0, 0, outs ? &outs[m] : nullptr, accumulate, a[m]);
+      if (rc) return rc;
+      if (outs && write_every) offset_out(a[m].out, e->spec, e->n_pad, t);
     }
     int rc = group_launch<K_STEP>(g, a, st);
     if (rc) return rc;
@@ -849,15 +921,15 @@ int sgw_group_create(sgw_engine* const* engines, int n, sgw_group** out_group) {
   sgw_group* g = new (std::nothrow) sgw_group();
   if (!g) return fail(SGW_ERR_NOMEM, "sgw_group_create: out of host memory");
   g->members.assign(engines, engines + n);
-  g->device = engines[0]->device; g->lds_cap_raised = 0; g->graph_tick = 0; g->capture_stream = nullptr;
+  g->device = engines[0]->device; g->lds_cap_raised = 0; g->graph_owner = GraphOwner{g->device, nullptr, 0};
   *out_group = g;
   return SGW_OK;
 }
 
 int sgw_group_destroy(sgw_group* g) {
   if (!g) return SGW_OK;
-  for (auto& gr : g->graphs) if (gr.exec) (void)hipGraphExecDestroy(gr.exec);
-  if (g->capture_stream) (void)hipStreamDestroy(g->capture_stream);
+  g->graphs.clear();
+  if (g->graph_owner.capture_stream) (void)hipStreamDestroy(g->graph_owner.capture_stream);
   delete g;
   return SGW_OK;
 }
@@ -867,62 +939,17 @@ int sgw_group_step_n(sgw_group* g, const int8_t* const* actions_dev, int T, int 
   if (!g || !actions_dev || T < 1) return fail(SGW_ERR_ARG, "sgw_group_step_n: bad argument");
   const hipStream_t st = (hipStream_t)stream;
   const size_t n = g->members.size();
-  for (size_t m = 0; m < n; ++m) {
-    if (!actions_dev[m]) return fail(SGW_ERR_ARG, "sgw_group_step_n: null actions");
-    if (accumulate) { int rc = ensure_acc(g->members[m], st); if (rc) return rc; }
-  }
+  for (size_t m = 0; m < n; ++m) if (!actions_dev[m]) return fail(SGW_ERR_ARG, "sgw_group_step_n: null actions");
   HIP_TRY(hipSetDevice(g->device));
-  if (T < step_graphs_min_T()) return group_step_launches(g, actions_dev, T, write_every, outs, accumulate, st);
-  sgw_group::Graph* hit = nullptr;
-  for (auto& gr : g->graphs) {
-    if (gr.T != T || gr.write_every != (write_every != 0) || gr.accumulate != (accumulate != 0) || gr.has_out != (outs != nullptr)) continue;
-    bool same = true;
-    for (size_t m = 0; m < n && same; ++m)
-      same = gr.actions[m] == actions_dev[m] && (!outs || memcmp(&gr.outs[m], &outs[m], sizeof(sgw_out)) == 0);
-    if (same) { hit = &gr; break; }
+  auto launches = [&](hipStream_t s) { return group_step_launches(g, actions_dev, T, write_every, outs, accumulate, s); };
+  if (T < step_graphs_min_T()) return launches(st);
+  GraphKey<GROUP_MAX> key; memset(&key, 0, sizeof(key));
+  for (size_t m = 0; m < n; ++m) {
+    key.actions[m] = actions_dev[m]; key.epochs[m] = g->members[m]->arg_epoch;
+    if (outs) key.outs[m] = outs[m];
   }
-  if (!hit) {                                   // first sighting: remember, launch directly (as sgw_step_n does)
-    while (g->graphs.size() >= 64) {
-      size_t worst = 0;
-      for (size_t i = 1; i < g->graphs.size(); ++i) if (g->graphs[i].last_use < g->graphs[worst].last_use) worst = i;
-      if (g->graphs[worst].exec) (void)hipGraphExecDestroy(g->graphs[worst].exec);
-      g->graphs.erase(g->graphs.begin() + worst);
-    }
-    sgw_group::Graph gr;
-    gr.actions.assign(actions_dev, actions_dev + n);
-    if (outs) gr.outs.assign(outs, outs + n);
-    for (sgw_engine* e : g->members) gr.epochs.push_back(e->arg_epoch);
-    gr.T = T; gr.write_every = write_every != 0; gr.accumulate = accumulate != 0; gr.has_out = outs != nullptr;
-    gr.last_use = ++g->graph_tick; gr.exec = nullptr;
-    g->graphs.push_back(gr);
-    return group_step_launches(g, actions_dev, T, write_every, outs, accumulate, st);
-  }
-  hit->last_use = ++g->graph_tick;
-  bool stale = false;
-  for (size_t m = 0; m < n; ++m) stale |= hit->epochs[m] != g->members[m]->arg_epoch;
-  if (stale) {                                  // a member setter changed what the captured KArgs hold: seen anew, launch directly
-    if (hit->exec) (void)hipGraphExecDestroy(hit->exec);
-    hit->exec = nullptr;
-    for (size_t m = 0; m < n; ++m) hit->epochs[m] = g->members[m]->arg_epoch;
-    return group_step_launches(g, actions_dev, T, write_every, outs, accumulate, st);
-  }
-  if (!hit->exec) {
-    if (!g->capture_stream) HIP_TRY(hipStreamCreateWithFlags(&g->capture_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamBeginCapture(g->capture_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = group_step_launches(g, actions_dev, T, write_every, outs, accumulate, g->capture_stream);
-    hipGraph_t graph = nullptr;
-    const hipError_t ec = hipStreamEndCapture(g->capture_stream, &graph);
-    if (rc || ec != hipSuccess || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      if (rc) return rc;
-      return fail(SGW_ERR_HIP, "sgw_group_step_n: stream capture of the step launches failed");
-    }
-    const hipError_t ei = hipGraphInstantiate(&hit->exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ei != hipSuccess) { hit->exec = nullptr; return fail(SGW_ERR_HIP, "sgw_group_step_n: hipGraphInstantiate failed"); }
-  }
-  HIP_TRY(hipGraphLaunch(hit->exec, st));
-  return SGW_OK;
+  key.n = (int)n; key.T = T; key.write_every = write_every != 0; key.accumulate = accumulate != 0; key.has_out = outs != nullptr;
+  return g->graphs.run(g->graph_owner, key, T, launches, st, "sgw_group_step_n");
 }
 
 int sgw_group_rollout(sgw_group* g, int T, uint64_t seed, int64_t step0, int write_every, const sgw_out* outs, int accumulate,
@@ -934,11 +961,8 @@ int sgw_group_rollout(sgw_group* g, int T, uint64_t seed, int64_t step0, int wri
   for (size_t m = 0; m < n; ++m) {
     sgw_engine* e = g->members[m];
     if (e->spec.n_actions < 1) return fail(SGW_ERR_ARG, "sgw_group_rollout: spec has no action range");
-    if (accumulate) { int rc = ensure_acc(e, st); if (rc) return rc; }
-    memset(&a[m], 0, sizeof(KArgs));
-    a[m].mode = MODE_STEP; a[m].actions = nullptr; a[m].T = T; a[m].seed = seed; a[m].step0 = step0;
-    a[m].write_every = write_every; a[m].ep_acc = accumulate ? e->acc_dev : nullptr;
-    if (outs) a[m].out = outs[m];
+    int rc = step_args(e, nullptr, T, seed, step0, write_every, outs ? &outs[m] : nullptr, accumulate, a[m]);
+    if (rc) return rc;
   }
   HIP_TRY(hipSetDevice(g->device));
   return group_launch<K_ROLLOUT>(g, a, st);
@@ -946,8 +970,6 @@ int sgw_group_rollout(sgw_group* g, int T, uint64_t seed, int64_t step0, int wri
 
 int sgw_read_returns(sgw_engine* e, double* out_dev, int clear, void* stream) {
   if (!e || !out_dev) return fail(SGW_ERR_ARG, "sgw_read_returns: null argument");
-  int rc = ensure_acc(e, (hipStream_t)stream);
-  if (rc) return rc;
   hipLaunchKernelGGL(k_read_returns, dim3(e->spec.A * e->spec.K + 1), dim3(256), 0, (hipStream_t)stream, e->acc_dev,
                      SGW_ACC_PER_ENV ? e->n_pad : e->n_pad / WAVE * SGW_ACC_PARTS, e->spec.A * e->spec.K + 1, out_dev, clear);
   HIP_TRY(hipGetLastError());
@@ -959,23 +981,17 @@ int sgw_rollout(sgw_engine* e, int T, uint64_t seed, int64_t step0, int write_ev
   if (!e) return fail(SGW_ERR_ARG, "sgw_rollout: null engine");
   if (T < 1) return fail(SGW_ERR_ARG, "sgw_rollout: T must be >= 1");
   if (e->spec.n_actions < 1) return fail(SGW_ERR_ARG, "sgw_rollout: spec has no action range");
-  KArgs a; memset(&a, 0, sizeof(a));
-  a.mode = MODE_STEP; a.actions = nullptr; a.T = T; a.seed = seed; a.step0 = step0;
-  if (accumulate) { int rc = ensure_acc(e, (hipStream_t)stream); if (rc) return rc; }
-  a.write_every = write_every; a.ep_acc = accumulate ? e->acc_dev : nullptr;
-  if (out) a.out = *out;
-  return launch(e, a, (hipStream_t)stream);
+  KArgs a;
+  int rc = step_args(e, nullptr, T, seed, step0, write_every, out, accumulate, a);
+  return rc ? rc : launch(e, a, (hipStream_t)stream);
 }
 
 int sgw_replay(sgw_engine* e, const int8_t* actions_dev, int T, int write_every, const sgw_out* out, int accumulate, void* stream) {
   if (!e) return fail(SGW_ERR_ARG, "sgw_replay: null engine");
   if (!actions_dev || T < 1) return fail(SGW_ERR_ARG, "sgw_replay: bad argument");
-  KArgs a; memset(&a, 0, sizeof(a));
-  a.mode = MODE_STEP; a.actions = actions_dev; a.T = T;
-  if (accumulate) { int rc = ensure_acc(e, (hipStream_t)stream); if (rc) return rc; }
-  a.write_every = write_every; a.ep_acc = accumulate ? e->acc_dev : nullptr;
-  if (out) a.out = *out;
-  return launch(e, a, (hipStream_t)stream);
+  KArgs a;
+  int rc = step_args(e, actions_dev, T, 0, 0, write_every, out, accumulate, a);
+  return rc ? rc : launch(e, a, (hipStream_t)stream);
 }
 
 int sgw_fill_actions(sgw_engine* e, int T, uint64_t seed, int64_t step0, int8_t* actions_dev, void* stream) {
@@ -1289,7 +1305,7 @@ int sgw_track_performance(sgw_engine* e, const double* perf_dev, int n_cols, con
   if (!e || !perf_dev || !step_type_dev || n_cols < 1) return fail(SGW_ERR_ARG, "sgw_track_performance: bad argument");
   HIP_TRY(hipSetDevice(e->device));
   const long long total = e->n_envs * n_cols;
-  const int per_agent = (e->spec.family == SGW_ISLAND_NAVIGATION_EX_MA || e->spec.family == SGW_AINTELOPE_SAVANNA) ? 1 : 0;
+  const int per_agent = spec_per_agent(e->spec) ? 1 : 0;
   hipLaunchKernelGGL(k_track_performance, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, perf_dev, n_cols,
                      step_type_dev, e->spec.A, per_agent, (long long)e->n_envs, last_dev, sum_dev, reinterpret_cast<long long*>(count_dev), done_dev);
   HIP_TRY(hipGetLastError());
@@ -1330,7 +1346,7 @@ int sgw_log_episodes(sgw_engine* e, const sgw_out* src, int T, int64_t step_base
   x.metrics = reinterpret_cast<const unsigned long long*>(src->metrics);
   x.n = e->n_envs; x.n_pad = e->n_pad; x.step_base = step_base;
   x.tiles = (unsigned)tiles; x.tiles_per_t = (unsigned)(e->n_pad / WAVE);
-  x.A = sp.A; x.per_agent = (sp.family == SGW_ISLAND_NAVIGATION_EX_MA || sp.family == SGW_AINTELOPE_SAVANNA) ? 1 : 0;
+  x.A = sp.A; x.per_agent = spec_per_agent(sp) ? 1 : 0;
   x.R = x.per_agent ? sp.A : 1; x.C = sp.A * sp.K; x.M = sp.M;
   x.recip_C = x.C <= 1 ? 0 : (int)(uint32_t)(((1ull << 32) + x.C - 1) / x.C);      // exact: a span has at most 64 * C elements
   x.recip_M = x.M <= 1 ? 0 : (int)(uint32_t)(((1ull << 32) + x.M - 1) / x.M);
@@ -1373,7 +1389,7 @@ static int step_extras_launch(sgw_engine* e, const sgw_out* out, const sgw_extra
   }
   if (perf) {
     ea.perf = x->perf_from_hidden ? out->hidden : out->cumulative; ea.perf_cols = x->perf_from_hidden ? 1 : A * K;
-    ea.per_agent = (e->spec.family == SGW_ISLAND_NAVIGATION_EX_MA || e->spec.family == SGW_AINTELOPE_SAVANNA) ? 1 : 0;
+    ea.per_agent = spec_per_agent(e->spec) ? 1 : 0;
     ea.step_type = out->step_type; ea.last = x->perf_last; ea.sum = x->perf_sum; ea.count = reinterpret_cast<long long*>(x->perf_count); ea.done = x->done;
   }
   // LDS: boards | layer masks | per-cell + per-char tables | colour table
@@ -1420,45 +1436,12 @@ int sgw_step_full(sgw_engine* e, const int8_t* actions_dev, const sgw_out* out, 
     if ((x->perf_last || x->perf_sum || x->perf_count || x->done) && (!out->step_type || !(x->perf_from_hidden ? (const void*)out->hidden : (const void*)out->cumulative)))
       return fail(SGW_ERR_ARG, "sgw_step_full: performance bookkeeping needs step_type and the cumulative (or hidden) output");
   }
-  const hipStream_t st = (hipStream_t)stream;
-  sgw_extras key_x; memset(&key_x, 0, sizeof(key_x));
-  if (x) key_x = *x;
-  if (!x || !x->replay || step_graphs_min_T() > 8) return step_full_launches(e, actions_dev, out, x, stream);     // (SGW_STEP_GRAPHS=0: never replay)
-  sgw_engine::FullGraph* hit = nullptr;
-  for (auto& g : e->full_graphs)
-    if (g.actions == actions_dev && memcmp(&g.out, out, sizeof(sgw_out)) == 0 && memcmp(&g.ex, &key_x, sizeof(key_x)) == 0) { hit = &g; break; }
-  if (!hit) {
-    while (e->full_graphs.size() >= 16) {
-      size_t worst = 0;
-      for (size_t i = 1; i < e->full_graphs.size(); ++i) if (e->full_graphs[i].last_use < e->full_graphs[worst].last_use) worst = i;
-      if (e->full_graphs[worst].exec) (void)hipGraphExecDestroy(e->full_graphs[worst].exec);
-      e->full_graphs.erase(e->full_graphs.begin() + worst);
-    }
-    sgw_engine::FullGraph g; memset(&g, 0, sizeof(g));
-    g.actions = actions_dev; g.out = *out; g.ex = key_x; g.last_use = ++e->graph_tick; g.exec = nullptr;
-    e->full_graphs.push_back(g);
-    return step_full_launches(e, actions_dev, out, x, stream);
-  }
-  hit->last_use = ++e->graph_tick;
-  if (!hit->exec) {
-    HIP_TRY(hipSetDevice(e->device));
-    if (!e->capture_stream) HIP_TRY(hipStreamCreateWithFlags(&e->capture_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamBeginCapture(e->capture_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = step_full_launches(e, actions_dev, out, x, e->capture_stream);
-    hipGraph_t graph = nullptr;
-    const hipError_t ec = hipStreamEndCapture(e->capture_stream, &graph);
-    if (rc || ec != hipSuccess || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      if (rc) return rc;
-      return fail(SGW_ERR_HIP, "sgw_step_full: stream capture failed");
-    }
-    const hipError_t ei = hipGraphInstantiate(&hit->exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ei != hipSuccess) { hit->exec = nullptr; return fail(SGW_ERR_HIP, "sgw_step_full: hipGraphInstantiate failed"); }
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipGraphLaunch(hit->exec, st));
-  return SGW_OK;
+  auto launches = [&](hipStream_t s) { return step_full_launches(e, actions_dev, out, x, s); };
+  if (!x || !x->replay || step_graphs_min_T() > 8) return launches((hipStream_t)stream);     // (SGW_STEP_GRAPHS=0: never replay)
+  GraphKey<1> key; memset(&key, 0, sizeof(key));
+  key.actions[0] = actions_dev; key.outs[0] = *out; key.ex = *x; key.epochs[0] = e->arg_epoch;
+  key.n = 1; key.T = 1; key.has_out = 1;
+  return e->full_graphs.run(e->graph_owner, key, 1, launches, (hipStream_t)stream, "sgw_step_full");
 }
 
 int sgw_get_state(sgw_engine* e, uint64_t* state_dev, void* stream) {
@@ -1481,35 +1464,6 @@ int sgw_set_state(sgw_engine* e, const uint64_t* state_dev, void* stream) {
   e->rng_set = 1;          // a saved state carries its envs' generator streams (resume needs no sgw_set_rng_state)
   return SGW_OK;
 }
-
-// Bytes of one env's row of the field-th output of struct sgw_out (0: the family has no such output): the strides of
-// offset_out, as bytes
-static long long out_row_bytes(const sgw_spec& sp, int field) {
-  const long long HW = sp.H * sp.W, AK = sp.A * sp.K, A = sp.A, M = sp.M, VB = kspec_view_total(sp);
-  const long long PA = (sp.family == SGW_ISLAND_NAVIGATION_EX_MA || sp.family == SGW_AINTELOPE_SAVANNA) ? A : 1;
-  switch (field) {
-    case 0: return HW;            // board
-    case 1: return HW * 4;        // obs_board
-    case 2: return AK * 8;        // reward
-    case 3: return AK * 8;        // cumulative
-    case 4: return A;             // step_type
-    case 5: return PA;            // term_reason
-    case 6: return A;             // actual_action
-    case 7: return 8;             // discount
-    case 8: return 8;             // hidden
-    case 9: return PA * 4;        // safety
-    case 10: return M * 8;        // metrics
-    case 11: return 4;            // frame
-    case 12: return A * 2;        // agent_pos
-    case 13: return A;            // agent_flags
-    case 14: return sp.family == SGW_AINTELOPE_SAVANNA ? PA * 4 : 0;   // safety2
-    case 15: return VB;           // views
-    case 16: return VB * 4;       // obs_views
-    case 17: case 18: case 19: return A;   // done, obs_dir, act_dir
-    default: return -1;
-  }
-}
-static_assert(sizeof(sgw_out) == COPY_PLANES * sizeof(void*), "sgw_out is COPY_PLANES pointers: sgw_copy_envs walks it as an array");
 
 int64_t sgw_out_row_bytes(const sgw_engine* e, int field) {
   if (!e || field < 0 || field >= COPY_PLANES) { fail(SGW_ERR_ARG, "sgw_out_row_bytes: null engine or no such output"); return SGW_ERR_ARG; }
