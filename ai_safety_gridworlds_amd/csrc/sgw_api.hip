@@ -19,6 +19,7 @@
 #include "sgw_island_ma.hpp"
 #include "sgw_island.hpp"
 #include "sgw_kernels.hpp"
+#include "sgw_observe.hpp"
 #include "sgw_rocks.hpp"
 #include "sgw_safeint.hpp"
 #include "sgw_savanna.hpp"
@@ -179,7 +180,7 @@ struct sgw_engine {
 static void drop_graphs(sgw_engine* e) { ++e->arg_epoch; }
 
 static size_t acc_bytes(const sgw_engine* e) {              // [env-waves * parts][A*K+1] doubles
-  return (size_t)(e->spec.A * e->spec.K + 1) * (size_t)(SGW_ACC_PER_ENV ? e->n_pad : e->n_pad / WAVE * SGW_ACC_PARTS) * 8;
+  return (size_t)(e->spec.A * e->spec.K + 1) * (size_t)(e->n_pad / WAVE * SGW_ACC_PARTS) * 8;
 }
 
 // island_navigation_ex: the packed (i16) state when the spec proves it exact (sgw_island.hpp); SGW_ISLAND_PLAIN_STATE in the
@@ -971,7 +972,7 @@ int sgw_group_rollout(sgw_group* g, int T, uint64_t seed, int64_t step0, int wri
 int sgw_read_returns(sgw_engine* e, double* out_dev, int clear, void* stream) {
   if (!e || !out_dev) return fail(SGW_ERR_ARG, "sgw_read_returns: null argument");
   hipLaunchKernelGGL(k_read_returns, dim3(e->spec.A * e->spec.K + 1), dim3(256), 0, (hipStream_t)stream, e->acc_dev,
-                     SGW_ACC_PER_ENV ? e->n_pad : e->n_pad / WAVE * SGW_ACC_PARTS, e->spec.A * e->spec.K + 1, out_dev, clear);
+                     e->n_pad / WAVE * SGW_ACC_PARTS, e->spec.A * e->spec.K + 1, out_dev, clear);
   HIP_TRY(hipGetLastError());
   return SGW_OK;
 }
@@ -1017,7 +1018,7 @@ int sgw_accumulate_returns(sgw_engine* e, const double* cumulative_dev, const ui
   return SGW_OK;
 }
 
-// ceil(2^32 / x) for div_recip (sgw_kernels.hpp): exact for every f <= f_max, or refused by the caller.  Each reciprocal is
+// ceil(2^32 / x) for div_recip (sgw_common.hpp): exact for every f <= f_max, or refused by the caller.  Each reciprocal is
 // checked over the quotients its users take: a block's cell index / HW (< PLANES_ENVS * HW) and a block's 4-cell item / Q
 // (< PLANES_ENVS * Q).  (The bound used to be the block's P * HW output bytes, for a per-byte expansion no kernel calls: it
 // refused e.g. 32 layers of a 17 x 17 board.)
@@ -1078,7 +1079,7 @@ int sgw_derived_stats(sgw_engine* e, const double* reward_dev, const double* cum
   }
   HIP_TRY(hipSetDevice(e->device));
   const int A = e->spec.A, K = e->spec.K;
-  const size_t lds = (size_t)(2 * A * K + A * (5 + K)) * WAVE * 8;           // R | C | O (sgw_kernels.hpp k_derived_stats)
+  const size_t lds = (size_t)(2 * A * K + A * (5 + K)) * WAVE * 8;           // R | C | O (sgw_observe.hpp k_derived_stats)
   if (lds > 65536 && !(e->lds_cap_raised & 8u)) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_derived_stats), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     e->lds_cap_raised |= 8u;

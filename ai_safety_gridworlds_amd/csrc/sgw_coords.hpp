@@ -11,7 +11,7 @@
 // pass's total, which the running base carries to the next pass.  A set cell's rank addresses ONE 4-byte store of its
 // coordinate pair; ranks >= cap and the entries past the count are never stored, so the store traffic follows the objects.
 #pragma once
-#include "sgw_kernels.hpp"      // div_recip
+#include "sgw_common.hpp"       // div_recip
 
 namespace sgw {
 

@@ -15,10 +15,10 @@
 //                    metric rows are copied by the whole wave: element j of the span is column j % C of record j / C, whose
 //                    source lane is the (j / C)-th set bit of the ballot (one ds_permute hands every rank its lane) -- coalesced
 //                    stores whose number follows the episodes, not N.  Records at index >= cap are not stored.
-// Rows n >= N never count.  The predicate is episode_ended (sgw_kernels.hpp), the one of sgw_track_performance; it inherits that
+// Rows n >= N never count.  The predicate is episode_ended (sgw_common.hpp), the one of sgw_track_performance; it inherits that
 // predicate's repeat on idle rounds of the per-agent families (every agent already DEAD, no reset: the row counts again).
 #pragma once
-#include "sgw_kernels.hpp"      // episode_ended, div_recip
+#include "sgw_common.hpp"       // episode_ended, div_recip
 
 namespace sgw {
 

@@ -42,6 +42,7 @@
 #include <utility>
 
 #include "sgw_common.hpp"
+#include "sgw_pcg64.hpp"
 
 namespace sgw {
 
@@ -53,7 +54,7 @@ struct M5 { uint64_t a, b, c, d, e; };
 struct PcgJump { uint64_t v[65][4]; };
 constexpr PcgJump make_pcg_jump() {
   PcgJump t{};
-  const unsigned __int128 mult = ((unsigned __int128)0x2360ED051FC65DA4ULL << 64) | 0x4385DF649FCCF645ULL;
+  const unsigned __int128 mult = ((unsigned __int128)PCG64_MULT_HI << 64) | PCG64_MULT_LO;
   unsigned __int128 a = 1, g = 0;
   for (int j = 0; j <= 64; ++j) {
     t.v[j][0] = (uint64_t)(a >> 64); t.v[j][1] = (uint64_t)a; t.v[j][2] = (uint64_t)(g >> 64); t.v[j][3] = (uint64_t)g;
@@ -95,26 +96,27 @@ struct FiremakerT {
     int frame, step_type, term, countdown, n_ext, at_ws;   // at_ws: bit a = agent a stands on a workshop tile
     int row[3], col[3];
     int dirs;                                              // bits 2a..2a+1 action direction of agent a, bits 6+2a.. its observation direction
-    uint32_t episode, rng_has32, rng_u32;
-    uint64_t rs_hi, rs_lo, ri_hi, ri_lo;                   // PCG64 state / increment
+    uint32_t episode;
+    Pcg64BufFirst g;                                       // the env's numpy PCG64 (state, inc, buffered uint32)
     M5 fire;
     uint32_t visits[15];                                   // [kind][agent]
     double cum[NU];
   };
 
   static __host__ __device__ int words() { return 25; }
+  static_assert(PCG64_FLAG_WORD == 0 && PCG64_U32_WORD == 2 && PCG64_WORD0 == 3, "load / store: w0 carries the generator's flag, w2 its buffered value, its four words follow");
 
   static __device__ void load(State& s, const KArgs& a, long long env) {
     Cursor c(a, env);
     uint64_t w0 = c.get(), w1 = c.get(), w2 = c.get();
     s.frame = (int)(w0 & 0xffff); s.step_type = (int)((w0 >> 32) & 0xf); s.term = (int)((w0 >> 36) & 0xf);
-    s.countdown = (int)((w0 >> 16) & 0xff); s.at_ws = (int)((w0 >> 24) & 0x7); s.rng_has32 = (uint32_t)((w0 >> 27) & 1);
+    s.countdown = (int)((w0 >> 16) & 0xff); s.at_ws = (int)((w0 >> 24) & 0x7); s.g.has32 = pcg64_flag_of(w0);
     s.n_ext = (int)((w0 >> 40) & 0xffff);
 #pragma unroll
     for (int ag = 0; ag < 3; ++ag) { s.row[ag] = (int)((w1 >> (16 * ag)) & 0xff); s.col[ag] = (int)((w1 >> (16 * ag + 8)) & 0xff); }
     s.dirs = (int)((w1 >> 48) & 0xfff);
-    s.rng_u32 = (uint32_t)w2; s.episode = (uint32_t)(w2 >> 32);
-    s.rs_hi = c.get(); s.rs_lo = c.get(); s.ri_hi = c.get(); s.ri_lo = c.get();
+    s.g.u32 = pcg64_u32_of(w2); s.episode = (uint32_t)(w2 >> 32);
+    pcg64_get(c, s.g);
     s.fire.a = c.get(); s.fire.b = c.get(); s.fire.c = c.get(); s.fire.d = c.get(); s.fire.e = c.get();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -129,13 +131,13 @@ struct FiremakerT {
   static __device__ void store(const State& s, const KArgs& a, long long env) {
     Cursor c(a, env);
     uint64_t w0 = (uint64_t)(s.frame & 0xffff) | ((uint64_t)(s.countdown & 0xff) << 16) | ((uint64_t)(s.at_ws & 7) << 24) |
-                  ((uint64_t)(s.rng_has32 & 1) << 27) | ((uint64_t)(s.step_type & 0xf) << 32) |
+                  pcg64_flag_bits(s.g) | ((uint64_t)(s.step_type & 0xf) << 32) |
                   ((uint64_t)(s.term & 0xf) << 36) | ((uint64_t)(s.n_ext & 0xffff) << 40);
     uint64_t w1 = (uint64_t)(s.dirs & 0xfff) << 48;
 #pragma unroll
     for (int ag = 0; ag < 3; ++ag) w1 |= ((uint64_t)(s.row[ag] & 0xff) << (16 * ag)) | ((uint64_t)(s.col[ag] & 0xff) << (16 * ag + 8));
-    c.put(w0); c.put(w1); c.put((uint64_t)s.rng_u32 | ((uint64_t)s.episode << 32));
-    c.put(s.rs_hi); c.put(s.rs_lo); c.put(s.ri_hi); c.put(s.ri_lo);
+    c.put(w0); c.put(w1); c.put(pcg64_u32_bits(s.g) | ((uint64_t)s.episode << 32));
+    pcg64_put(c, s.g);
     c.put(s.fire.a); c.put(s.fire.b); c.put(s.fire.c); c.put(s.fire.d); c.put(s.fire.e);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -164,32 +166,6 @@ struct FiremakerT {
     for (int u = 0; u < NU; ++u) s.cum[u] = 0.0;
   }
 
-  // ---- numpy PCG64 -----------------------------------------------------------------------------
-  static __device__ uint64_t next64(State& s) {
-    const uint64_t MH = 0x2360ED051FC65DA4ULL, ML = 0x4385DF649FCCF645ULL;
-    uint64_t lo = s.rs_lo * ML;
-    uint64_t hi = __umul64hi(s.rs_lo, ML) + s.rs_hi * ML + s.rs_lo * MH;
-    uint64_t nlo = lo + s.ri_lo;
-    hi += s.ri_hi + (nlo < lo ? 1ull : 0ull);
-    s.rs_lo = nlo; s.rs_hi = hi;
-    uint64_t x = hi ^ nlo;
-    unsigned rot = (unsigned)(hi >> 58);
-    return (x >> rot) | (x << ((64u - rot) & 63u));
-  }
-  static __device__ uint32_t next32(State& s) {
-    if (s.rng_has32) { s.rng_has32 = 0; return s.rng_u32; }
-    uint64_t n = next64(s);
-    s.rng_has32 = 1; s.rng_u32 = (uint32_t)(n >> 32);
-    return (uint32_t)n;
-  }
-  static __device__ double random01(State& s) { return (double)(next64(s) >> 11) * (1.0 / 9007199254740992.0); }
-  static __device__ int interval(State& s, uint32_t max) {        // random_interval for max in {1, 2}
-    const uint32_t mask = max | (max >> 1);
-    uint32_t v;
-    do { v = next32(s) & mask; } while (v > max);
-    return (int)v;
-  }
-
   // The step after LAST still shuffles the (discarded) actions before it resets (PM:177-180, 211-221)
   // the agents in the submitted dict: an action < 0 = "not in the dict" (EnvironmentMa.step plays exactly the agents it is given,
   // PM:173-246; the Gym wrapper with agent_character steps one agent, gridworld_gym_env.py:476-479)
@@ -200,8 +176,8 @@ struct FiremakerT {
   static __device__ void pre_autoreset(State& s, const KArgs& a, const int (&actions)[NA]) {
     if ((a.sp.flags & F_SHUFFLE) && s.step_type == ST_LAST) {        // Generator.shuffle of the n submitted actions, n > 1
       const int n = n_submitted(a.sp, actions);
-      if (n == 3) interval(s, 2);
-      if (n >= 2) interval(s, 1);
+      if (n == 3) interval(s.g, 2);
+      if (n >= 2) interval(s.g, 1);
     }
   }
 
@@ -298,10 +274,7 @@ struct FiremakerT {
     U128 r; r.lo = x.lo + y.lo; r.hi = x.hi + y.hi + (r.lo < x.lo ? 1ull : 0ull); return r;
   }
   static __device__ double pcg_double(const U128& x) {             // XSL-RR 128/64, then Generator.random()
-    uint64_t v = x.hi ^ x.lo;
-    const unsigned rot = (unsigned)(x.hi >> 58);
-    v = (v >> rot) | (v << ((64u - rot) & 63u));
-    return (double)(v >> 11) * (1.0 / 9007199254740992.0);
+    return pcg64_to_double(pcg64_xsl_rr(x.hi, x.lo));
   }
   // values every lane holds identically (LDS constants): move them to SGPRs so they cost no vector registers
   static __device__ uint64_t uniform_u64(uint64_t v) {
@@ -571,7 +544,7 @@ struct FiremakerT {
 
     // ---- cooperative phase: this wave's 16 envs, one at a time; envs with nothing burning and nothing to ignite are skipped
     M5 res = old;
-    uint64_t res_hi = s.rs_hi, res_lo = s.rs_lo;
+    uint64_t res_hi = s.g.rs_hi, res_lo = s.g.rs_lo;
     // (a lane whose play slot is empty -- it resets this step, or fewer agents were submitted than the round has slots -- has none)
     const bool has_work = live && ((old.a | old.b | old.c | old.d | old.e | cand.a | cand.b | cand.c | cand.d | cand.e) != 0ull);
     // burning envs are handed out dynamically: every wave pulls tickets from one LDS counter until it draws one past
@@ -603,7 +576,7 @@ struct FiremakerT {
         const uint64_t o[5] = {rl64(old.a, e), rl64(old.b, e), rl64(old.c, e), rl64(old.d, e), rl64(old.e, e)};
         const uint64_t c[5] = {rl64(cand.a, e), rl64(cand.b, e), rl64(cand.c, e), rl64(cand.d, e), rl64(cand.e, e)};
         uint64_t nf[5] = {o[0], o[1], o[2], o[3], o[4]};
-        const U128 st = {rl64(s.rs_hi, e), rl64(s.rs_lo, e)}, inc = {rl64(s.ri_hi, e), rl64(s.ri_lo, e)};
+        const U128 st = {rl64(s.g.rs_hi, e), rl64(s.g.rs_lo, e)}, inc = {rl64(s.g.ri_hi, e), rl64(s.g.ri_lo, e)};
         const uint32_t wse = rl32(ws, e);
         const U128 gi = mul128(gj, inc);
         g.xa = add128(mul128(aj, st), gi);                                // state after lane+1 steps
@@ -644,7 +617,7 @@ struct FiremakerT {
     FM_T(10);                                                   // waiting for the slowest wave of the workgroup
     if (has_work) {
       s.fire.a = ex[0]; s.fire.b = ex[64]; s.fire.c = ex[128]; s.fire.d = ex[192]; s.fire.e = ex[256];
-      s.rs_hi = ex[320]; s.rs_lo = ex[384];
+      s.g.rs_hi = ex[320]; s.g.rs_lo = ex[384];
     }
     cx.parity ^= 1;                                            // double-buffered: the next update writes the other half
 
@@ -773,12 +746,12 @@ struct FiremakerT {
     int o2 = 2;
     if (live && (sp.flags & F_SHUFFLE)) {
       if (n == 3) {
-        const int j = interval(s, 2);
+        const int j = interval(s.g, 2);
         const int t2 = j == 0 ? o0 : (j == 1 ? o1 : o2);
         o0 = j == 0 ? o2 : o0; o1 = j == 1 ? o2 : o1; o2 = t2;
       }
       if (n >= 2) {
-        const int j = interval(s, 1);
+        const int j = interval(s.g, 1);
         const int t1 = j == 0 ? o0 : o1;
         o0 = j == 0 ? o1 : o0; o1 = t1;
       }

@@ -34,6 +34,7 @@
 #pragma once
 
 #include "sgw_common.hpp"
+#include "sgw_pcg64.hpp"
 #include "sgw_pow.hpp"
 
 namespace sgw {
@@ -104,8 +105,8 @@ struct IslandMaT {
     int frame, step_type, term;             // env-level summary: ST_LAST once every agent is done
     int ast[2], tr[2], adir[2], odir[2], acted[2];
     int row[2], col[2];
-    uint32_t episode_no, map_episode, map_cached, rng_has32, rng_u32;
-    uint64_t rs_hi, rs_lo, ri_hi, ri_lo;
+    uint32_t episode_no, map_episode, map_cached;
+    Pcg64BufFirst g;                        // the env's numpy PCG64 (same stream discipline as firemaker: environment_data[NP_RANDOM] survives resets)
     uint32_t gap_v[2], drink_v[2], food_v[2], gold_v[2], silver_v[2];
     double drink_sat[2], food_sat[2], d_avail, d_frac, f_avail, f_frac;
     Map8 map;
@@ -114,6 +115,7 @@ struct IslandMaT {
 
   static __host__ __device__ int words(int K) { return 18 + NW + 2 * K; }
   static __device__ int slot(const KSpec& sp, int u) { return sp.dim_slot[u / NUA][u % NUA]; }
+  static_assert(PCG64_FLAG_WORD == 0 && PCG64_U32_WORD == 2 && PCG64_WORD0 == 3, "load / store: w0 carries the generator's flag, w2 its buffered value, its four words follow");
 
   static __device__ void load(State& s, const KArgs& a, long long env) {
     Cursor c(a, env);
@@ -121,15 +123,15 @@ struct IslandMaT {
     s.frame = (int)(w0 & 0xffff);
     s.ast[0] = (int)((w0 >> 16) & 7); s.ast[1] = (int)((w0 >> 19) & 7);
     s.tr[0] = (int)((w0 >> 22) & 3); s.tr[1] = (int)((w0 >> 24) & 3);
-    s.acted[0] = (int)((w0 >> 26) & 1); s.rng_has32 = (uint32_t)((w0 >> 27) & 1);
+    s.acted[0] = (int)((w0 >> 26) & 1); s.g.has32 = pcg64_flag_of(w0);
     s.adir[0] = (int)((w0 >> 28) & 3); s.adir[1] = (int)((w0 >> 30) & 3);
     s.step_type = (int)((w0 >> 32) & 0xf); s.term = (int)((w0 >> 36) & 0xf);   // same place in every family (sgw_create)
     s.odir[0] = (int)((w0 >> 40) & 3); s.odir[1] = (int)((w0 >> 42) & 3);
     s.acted[1] = (int)((w0 >> 44) & 1); s.map_cached = (uint32_t)((w0 >> 45) & 1);
     s.row[0] = (int)(w1 & 0xff); s.col[0] = (int)((w1 >> 8) & 0xff); s.row[1] = (int)((w1 >> 16) & 0xff); s.col[1] = (int)((w1 >> 24) & 0xff);
     s.episode_no = (uint32_t)((w1 >> 32) & 0xffff); s.map_episode = (uint32_t)((w1 >> 48) & 0xffff);
-    s.rng_u32 = (uint32_t)w2;
-    s.rs_hi = c.get(); s.rs_lo = c.get(); s.ri_hi = c.get(); s.ri_lo = c.get();
+    s.g.u32 = pcg64_u32_of(w2);
+    pcg64_get(c, s.g);
     const uint64_t v0 = c.get(), v1 = c.get(), v2 = c.get();
     s.gap_v[0] = (uint32_t)(v0 & 0xffff); s.gap_v[1] = (uint32_t)((v0 >> 16) & 0xffff);
     s.drink_v[0] = (uint32_t)((v0 >> 32) & 0xffff); s.drink_v[1] = (uint32_t)((v0 >> 48) & 0xffff);
@@ -147,14 +149,14 @@ struct IslandMaT {
   static __device__ void store(const State& s, const KArgs& a, long long env) {
     const uint64_t w0 = (uint64_t)(s.frame & 0xffff) | ((uint64_t)(s.ast[0] & 7) << 16) | ((uint64_t)(s.ast[1] & 7) << 19) |
                         ((uint64_t)(s.tr[0] & 3) << 22) | ((uint64_t)(s.tr[1] & 3) << 24) | ((uint64_t)(s.acted[0] & 1) << 26) |
-                        ((uint64_t)(s.rng_has32 & 1) << 27) | ((uint64_t)(s.adir[0] & 3) << 28) | ((uint64_t)(s.adir[1] & 3) << 30) |
+                        pcg64_flag_bits(s.g) | ((uint64_t)(s.adir[0] & 3) << 28) | ((uint64_t)(s.adir[1] & 3) << 30) |
                         ((uint64_t)(s.step_type & 0xf) << 32) | ((uint64_t)(s.term & 0xf) << 36) | ((uint64_t)(s.odir[0] & 3) << 40) |
                         ((uint64_t)(s.odir[1] & 3) << 42) | ((uint64_t)(s.acted[1] & 1) << 44) | ((uint64_t)(s.map_cached & 1) << 45);
     const uint64_t w1 = (uint64_t)(s.row[0] & 0xff) | ((uint64_t)(s.col[0] & 0xff) << 8) | ((uint64_t)(s.row[1] & 0xff) << 16) |
                         ((uint64_t)(s.col[1] & 0xff) << 24) | ((uint64_t)(s.episode_no & 0xffff) << 32) | ((uint64_t)(s.map_episode & 0xffff) << 48);
     Cursor c(a, env);
-    c.put(w0); c.put(w1); c.put((uint64_t)s.rng_u32);
-    c.put(s.rs_hi); c.put(s.rs_lo); c.put(s.ri_hi); c.put(s.ri_lo);
+    c.put(w0); c.put(w1); c.put(pcg64_u32_bits(s.g));
+    pcg64_put(c, s.g);
     c.put((uint64_t)(s.gap_v[0] & 0xffff) | ((uint64_t)(s.gap_v[1] & 0xffff) << 16) | ((uint64_t)(s.drink_v[0] & 0xffff) << 32) | ((uint64_t)(s.drink_v[1] & 0xffff) << 48));
     c.put((uint64_t)(s.food_v[0] & 0xffff) | ((uint64_t)(s.food_v[1] & 0xffff) << 16) | ((uint64_t)(s.gold_v[0] & 0xffff) << 32) | ((uint64_t)(s.gold_v[1] & 0xffff) << 48));
     c.put((uint64_t)(s.silver_v[0] & 0xffff) | ((uint64_t)(s.silver_v[1] & 0xffff) << 16));
@@ -164,32 +166,6 @@ struct IslandMaT {
     if constexpr (NW == 8) { c.put(s.map.e); c.put(s.map.f); c.put(s.map.g); c.put(s.map.h); }
 #pragma unroll
     for (int u = 0; u < NU; ++u) if (slot(a.sp, u) >= 0) c.putf(s.cum[u]);
-  }
-
-  // ---- numpy PCG64 (same stream discipline as firemaker: environment_data[NP_RANDOM] survives resets) -------------
-  static __device__ uint64_t next64(State& s) {
-    const uint64_t MH = 0x2360ED051FC65DA4ULL, ML = 0x4385DF649FCCF645ULL;
-    uint64_t lo = s.rs_lo * ML;
-    uint64_t hi = __umul64hi(s.rs_lo, ML) + s.rs_hi * ML + s.rs_lo * MH;
-    uint64_t nlo = lo + s.ri_lo;
-    hi += s.ri_hi + (nlo < lo ? 1ull : 0ull);
-    s.rs_lo = nlo; s.rs_hi = hi;
-    uint64_t x = hi ^ nlo;
-    unsigned rot = (unsigned)(hi >> 58);
-    return (x >> rot) | (x << ((64u - rot) & 63u));
-  }
-  static __device__ uint32_t next32(State& s) {
-    if (s.rng_has32) { s.rng_has32 = 0; return s.rng_u32; }
-    uint64_t n = next64(s);
-    s.rng_has32 = 1; s.rng_u32 = (uint32_t)(n >> 32);
-    return (uint32_t)n;
-  }
-  static __device__ int interval(State& s, uint32_t max) {        // distributions.c random_interval, max < 2^32
-    uint32_t mask = max;
-    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-    uint32_t v;
-    do { v = next32(s) & mask; } while (v > max);
-    return (int)v;
   }
 
   // ---- 4-bit map ----------------------------------------------------------------------------------------------
@@ -223,7 +199,7 @@ struct IslandMaT {
     return actions[ag] >= 0 && (!any_dead || s.ast[ag] == AST_DEAD);
   }
   static __device__ void pre_autoreset(State& s, const KArgs& a, const int (&actions)[2]) {
-    if ((a.sp.flags & F_SHUFFLE) && s.step_type == ST_LAST && eligible(s, 0, actions) && eligible(s, 1, actions)) interval(s, 1);
+    if ((a.sp.flags & F_SHUFFLE) && s.step_type == ST_LAST && eligible(s, 0, actions) && eligible(s, 1, actions)) interval(s.g, 1);
   }
   static __device__ bool reset_requested(const State& s, const KArgs&, const int (&actions)[2]) {
     return s.step_type == ST_NONE || eligible(s, 0, actions) || eligible(s, 1, actions);
@@ -258,7 +234,7 @@ struct IslandMaT {
         Map8 m = level;
         const int w = sp.W - 2, n = (sp.H - 2) * w;
         for (int i = n - 1; i >= 1; --i) {
-          const int j = interval(s, (uint32_t)i);
+          const int j = interval(s.g, (uint32_t)i);
           const int ci = (i / w + 1) * sp.W + i % w + 1, cj = (j / w + 1) * sp.W + j % w + 1;
           const int vi = mget(m, ci), vj = mget(m, cj);
           mset(m, ci, vj); mset(m, cj, vi);
@@ -419,7 +395,7 @@ struct IslandMaT {
     const bool alive0 = s.ast[0] < AST_LAST && actions[0] >= 0, alive1 = s.ast[1] < AST_LAST && actions[1] >= 0;
     int first = alive0 ? 0 : 1;
     const int n = (alive0 ? 1 : 0) + (alive1 ? 1 : 0);
-    if (n == 2 && (sp.flags & F_SHUFFLE)) first = interval(s, 1) == 0 ? 1 : 0;     // Generator.shuffle of 2: swap when j == 0
+    if (n == 2 && (sp.flags & F_SHUFFLE)) first = interval(s.g, 1) == 0 ? 1 : 0;     // Generator.shuffle of 2: swap when j == 0
     double discount = (s.tr[0] != T_UNSET && s.tr[1] != T_UNSET) ? 0.0 : 1.0;      // no play: the last discount stands
     if (n >= 1) discount = play_one(s, first, first == 0 ? actions[0] : actions[1], sp, p, r);
     // a play behind a QUIT is dropped (the reference's engine raises for it); the shuffle above has drawn

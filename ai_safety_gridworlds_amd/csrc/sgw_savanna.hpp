@@ -35,6 +35,7 @@
 #include <utility>
 
 #include "sgw_common.hpp"
+#include "sgw_pcg64.hpp"
 #include "sgw_pow.hpp"
 
 namespace sgw {
@@ -151,13 +152,12 @@ struct Savanna {
   enum { L_P = 0, L_D = 1, L_F = 2, L_SD = 3, L_SF = 4 };     // dynamic layers; resources are L_D + {0: D, 1: F, 2: d, 3: f}
   enum { V_GAP, V_DRINK, V_FOOD, V_SDRINK, V_SFOOD, V_GOLD, V_SILVER };
 
-  struct Rng { uint64_t rs_hi, rs_lo, ri_hi, ri_lo; uint32_t has32, u32; };
   struct State {
     int frame, step_type, term;
     int ast, adir[2], odir[2], acted[2];
     int row[2], col[2];
     uint32_t episode_no, map_episode, map_cached;
-    Rng g;                                 // the env's numpy PCG64 (state, inc, buffered uint32)
+    Pcg64 g;                               // the env's numpy PCG64 (state, inc, buffered uint32)
     int saf[2], saf2[2];                   // safety_<agent> (water), safety2_<agent> (predators)
     uint32_t stepc[2];                     // AgentSafetySpriteMo.step_count (MM:1599-1623): plays of this agent in the episode
     uint32_t vis[7][2];
@@ -169,6 +169,7 @@ struct Savanna {
   };
 
   static constexpr int W_STATIC = 19, W_DYN = 31, W_CUM = 46;
+  static_assert(PCG64_FLAG_WORD == 0 && PCG64_U32_WORD == 2 && PCG64_WORD0 == 3, "load / store: w0 carries the generator's flag, w2 its buffered value, its four words follow");
   static __host__ __device__ int words(int K) { return W_CUM + 2 * K + 16; }
   static __device__ __forceinline__ int w_init(const KSpec& sp) { return W_CUM + 2 * sp.K; }
   static __device__ __forceinline__ int slot(const KSpec& sp, int u) { return sp.dim_slot[u / NUA][u % NUA]; }
@@ -179,16 +180,16 @@ struct Savanna {
     const uint64_t w0 = c.get(), w1 = c.get(), w2 = c.get();
     s.frame = (int)(w0 & 0xffff);
     s.ast = (int)((w0 >> 16) & 7);
-    s.acted[0] = (int)((w0 >> 26) & 1); s.g.has32 = (uint32_t)((w0 >> 27) & 1);
+    s.acted[0] = (int)((w0 >> 26) & 1); s.g.has32 = pcg64_flag_of(w0);
     s.adir[0] = (int)((w0 >> 28) & 3); s.adir[1] = (int)((w0 >> 30) & 3);
     s.step_type = (int)((w0 >> 32) & 0xf); s.term = (int)((w0 >> 36) & 0xf);   // same place in every family (sgw_create)
     s.odir[0] = (int)((w0 >> 40) & 3); s.odir[1] = (int)((w0 >> 42) & 3);
     s.acted[1] = (int)((w0 >> 44) & 1); s.map_cached = (uint32_t)((w0 >> 45) & 1);
     s.row[0] = (int)(w1 & 0xff); s.col[0] = (int)((w1 >> 8) & 0xff); s.row[1] = (int)((w1 >> 16) & 0xff); s.col[1] = (int)((w1 >> 24) & 0xff);
     s.episode_no = (uint32_t)((w1 >> 32) & 0xffff); s.map_episode = (uint32_t)((w1 >> 48) & 0xffff);
-    s.g.u32 = (uint32_t)w2; s.saf[0] = (int)((w2 >> 32) & 0xff); s.saf[1] = (int)((w2 >> 40) & 0xff);
+    s.g.u32 = pcg64_u32_of(w2); s.saf[0] = (int)((w2 >> 32) & 0xff); s.saf[1] = (int)((w2 >> 40) & 0xff);
     s.saf2[0] = (int)((w2 >> 48) & 0xff); s.saf2[1] = (int)((w2 >> 56) & 0xff);
-    s.g.rs_hi = c.get(); s.g.rs_lo = c.get(); s.g.ri_hi = c.get(); s.g.ri_lo = c.get();
+    pcg64_get(c, s.g);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                                     // 14 visit counters, 16 bits each, 4 per word
       const uint64_t v = c.get();
@@ -212,15 +213,15 @@ struct Savanna {
   static __device__ __forceinline__ void store(const State& s, const KArgs& a, long long env) {
     SAV_T(5);                                                   // outputs staged and copied out
     const uint64_t w0 = (uint64_t)(s.frame & 0xffff) | ((uint64_t)(s.ast & 7) << 16) | ((uint64_t)(s.acted[0] & 1) << 26) |
-                        ((uint64_t)(s.g.has32 & 1) << 27) | ((uint64_t)(s.adir[0] & 3) << 28) | ((uint64_t)(s.adir[1] & 3) << 30) |
+                        pcg64_flag_bits(s.g) | ((uint64_t)(s.adir[0] & 3) << 28) | ((uint64_t)(s.adir[1] & 3) << 30) |
                         ((uint64_t)(s.step_type & 0xf) << 32) | ((uint64_t)(s.term & 0xf) << 36) | ((uint64_t)(s.odir[0] & 3) << 40) |
                         ((uint64_t)(s.odir[1] & 3) << 42) | ((uint64_t)(s.acted[1] & 1) << 44) | ((uint64_t)(s.map_cached & 1) << 45);
     const uint64_t w1 = (uint64_t)(s.row[0] & 0xff) | ((uint64_t)(s.col[0] & 0xff) << 8) | ((uint64_t)(s.row[1] & 0xff) << 16) |
                         ((uint64_t)(s.col[1] & 0xff) << 24) | ((uint64_t)(s.episode_no & 0xffff) << 32) | ((uint64_t)(s.map_episode & 0xffff) << 48);
     Cursor c(a, env);
-    c.put(w0); c.put(w1); c.put((uint64_t)s.g.u32 | ((uint64_t)(s.saf[0] & 0xff) << 32) | ((uint64_t)(s.saf[1] & 0xff) << 40) |
+    c.put(w0); c.put(w1); c.put(pcg64_u32_bits(s.g) | ((uint64_t)(s.saf[0] & 0xff) << 32) | ((uint64_t)(s.saf[1] & 0xff) << 40) |
           ((uint64_t)(s.saf2[0] & 0xff) << 48) | ((uint64_t)(s.saf2[1] & 0xff) << 56));
-    c.put(s.g.rs_hi); c.put(s.g.rs_lo); c.put(s.g.ri_hi); c.put(s.g.ri_lo);
+    pcg64_put(c, s.g);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       uint64_t v = 0;
@@ -243,47 +244,9 @@ struct Savanna {
     SAV_T(6);                                                   // state stores issued
   }
 
-  // ---- numpy PCG64 ------------------------------------------------------------------------------------------------
-  static __device__ __forceinline__ uint64_t next64(Rng& g) {
-    const uint64_t MH = 0x2360ED051FC65DA4ULL, ML = 0x4385DF649FCCF645ULL;
-    uint64_t lo = g.rs_lo * ML;
-    uint64_t hi = __umul64hi(g.rs_lo, ML) + g.rs_hi * ML + g.rs_lo * MH;
-    uint64_t nlo = lo + g.ri_lo;
-    hi += g.ri_hi + (nlo < lo ? 1ull : 0ull);
-    g.rs_lo = nlo; g.rs_hi = hi;
-    uint64_t x = hi ^ nlo;
-    unsigned rot = (unsigned)(hi >> 58);
-    return (x >> rot) | (x << ((64u - rot) & 63u));
-  }
-  static __device__ __forceinline__ uint32_t next32(Rng& g) {
-    if (g.has32) { g.has32 = 0; return g.u32; }
-    uint64_t n = next64(g);
-    g.has32 = 1; g.u32 = (uint32_t)(n >> 32);
-    return (uint32_t)n;
-  }
-  static __device__ __forceinline__ int interval(Rng& g, uint32_t max) {        // distributions.c random_interval (Generator.shuffle)
-    uint32_t mask = max;
-    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-    uint32_t v;
-    int guard = 0;
-    do { v = next32(g) & mask; } while (v > max && ++guard < 1024);     // p(reject) < 1/2 per draw
-    return (int)(v > max ? max : v);
-  }
-  static __device__ __forceinline__ int lemire(Rng& g, uint32_t rng) {          // distributions.c bounded_lemire_uint32 (integers / choice)
-    if (rng == 0u) return 0;
-    const uint32_t ex = rng + 1u;
-    uint64_t m = (uint64_t)next32(g) * ex;
-    uint32_t left = (uint32_t)m;
-    if (left < ex) {
-      const uint32_t thr = (0xffffffffu - rng) % ex;
-      // a live stream leaves after ~1 draw (thr / 2^32 < 2^-24 here); the cap keeps a wave with a dead stream from spinning
-      for (int guard = 0; left < thr && guard < 64; ++guard) { m = (uint64_t)next32(g) * ex; left = (uint32_t)m; }
-    }
-    return (int)(m >> 32);
-  }
   // Generator.choice(pop, size, replace=False), pop <= 10000: Floyd's sampler, then _shuffle_int over the picks (their
   // order never matters here, the draws do).  Returns the picked ranks as a bitmap.
-  static __device__ __forceinline__ B3 choose(Rng& g, int pop, int size) {
+  static __device__ __forceinline__ B3 choose(Pcg64& g, int pop, int size) {
     B3 ch{0ull, 0ull, 0ull};
     for (int j = pop - size; j < pop; ++j) {
       const int val = lemire(g, (uint32_t)j);
@@ -303,7 +266,7 @@ struct Savanna {
   // the all-LAST round still shuffles its (discarded) actions when both agents submitted one (an action < 0 = not submitted:
   // EnvironmentMa.step with a subset of the agents, the AEC wrapper's way)
   static __device__ __forceinline__ void pre_autoreset(State& s, const KArgs& a, const int (&actions)[2]) {
-    if ((a.sp.flags & F_SHUFFLE) && (a.sp.flags & F_TWO) && s.step_type == ST_LAST && actions[0] >= 0 && actions[1] >= 0) interval(s.g, 1);
+    if ((a.sp.flags & F_SHUFFLE) && (a.sp.flags & F_TWO) && s.step_type == ST_LAST && actions[0] >= 0 && actions[1] >= 0) interval_guarded_clamped(s.g, 1);
   }
   static __device__ __forceinline__ bool reset_requested(const State& s, const KArgs& a, const int (&actions)[2]) {
     return s.step_type == ST_NONE || actions[0] >= 0 || ((a.sp.flags & F_TWO) && actions[1] >= 0);   // a one-agent env's second slot is padding
@@ -429,7 +392,7 @@ struct Savanna {
       }
       const int w = W - 2, n = (sp.H - 2) * w;                       // MA:1224-1241
       for (int i = n - 1; i >= 1; --i) {
-        const int j = interval(s.g, (uint32_t)i);
+        const int j = interval_guarded_clamped(s.g, (uint32_t)i);
         const int ci = (i / w + 1) * W + i % w + 1, cj = (j / w + 1) * W + j % w + 1;
         const uint8_t vi = cells[ci], vj = cells[cj];
         cells[ci] = vj; cells[cj] = vi;
@@ -645,7 +608,7 @@ struct Savanna {
         const int cell = b3_pop_lowest(snap);
         if (cell == p0 || (two && cell == p1)) { injury += (cell == pos) ? p[P_PREDATOR] : 0.0; continue; }
         if (!last_of_round) continue;
-        const double u = (double)(next64(s.g) >> 11) * (1.0 / 9007199254740992.0);
+        const double u = random01(s.g);
         if (u >= p[P_PRED_PROB]) continue;
         const int ch = lemire(s.g, 3u);                                 // UP DOWN LEFT RIGHT
         int rr = row_of(cell, inv), qq = cell - rr * W;
@@ -679,7 +642,7 @@ struct Savanna {
     const bool sub0 = actions[0] >= 0, sub1 = two && actions[1] >= 0;
     int first = sub0 ? 0 : 1;
     const int nplays = (sub0 ? 1 : 0) + (sub1 ? 1 : 0);
-    if (nplays == 2 && (sp.flags & F_SHUFFLE)) first = interval(s.g, 1) == 0 ? 1 : 0;     // Generator.shuffle of 2: swap when j == 0
+    if (nplays == 2 && (sp.flags & F_SHUFFLE)) first = interval_guarded_clamped(s.g, 1) == 0 ? 1 : 0;     // Generator.shuffle of 2: swap when j == 0
     bool quit = false;                                                          // a play behind a QUIT is dropped (the reference's engine raises
     for (int i = 0; i < nplays && !quit; ++i) {                                 // for it); the shuffle above has drawn.  One inlined copy of the body
       const int ag = first ^ i;

@@ -1,8 +1,8 @@
 // sgw_savanna_layers.hpp -- aintelope_savanna's unoccluded observation layers from the state bitmaps (sgw_state_layers), on the
-// plane writer of sgw_kernels.hpp.  Include after sgw_savanna.hpp and sgw_kernels.hpp.
+// plane writer of sgw_observe.hpp.  Include after sgw_savanna.hpp and sgw_observe.hpp.
 #pragma once
 
-#include "sgw_kernels.hpp"
+#include "sgw_observe.hpp"
 #include "sgw_savanna.hpp"
 
 namespace sgw {
@@ -12,7 +12,7 @@ namespace sgw {
 // where every other layer is blank when gap_only_blank (observe_gaps_only_where_other_layers_are_blank=True, SV:1690).
 // A workgroup takes `epb` envs: their 27 bitmap words + the position word go to LDS, phase 1 reduces a cell to a 12-bit code
 // vector (bit k = "source k is on here": wall, W, G, S, P, D, F, d, f, agent 0, agent 1, gap), phase 2 is the plane writer of
-// sgw_kernels.hpp -- four cells per lane, one dword store per layer, the layer's source picked by a scalar shift.  (Round 2:
+// sgw_observe.hpp -- four cells per lane, one dword store per layer, the layer's source picked by a scalar shift.  (Round 2:
 // a thread per cell re-reading the state words from global memory and storing a byte per layer: 137 us at 65 536 envs.)
 constexpr int SAV_LAYER_WORDS = 28;
 __global__ __launch_bounds__(PLANES_THREADS) void k_savanna_layers(const uint64_t* state, long long n_pad, long long n, int words, PlaneGeom g, int W, int two,

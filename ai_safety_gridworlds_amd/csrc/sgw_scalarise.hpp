@@ -15,7 +15,7 @@
 // Work mapping: one wave per 64 envs of one step t.  The wave's 64 x A rows of `reward` and `cumulative` are contiguous in
 // global memory (each row is K doubles; a lane walking its own row would read at a stride of 8 K bytes): they come in as 16-byte
 // loads and are transposed through LDS as [agent * K + dimension][lane], so a lane then reads its own vector conflict-free
-// (the staging of derived_stats_wave, sgw_kernels.hpp).  Only the rows n < N of a step's N_pad block are read or written.
+// (the staging of derived_stats_wave, sgw_observe.hpp).  Only the rows n < N of a step's N_pad block are read or written.
 // LDS (dynamic): R [A * K][64] | C [A * K][64] doubles = 1 KiB per column pair, at most 64 KiB.
 #pragma once
 

@@ -8,6 +8,8 @@
 
 #include <stdint.h>
 
+#include "sgw_pcg64.hpp"
+
 #if defined(__HIPCC__)
 #define SGW_SEED_HD __host__ __device__
 #else
@@ -51,7 +53,7 @@ SGW_SEED_HD inline void pcg64_from_seed(uint64_t seed, uint64_t out[4]) {
   uint64_t v[4];
   for (int j = 0; j < 4; ++j) v[j] = (uint64_t)w[2 * j] | ((uint64_t)w[2 * j + 1] << 32);
   typedef unsigned __int128 u128;
-  const u128 mult = ((u128)0x2360ED051FC65DA4ull << 64) | 0x4385DF649FCCF645ull;
+  const u128 mult = ((u128)PCG64_MULT_HI << 64) | PCG64_MULT_LO;
   const u128 initstate = ((u128)v[0] << 64) | v[1], initseq = ((u128)v[2] << 64) | v[3];
   const u128 inc = (initseq << 1) | 1u;
   u128 state = inc;
@@ -88,8 +90,6 @@ SGW_SEED_HD inline uint64_t resolve_seed(const uint64_t* seeds, uint64_t base, c
 }  // namespace sgw
 
 #if defined(__HIPCC__)
-#include "sgw_common.hpp"
-
 namespace sgw {
 
 // The engine form: what k_set_rng (sgw_kernels.hpp) writes, from seeds instead of uploaded words and under a mask.  One lane
@@ -102,9 +102,9 @@ __global__ void k_seed_rng(uint64_t* state, long long n_pad, long long n, int wo
   if (mask && (e >= n || !mask[e])) return;
   uint64_t pcg[4] = {0x9E3779B97F4A7C15ull, (uint64_t)e, 0ull, 1ull};
   if (e < n) pcg64_from_seed(resolve_seed(seeds, base, layout_seeds, flags, e), pcg);
-  for (int k = 0; k < 4; ++k) state[state_index(3 + k, e, words)] = pcg[k];
-  state[state_index(0, e, words)] &= ~(1ull << 27);       // the buffered next_uint32: flag and value
-  state[state_index(2, e, words)] &= ~0xffffffffull;
+  for (int k = 0; k < 4; ++k) state[state_index(PCG64_WORD0 + k, e, words)] = pcg[k];
+  state[state_index(PCG64_FLAG_WORD, e, words)] &= ~(1ull << PCG64_FLAG_BIT);       // the buffered next_uint32: flag and value
+  state[state_index(PCG64_U32_WORD, e, words)] &= ~PCG64_U32_MASK;
 }
 
 // The stand-alone form: out uint64 [n, 4]

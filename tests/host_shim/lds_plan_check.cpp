@@ -40,7 +40,7 @@ static bool disjoint(const Region& a, const Region& b) { return a.off + a.bytes 
 static int check(const Geometry& g, int need) {
   const LdsPlan p = lds_plan(g.HW, g.A, g.K, g.M, g.pa, need, g.vb, g.cs, g.vg);
   const long long AK = (long long)g.A * g.K;
-  const bool returns = (need & LN_RETURNS) && !SGW_ACC_PER_ENV;
+  const bool returns = (need & LN_RETURNS) != 0;
   std::vector<Region> r;
   r.push_back({"board", 0, 64LL * g.HW, 16});
   if (need & LN_REWARD) r.push_back({"vec_r", p.vec_r, AK * 512, 16});
