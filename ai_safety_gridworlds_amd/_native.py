@@ -64,6 +64,15 @@ class Episodes(C.Structure):
               ("term_reason", C.c_void_p), ("ret", C.c_void_p), ("hidden", C.c_void_p), ("metrics", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class Policy(C.Structure):
+  """Mirror of `struct sgw_policy` (sgw_policy_act / sgw_policy_step_n): a table policy, device pointers (0 = NULL)."""
+  _fields_ = [("source", C.c_int32), ("n_policies", C.c_int32), ("n_codes", C.c_int32), ("cells", C.c_int32),
+              ("code_of", C.c_void_p), ("weights", C.c_void_p), ("bias", C.c_void_p), ("policy_of_env", C.c_void_p),
+              ("explore_below", C.c_uint64), ("seed", C.c_uint64), ("step_dev", C.c_void_p)]
+
+
+POLICY_BOARD, POLICY_VIEWS = 0, 1
+
 _lib = None
 
 
@@ -154,6 +163,10 @@ def lib():
   if hasattr(L, "sgw_scalarise"):                           # (as above: an older SGW_LIBRARY build has no scalar rewards)
     L.sgw_scalarise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p]
+  if hasattr(L, "sgw_policy_act"):                          # (as above: an older SGW_LIBRARY build has no table policies)
+    L.sgw_sizeof_policy.restype = C.c_int
+    L.sgw_policy_act.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sgw_policy_step_n.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_void_p, C.c_int, C.c_int, C.POINTER(Out), C.c_void_p, C.c_int, C.c_void_p]
   if L.sgw_abi_version() != ABI_VERSION:
     raise SgwError("libsgw.so ABI %d != binding ABI %d" % (L.sgw_abi_version(), ABI_VERSION))
   if L.sgw_sizeof_spec() != C.sizeof(Spec) or L.sgw_sizeof_out() != C.sizeof(Out):
@@ -164,6 +177,8 @@ def lib():
     raise SgwError("struct layout mismatch: sgw_extras %d vs %d" % (L.sgw_sizeof_extras(), C.sizeof(Extras)))
   if hasattr(L, "sgw_log_episodes") and L.sgw_sizeof_episodes() != C.sizeof(Episodes):
     raise SgwError("struct layout mismatch: sgw_episodes %d vs %d" % (L.sgw_sizeof_episodes(), C.sizeof(Episodes)))
+  if hasattr(L, "sgw_policy_act") and L.sgw_sizeof_policy() != C.sizeof(Policy):
+    raise SgwError("struct layout mismatch: sgw_policy %d vs %d" % (L.sgw_sizeof_policy(), C.sizeof(Policy)))
   _lib = L
   return L
 
@@ -177,7 +192,8 @@ EXPORTS = [
     "sgw_sizeof_episodes", "sgw_episode_scratch_bytes", "sgw_log_episodes",
     "sgw_seed_rng", "sgw_pcg64_from_seeds",
     "sgw_copy_envs", "sgw_out_row_bytes",
-    "sgw_scalarise"]
+    "sgw_scalarise",
+    "sgw_sizeof_policy", "sgw_policy_act", "sgw_policy_step_n"]
 
 
 def check(rc, what=""):

@@ -34,6 +34,7 @@
 #include "sgw_seed.hpp"
 #include "sgw_copy.hpp"
 #include "sgw_scalarise.hpp"
+#include "sgw_policy.hpp"
 
 using namespace sgw;
 
@@ -76,13 +77,15 @@ template <int N> struct GraphKey {
   const int8_t* actions[N];
   sgw_out outs[N];
   sgw_extras ex;                                // sgw_step_full
+  sgw_policy pol;                               // sgw_policy_step_n: the policy by value, and where step 0 reads its observation
+  const void* obs0;
   unsigned long long epochs[N];
   int n, T, write_every, accumulate, has_out;
   bool same(const GraphKey& o) const {
     if (actions[0] != o.actions[0] || n != o.n || T != o.T || write_every != o.write_every || accumulate != o.accumulate ||
         has_out != o.has_out) return false;
     return memcmp(actions, o.actions, sizeof(actions[0]) * n) == 0 && memcmp(outs, o.outs, sizeof(sgw_out) * n) == 0 &&
-           memcmp(&ex, &o.ex, sizeof(ex)) == 0;
+           memcmp(&ex, &o.ex, sizeof(ex)) == 0 && memcmp(&pol, &o.pol, sizeof(pol)) == 0 && obs0 == o.obs0;
   }
 };
 
@@ -168,6 +171,8 @@ struct sgw_engine {
   // captures and 64 Ki kernel nodes in all.  sgw_step_full: one captured graph per (actions, out, extras) triple, at most 16
   GraphOwner graph_owner;
   GraphCache<1> graphs{256, 65536, " of the step launches"}, full_graphs{16, 0, ""};
+  // sgw_policy_step_n: the 2T + 1 launches of one closed-loop call, in a cache of their own (they never evict sgw_step_n's): at most 64
+  GraphCache<1> policy_graphs{64, 0, " of the policy and step launches"};
   unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel, + 4 for the BigViews variant; bit 20 for a shaped kernel with compiled rules): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
   int step_shape;          // 1 + the ShapedSteps entry whose kernel runs this engine's one-step launches, 0 = the generic kernel
   int step_rules;          // 1: that entry's kernel with the spec's rule set compiled in runs them (ShapedStep::Rules), 0: the entry's own family
@@ -425,6 +430,7 @@ int sgw_destroy(sgw_engine* e) {
   if (!e) return SGW_OK;
   e->graphs.clear();
   e->full_graphs.clear();
+  e->policy_graphs.clear();
   if (e->graph_owner.capture_stream) (void)hipStreamDestroy(e->graph_owner.capture_stream);
   if (e->tables_dev) (void)hipFree(e->tables_dev);
   if (e->state_dev) (void)hipFree(e->state_dev);
@@ -1546,6 +1552,114 @@ int sgw_scalarise(sgw_engine* e, const double* reward_dev, const double* cumulat
   hipLaunchKernelGGL(k_scalarise, dim3((unsigned)(chunks * T)), dim3(WAVE), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return SGW_OK;
+}
+
+}  // extern "C"
+
+// ---- table policies: sgw_policy_act, sgw_policy_step_n (sgw_policy.hpp) -------------------------------------------------------
+struct PolicyLaunch { PolicyArgs a; unsigned blocks, threads; size_t lds; };
+
+// the checks of a policy against the engine's spec, and everything of a launch that does not move from step to step
+static int policy_plan(const sgw_engine* e, const sgw_policy* p, const char* who, PolicyLaunch& L) {
+  if (!p) return fail(SGW_ERR_ARG, "%s: null policy", who);
+  if (!p->code_of || !p->weights || !p->step_dev) return fail(SGW_ERR_ARG, "%s: the policy's code_of, weights and step_dev are required", who);
+  if (p->source != SGW_POLICY_BOARD && p->source != SGW_POLICY_VIEWS) return fail(SGW_ERR_ARG, "%s: source must be SGW_POLICY_BOARD or SGW_POLICY_VIEWS", who);
+  if (p->n_policies < 1) return fail(SGW_ERR_ARG, "%s: n_policies < 1", who);
+  if (p->n_codes < 1 || p->n_codes > 64) return fail(SGW_ERR_ARG, "%s: n_codes outside 1..64", who);
+  if (p->explore_below > (1ull << 32)) return fail(SGW_ERR_ARG, "%s: explore_below > 2^32", who);
+  const sgw_spec& sp = e->spec;
+  if (sp.n_actions < 1 || sp.n_actions > POLICY_MAX_ACTIONS) return fail(SGW_ERR_UNSUPPORTED, "%s: table policies take specs with 1..16 actions", who);
+  PolicyArgs& a = L.a; memset(&a, 0, sizeof(a));
+  int need = 0;
+  if (p->source == SGW_POLICY_VIEWS) {
+    const ViewSpec v = make_viewspec(e);
+    if (v.total <= 0) return fail(SGW_ERR_ARG, "%s: source VIEWS on a spec without agent windows", who);
+    a.row_bytes = v.total;
+    for (int ag = 0; ag < sp.A; ++ag) {
+      a.c_a[ag] = v.vh[ag] * v.vw[ag]; a.off_a[ag] = v.off[ag];
+      need = a.c_a[ag] > need ? a.c_a[ag] : need;
+    }
+  } else {
+    a.row_bytes = need = sp.H * sp.W;
+    for (int ag = 0; ag < sp.A; ++ag) { a.c_a[ag] = need; a.off_a[ag] = 0; }
+  }
+  if (p->cells < need) return fail(SGW_ERR_ARG, "%s: cells is smaller than the source needs (H*W, or the largest window)", who);
+  int E = 64;
+  while (E > 16 && (long long)E * a.row_bytes > POLICY_MAX_ROW_LDS) E >>= 1;
+  if ((long long)E * a.row_bytes > POLICY_MAX_ROW_LDS) return fail(SGW_ERR_UNSUPPORTED, "%s: the observation row is too long to stage", who);
+  const long long blocks = (e->n_envs + E - 1) / E;
+  if (blocks > 0x7fffffffLL) return fail(SGW_ERR_ARG, "%s: too many envs for one launch", who);
+  a.code_of = p->code_of; a.weights = p->weights; a.bias = p->bias; a.policy_of_env = p->policy_of_env; a.step_dev = p->step_dev;
+  a.explore_below = p->explore_below; a.seed = p->seed;
+  a.n = e->n_envs; a.env_id_base = e->env_id_base;
+  a.envs_per_block = E; a.A = sp.A; a.P = p->n_policies; a.G = p->n_codes; a.C = p->cells; a.n_actions = sp.n_actions; a.action_lo = sp.action_lo;
+  const int pairs = E * sp.A;
+  L.blocks = (unsigned)blocks;
+  L.threads = (unsigned)(pairs >= POLICY_THREADS_MAX ? POLICY_THREADS_MAX : (pairs + WAVE - 1) / WAVE * WAVE);
+  L.lds = ((size_t)E * a.row_bytes + 15) / 16 * 16 + 256;
+  return SGW_OK;
+}
+
+static int policy_launch(const sgw_engine* e, PolicyLaunch& L, const uint8_t* obs, long long t, int8_t* actions, hipStream_t st) {
+  if (((uintptr_t)obs) & 15) return fail(SGW_ERR_ARG, "policy: the observation rows must be 16-byte aligned (they move as 16-byte accesses)");
+  if (L.blocks == 0) return SGW_OK;
+  L.a.obs = obs; L.a.t = t; L.a.actions = actions;
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_policy_act, dim3(L.blocks), dim3(L.threads), L.lds, st, L.a);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+extern "C" {
+
+int sgw_sizeof_policy(void) { return (int)sizeof(sgw_policy); }
+
+int sgw_policy_act(sgw_engine* e, const sgw_policy* p, const uint8_t* obs_dev, int64_t t, int8_t* actions_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_act: null engine");
+  if (!obs_dev || !actions_dev) return fail(SGW_ERR_ARG, "sgw_policy_act: null observation or actions");
+  PolicyLaunch L;
+  const int rc = policy_plan(e, p, "sgw_policy_act", L);
+  if (rc) return rc;
+  return policy_launch(e, L, obs_dev, (long long)t, actions_dev, (hipStream_t)stream);
+}
+
+int sgw_policy_step_n(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, int T, int write_every, const sgw_out* out,
+                      int8_t* actions_out_dev, int accumulate, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_step_n: null engine");
+  if (T < 1) return fail(SGW_ERR_ARG, "sgw_policy_step_n: T < 1");
+  if (!obs0_dev || !actions_out_dev || !out) return fail(SGW_ERR_ARG, "sgw_policy_step_n: obs0, out and actions_out are required");
+  PolicyLaunch L;
+  int rc = policy_plan(e, p, "sgw_policy_step_n", L);
+  if (rc) return rc;
+  const bool from_views = p->source == SGW_POLICY_VIEWS;
+  const uint8_t* produced = from_views ? out->views : out->board;         // what a step leaves for the next act
+  if (!produced) return fail(SGW_ERR_ARG, "sgw_policy_step_n: the policy's source (%s) is not among the outputs", from_views ? "views" : "board");
+  const long long per_step = e->n_envs * e->spec.A, obs_step = e->n_pad * (long long)L.a.row_bytes;
+  const hipStream_t st = (hipStream_t)stream;
+  auto launches = [&](hipStream_t s) -> int {
+    for (int t = 0; t < T; ++t) {
+      int8_t* row = actions_out_dev + (long long)t * per_step;
+      const uint8_t* obs = t == 0 ? obs0_dev : (write_every ? produced + (long long)(t - 1) * obs_step : produced);
+      int r = policy_launch(e, L, obs, t, row, s);
+      if (r) return r;
+      KArgs a;
+      r = step_args(e, row, 1, 0, 0, 0, out, accumulate, a);
+      if (r) return r;
+      if (write_every) offset_out(a.out, e->spec, e->n_pad, t);
+      r = launch(e, a, s);
+      if (r) return r;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_policy_advance, dim3(1), dim3(1), 0, s, p->step_dev, (long long)T);
+    HIP_TRY(hipGetLastError());
+    return (int)SGW_OK;
+  };
+  if (T < step_graphs_min_T()) return launches(st);
+  GraphKey<1> key; memset(&key, 0, sizeof(key));
+  key.actions[0] = actions_out_dev; key.epochs[0] = e->arg_epoch; key.pol = *p; key.obs0 = obs0_dev;
+  key.n = 1; key.T = T; key.write_every = write_every != 0; key.accumulate = accumulate != 0; key.has_out = 1;
+  key.outs[0] = *out;
+  return e->policy_graphs.run(e->graph_owner, key, 2LL * T + 1, launches, st, "sgw_policy_step_n");
 }
 
 }  // extern "C"

@@ -334,8 +334,8 @@ struct StageRow {
 
 // ---- Philox-4x32-10 (same stream as ai_safety_gridworlds_amd/philox.py) ---------------------
 struct U4 { uint32_t x, y, z, w; };
-__device__ inline U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                   uint32_t k0, uint32_t k1) {
+__host__ __device__ inline U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                            uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
     uint64_t p0 = (uint64_t)0xD2511F53u * c0;
@@ -349,7 +349,7 @@ __device__ inline U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32
   }
   return U4{c0, c1, c2, c3};
 }
-enum { TAG_ACTION = 0, TAG_EPISODE = 1 };
+enum { TAG_ACTION = 0, TAG_EPISODE = 1, TAG_POLICY = 2 };   // TAG_POLICY: the exploration draws of a table policy (sgw_policy.hpp)
 __device__ inline int synth_action(unsigned long long seed, long long env_id, long long step,
                                    int agent, int lo, int n) {
   U4 r = philox4x32_10((uint32_t)step, TAG_ACTION, (uint32_t)agent, (uint32_t)((uint64_t)env_id >> 32),

@@ -781,6 +781,70 @@ class BatchedEngine(object):
             "sgw_scalarise")
     return out[:, 0] if A == 1 else out
 
+  # -- closed loop: table policies (policy.py) ------------------------------------------------
+  def _policy_source(self, policy, what):
+    """The engine's output buffer a policy reads, as its latest [N_pad, row] rows."""
+    if policy.device != self.device or policy.n_envs != self.n_envs or policy.spec is not self.spec:
+      raise N.SgwError("%s: the policy was built for another engine (spec, device or number of envs differ)" % what)
+    if policy.source not in self._bufs:
+      raise N.SgwError("%s: the policy reads the %r output, which this engine does not write (outputs=%r)" % (what, policy.source, self.outputs))
+    t = self._bufs[policy.source]
+    return t[-1] if self._T > 1 else t
+
+  def act(self, policy, obs=None, out=None, t=0):
+    """The actions a TablePolicy takes on `obs` (sgw_policy_act: one launch, no synchronisation): int8 [N, A].  obs: uint8
+    [N or N_pad, H*W] board rows / [N or N_pad, view_bytes] window rows on this device (default: the engine's current `board` /
+    `views` output).  The exploration draws are those of step policy.step + t; policy.step is not advanced.  out: an int8 [N, A]
+    tensor to write into (default: a persistent buffer of the engine, rewritten by the next call)."""
+    if obs is None:
+      obs = self._policy_source(policy, "act")
+    else:
+      src = self._policy_source(policy, "act")
+      row = src.shape[-1]
+      if (not torch.is_tensor(obs) or obs.device != self.device or obs.dtype != torch.uint8 or not obs.is_contiguous()
+          or obs.numel() not in (self.n_envs * row, self.n_pad * row)):
+        raise N.SgwError("act: obs must be a contiguous uint8 [%d or %d, %d] tensor on %s (there is no CPU path)"
+                         % (self.n_envs, self.n_pad, row, self.device))
+    if out is None:
+      out = getattr(self, "_act_out", None)
+      if out is None:
+        out = self._act_out = torch.zeros((self.n_envs, self.spec.A), dtype=torch.int8, device=self.device)
+    elif out.dtype != torch.int8 or out.device != self.device or not out.is_contiguous() or out.numel() != self.n_envs * self.spec.A:
+      raise N.SgwError("act: out must be a contiguous int8 [N, A] tensor on %s" % (self.device,))
+    N.check(self._lib.sgw_policy_act(self._h, C.byref(policy.native()), obs.data_ptr(), int(t), out.data_ptr(), self._stream()),
+            "sgw_policy_act")
+    return out.reshape(self.n_envs, self.spec.A)
+
+  def policy_step_n(self, policy, T, write_every=False, accumulate=False):
+    """T closed-loop steps from ONE library call (sgw_policy_step_n): the policy reads what the last step (or reset) wrote, its
+    actions are played by the ordinary step launch, T times, and policy.step advances by T.  Returns the last step's arrays, or
+    [T, N, ...] arrays with write_every, plus "actions" int8 [T, N, A]: the tape that was played (step_n over it reproduces the
+    outputs).  The buffers are persistent per (T, write_every), so from the third identical call on (T >= 8) the 2T + 1 launches
+    are one graph replay; the policy's tensors are read through their pointers, so weights rewritten in place take effect.
+    Source 'views' needs a spec whose step launch writes the windows itself (fused_views)."""
+    T = int(T)
+    if T < 1:
+      raise ValueError("policy_step_n: T must be >= 1")
+    if policy.source == "views" and not fused_views(self.spec):
+      raise N.SgwError("policy_step_n: this spec's windows do not come from the step launch (fused_views is false): "
+                       "the closed loop over windows is not available for it")
+    obs0 = self._policy_source(policy, "policy_step_n")
+    want_T = T if write_every else 1
+    if self._T != want_T:                   # the new buffers start from the observation the envs are at
+      keep = obs0.clone()
+      self._alloc_outputs(want_T)
+      obs0 = self._policy_source(policy, "policy_step_n")
+      obs0.copy_(keep)
+    tapes = self.__dict__.setdefault("_policy_tapes", {})
+    acts = tapes.get(T)
+    if acts is None:
+      acts = tapes[T] = torch.zeros((T, self.n_envs, self.spec.A), dtype=torch.int8, device=self.device)
+    N.check(self._lib.sgw_policy_step_n(self._h, C.byref(policy.native()), obs0.data_ptr(), T, 1 if write_every else 0, C.byref(self._out),
+                                        acts.data_ptr(), 1 if accumulate else 0, self._stream()), "sgw_policy_step_n")
+    res = self._views()
+    res["actions"] = acts
+    return res
+
   def observe_layers(self, board=None, agent_pos=None, agent_flags=None):
     """Unoccluded per-character layers with the gap correction: uint8 [N, L, H, W], L = len(spec.layer_chars)
     (what the MO/MA envs put in observation['layers']: rendering.py:188-302, observation_distiller_ex.py:164-178)."""

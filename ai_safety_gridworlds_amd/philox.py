@@ -11,7 +11,8 @@ launch shape (SURVEY.md §8d "Synthetic inputs").
   action  = lo + ((x0 * n_actions) >> 32)          # multiply-shift, x0 = word 0
 
 stream_tag separates uses: 0 = actions, 1 = per-episode Bernoulli draws
-(safe_interruptibility should_interrupt), 2 = reserved.
+(safe_interruptibility should_interrupt), 2 = the exploration draws of a table policy
+(policy.py: word 0 decides whether the agent explores, word 1 picks the action).
 """
 import numpy as np
 
@@ -23,6 +24,7 @@ _MASK = np.uint64(0xFFFFFFFF)
 
 TAG_ACTION = 0
 TAG_EPISODE = 1
+TAG_POLICY = 2
 
 
 def philox4x32_10(c0, c1, c2, c3, k0, k1):

@@ -334,6 +334,50 @@ int sgw_scalarise(sgw_engine* e, const double* reward_dev, const double* cumulat
                   const int32_t* k_agent, double* scalar_reward_dev, double* scalar_cumulative_dev, double* scalar_average_dev,
                   void* stream);
 
+/* Closed-loop stepping: a TABLE POLICY evaluated on the device, so that actions may depend on what the envs just returned
+ * without a host round trip.  The policy is a linear score over the one-hot encoding of the observation bytes.  For env n and
+ * agent a, with p = policy_of_env ? policy_of_env[n] : 0 (p outside 0 .. n_policies-1: the env's actions are written as 0 and no
+ * table is read) and o[0 .. C_a) the agent's observation bytes -- SGW_POLICY_BOARD: the env's row of the `board` output, C_a =
+ * H*W, the same bytes for every agent; SGW_POLICY_VIEWS: agent a's window inside the env's row of the `views` output (byte
+ * offset = the sum of the previous agents' window sizes), C_a = h_a * w_a, 0 for an agent without a window:
+ *   score[j] (float32, j = 0 .. n_actions-1) starts at bias[p][a][j] (+0.0f without a bias); then ONE float32 addition per cell,
+ *   c = 0, 1, ..., C_a-1 in that order: score[j] += weights[p][a][c][code_of[o[c]]][j].  No multiply, no reassociation.
+ *   best = 0; for j = 1 .. n_actions-1: if (score[j] > score[best]) best = j   (the first maximum wins; a NaN never displaces)
+ *   (x0, x1, _, _) = Philox-4x32-10(counter = (step, 2, a, env_id >> 32), key = (seed, env_id)), env_id the global env id,
+ *   step = *step_dev + t; the agent explores iff (uint64)x0 < explore_below (0 = never, 2^32 = always), taking index
+ *   (x1 * n_actions) >> 32 instead of best.
+ *   actions[n][a] = action_lo + index (int8), for every agent, finished ones included (as sgw_rollout's synthetic stream).
+ * Rows n >= N are neither read nor written.  n_actions and action_lo are the spec's; n_actions <= 16 (SGW_ERR_UNSUPPORTED beyond). */
+enum { SGW_POLICY_BOARD = 0, SGW_POLICY_VIEWS = 1 };
+typedef struct sgw_policy {
+  int32_t source, n_policies, n_codes, cells;   /* cells = C: H*W, or the largest window's h*w (agent a uses its first C_a) */
+  const uint8_t* code_of;                       /* [256] byte -> code in 0..n_codes-1 */
+  const float* weights;                         /* [P, A, C, n_codes, n_actions] */
+  const float* bias;                            /* [P, A, n_actions] or NULL */
+  const int32_t* policy_of_env;                 /* [N] or NULL */
+  uint64_t explore_below, seed;
+  int64_t* step_dev;                            /* [1]; required */
+} sgw_policy;
+int sgw_sizeof_policy(void);
+/* One launch: the actions of step *step_dev + t from obs_dev ([N_pad, H*W] for BOARD, [N_pad, view_bytes] for VIEWS; 16-byte
+ * aligned) into actions_dev int8 [N, A].  *step_dev is read when the launch runs and is not advanced.  All pointers of `p` are
+ * device pointers; every entry of code_of must be < n_codes (unchecked on the device).  Capturable. */
+int sgw_policy_act(sgw_engine* e, const sgw_policy* p, const uint8_t* obs_dev, int64_t t, int8_t* actions_dev, void* stream);
+/* T closed-loop steps in one call, 2T + 1 launches on `stream`: for t = 0 .. T-1 sgw_policy_act(t) reads obs0_dev at t == 0 and
+ * afterwards what step t-1 wrote (out->board or out->views; row t-1 of it with write_every != 0) and writes row t of
+ * actions_out_dev int8 [T, N, A]; then the ordinary sgw_step launch plays that row (write_every / accumulate as for
+ * sgw_step_n).  At the end *step_dev += T.  With write_every == 0, obs0_dev == out->board (out->views) is the normal call.
+ * Identical, output for output and action for action, to a host loop of sgw_policy_act + sgw_step.
+ * T >= 8: the second call with the same (policy struct, obs0_dev, T, write_every, out pointers, actions_out_dev, accumulate) captures
+ * the chain -- one serial chain of kernel nodes -- into a hipGraph of the engine's own cache (64 entries, apart from
+ * sgw_step_n's) and replays it from then on.  Tables, policy_of_env and *step_dev are read through their pointers when the
+ * launches run: rewrite the weights in place between calls and every call is still one replay.
+ * SGW_ERR_ARG: a null engine or required pointer; source not BOARD / VIEWS; n_policies < 1; n_codes outside 1..64; cells smaller
+ * than the source needs; VIEWS on a spec without windows or with out->views == NULL; BOARD with out->board == NULL;
+ * explore_below > 2^32; T < 1; obs not 16-byte aligned. */
+int sgw_policy_step_n(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, int T, int write_every,
+                      const sgw_out* out, int8_t* actions_out_dev /* [T, N, A] */, int accumulate, void* stream);
+
 /* Per-env performance bookkeeping of SafetyEnvironment{,Mo}: _episodic_performances.append(...) at every LAST timestep
  * (safety_game.py:253-263, 301-302; safety_game_mo.py:1015-1016), get_last_performance (229-251) and get_overall_performance =
  * sum(performances) / len(performances) (194-208, 234-244; safety_game_mo.py:917-938).  perf_dev double [N, C] is the step's
