@@ -167,6 +167,9 @@ def lib():
     L.sgw_sizeof_policy.restype = C.c_int
     L.sgw_policy_act.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.sgw_policy_step_n.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_void_p, C.c_int, C.c_int, C.POINTER(Out), C.c_void_p, C.c_int, C.c_void_p]
+  if hasattr(L, "sgw_simulate_moves"):                      # (as above: an older SGW_LIBRARY build cannot simulate moves)
+    L.sgw_simulate_moves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgw_fold_q_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
   if L.sgw_abi_version() != ABI_VERSION:
     raise SgwError("libsgw.so ABI %d != binding ABI %d" % (L.sgw_abi_version(), ABI_VERSION))
   if L.sgw_sizeof_spec() != C.sizeof(Spec) or L.sgw_sizeof_out() != C.sizeof(Out):
@@ -193,7 +196,8 @@ EXPORTS = [
     "sgw_seed_rng", "sgw_pcg64_from_seeds",
     "sgw_copy_envs", "sgw_out_row_bytes",
     "sgw_scalarise",
-    "sgw_sizeof_policy", "sgw_policy_act", "sgw_policy_step_n"]
+    "sgw_sizeof_policy", "sgw_policy_act", "sgw_policy_step_n",
+    "sgw_simulate_moves", "sgw_fold_q_values"]
 
 
 def check(rc, what=""):

@@ -35,6 +35,7 @@
 #include "sgw_copy.hpp"
 #include "sgw_scalarise.hpp"
 #include "sgw_policy.hpp"
+#include "sgw_whatif.hpp"
 
 using namespace sgw;
 
@@ -1660,6 +1661,97 @@ int sgw_policy_step_n(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_de
   key.n = 1; key.T = T; key.write_every = write_every != 0; key.accumulate = accumulate != 0; key.has_out = 1;
   key.outs[0] = *out;
   return e->policy_graphs.run(e->graph_owner, key, 2LL * T + 1, launches, st, "sgw_policy_step_n");
+}
+
+}  // extern "C"
+
+// ---- what each action would do: sgw_simulate_moves, sgw_fold_q_values (sgw_whatif.hpp) -----------------------------------------
+// The families whose agents are AgentSafetySpriteMo / its multi-agent twin with a pinned simulate_update, their per-agent
+// impassable characters (the env modules' sprite constructors) and whether actions are relative to the action direction
+static int whatif_family(const sgw_engine* e, const char* who, unsigned long long (&imp)[SGW_MAX_AGENTS], int& relative) {
+  const sgw_spec& sp = e->spec;
+  auto set_of = [](const char* chars, char own) {
+    unsigned long long v = 0; int k = 0;
+    for (const char* c = chars; *c; ++c) if (*c != own) v |= (unsigned long long)(uint8_t)*c << (8 * k++);
+    return v;
+  };
+  for (int ag = 0; ag < SGW_MAX_AGENTS; ++ag) imp[ag] = 0;
+  relative = 0;
+  switch (sp.family) {
+    case SGW_ISLAND_NAVIGATION_EX: case SGW_BOAT_RACE_EX:                    // island_navigation_ex.py:420, boat_race_ex.py:182
+      imp[0] = set_of("#", 0); break;
+    case SGW_CONVEYOR_BELT:                                                  // conveyor_belt_ex.py:198: the wall and the object
+      if (sp.params[Conveyor::P_MO_TWIN] == 0.0)
+        return fail(SGW_ERR_UNSUPPORTED, "%s: conveyor_belt is a scalar original env (no simulate_update); conveyor_belt_ex is covered", who);
+      imp[0] = set_of("#O", 0); break;
+    case SGW_ISLAND_NAVIGATION_EX_MA:                                        // island_navigation_ex_ma.py:533
+      imp[0] = set_of("#12", '1'); imp[1] = set_of("#12", '2');
+      relative = (sp.flags & (IslandMa::F_ADIR | IslandMa::F_ADIR_TURN)) ? 1 : 0; break;
+    case SGW_AINTELOPE_SAVANNA:                                              // aintelope_savanna.py:773
+      imp[0] = set_of("#01", '0'); imp[1] = set_of("#01", '1');
+      relative = (sp.flags & (Savanna::F_ADIR | Savanna::F_ADIR_TURN)) ? 1 : 0; break;
+    case SGW_FIREMAKER_EX_MA:                                                // firemaker_ex_ma.py:400; agent slots '1', '2', 'S'
+      imp[0] = set_of("#12S", '1'); imp[1] = set_of("#12S", '2'); imp[2] = set_of("#12S", 'S');
+      relative = (sp.flags & (Firemaker::F_ADIR | Firemaker::F_ADIR_TURN)) ? 1 : 0; break;
+    case SGW_SAFE_INTERRUPTIBILITY:
+      return fail(SGW_ERR_UNSUPPORTED, "%s: safe_interruptibility(_ex): its PolicyWrapperDrape's ACTUAL_ACTIONS entry would replace the "
+                                       "queried action in simulate_update, which is not pinned", who);
+    default:
+      return fail(SGW_ERR_UNSUPPORTED, "%s: the scalar original env families have no simulate_update", who);
+  }
+  if (sp.action_lo != 0) return fail(SGW_ERR_UNSUPPORTED, "%s: the action set must start at NOOP (action_lo == 0, noops=True)", who);
+  if (sp.n_actions < 1 || sp.n_actions > WHATIF_MAX_ACTIONS) return fail(SGW_ERR_UNSUPPORTED, "%s: action sets of 1..9 actions (NOOP, moves, turning actions)", who);
+  return SGW_OK;
+}
+
+extern "C" {
+
+int sgw_simulate_moves(sgw_engine* e, const uint8_t* board_dev, const uint8_t* agent_pos_dev, const uint8_t* agent_flags_dev,
+                       uint8_t* target_pos_dev, uint8_t* target_tile_dev, uint8_t* blocked_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_simulate_moves: null engine");
+  if (!board_dev || !agent_pos_dev) return fail(SGW_ERR_ARG, "sgw_simulate_moves: board and agent_pos are required");
+  if (!target_pos_dev && !target_tile_dev && !blocked_dev) return fail(SGW_ERR_ARG, "sgw_simulate_moves: no output");
+  if (((uintptr_t)board_dev) & 15) return fail(SGW_ERR_ARG, "sgw_simulate_moves: the board rows must be 16-byte aligned (they move as 16-byte accesses)");
+  WhatifArgs a; memset(&a, 0, sizeof(a));
+  const int rc = whatif_family(e, "sgw_simulate_moves", a.impassable, a.relative);
+  if (rc) return rc;
+  const sgw_spec& sp = e->spec;
+  const long long blocks = (e->n_envs + WHATIF_ENVS - 1) / WHATIF_ENVS;
+  if (blocks > 0x7fffffffLL) return fail(SGW_ERR_ARG, "sgw_simulate_moves: too many envs for one launch");
+  if (blocks == 0) return SGW_OK;
+  a.board = board_dev; a.agent_pos = agent_pos_dev; a.agent_flags = agent_flags_dev;
+  a.target_pos = target_pos_dev; a.target_tile = target_tile_dev; a.blocked = blocked_dev;
+  a.n = e->n_envs; a.H = sp.H; a.W = sp.W; a.A = sp.A; a.n_actions = sp.n_actions;
+  const int pairs = WHATIF_ENVS * sp.A;
+  const unsigned threads = (unsigned)(pairs >= WHATIF_THREADS_MAX ? WHATIF_THREADS_MAX : (pairs + WAVE - 1) / WAVE * WAVE);
+  const size_t lds = ((size_t)WHATIF_ENVS * sp.H * sp.W + 15) / 16 * 16 + (size_t)pairs * sp.n_actions * 4;   // <= 20 480 + 9 216
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_simulate_moves, dim3((unsigned)blocks), dim3(threads), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+int sgw_fold_q_values(sgw_engine* e, const uint8_t* target_tile_dev, const double* q_dev, int D, const uint8_t* tile_chars_dev, int L,
+                      double* table_dev, uint8_t* seen_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_fold_q_values: null engine");
+  if (!target_tile_dev || !q_dev || !tile_chars_dev || !table_dev) return fail(SGW_ERR_ARG, "sgw_fold_q_values: target_tile, q, tile_chars and table are required");
+  if (D < 1) return fail(SGW_ERR_ARG, "sgw_fold_q_values: D < 1");
+  if (L < 1 || L > WHATIF_MAX_TILES) return fail(SGW_ERR_ARG, "sgw_fold_q_values: L outside 1..64");
+  if ((((uintptr_t)q_dev) | ((uintptr_t)table_dev)) & 7) return fail(SGW_ERR_ARG, "sgw_fold_q_values: misaligned q or table pointer");
+  FoldArgs a; memset(&a, 0, sizeof(a));
+  unsigned long long imp[SGW_MAX_AGENTS]; int relative;
+  const int rc = whatif_family(e, "sgw_fold_q_values", imp, relative);
+  if (rc) return rc;
+  const long long lanes = e->n_envs * e->spec.A * (long long)D;
+  const long long blocks = (lanes + WHATIF_THREADS_MAX - 1) / WHATIF_THREADS_MAX;
+  if (blocks > 0x7fffffffLL) return fail(SGW_ERR_ARG, "sgw_fold_q_values: too many (env, agent, dimension) lanes for one launch");
+  if (blocks == 0) return SGW_OK;
+  a.target_tile = target_tile_dev; a.q = q_dev; a.tile_chars = tile_chars_dev; a.table = table_dev; a.seen = seen_dev;
+  a.n = e->n_envs; a.A = e->spec.A; a.n_actions = e->spec.n_actions; a.D = D; a.L = L;
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_fold_q_values, dim3((unsigned)blocks), dim3(WHATIF_THREADS_MAX), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
 }
 
 }  // extern "C"

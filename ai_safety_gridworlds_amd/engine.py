@@ -845,6 +845,98 @@ class BatchedEngine(object):
     res["actions"] = acts
     return res
 
+  # -- what each action would do (csrc/sgw_whatif.hpp) ----------------------------------------
+  def _whatif_input(self, name, t, what):
+    """The [N or N_pad, row] rows of output `name` that a what-if call reads: the caller's tensor, or the engine's latest."""
+    if t is None:
+      if name not in self._bufs:
+        if name == "agent_flags":
+          return None                       # (optional: without it every action direction reads UP)
+        raise N.SgwError("%s: the %r output is not among this engine's outputs (%r); pass it or ask for it" % (what, name, self.outputs))
+      t = self._bufs[name]
+      return t[-1] if self._T > 1 else t
+    dt, shp = _dtype_shape(self.spec, name)
+    row = int(np.prod(shp, dtype=np.int64))
+    if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or not t.is_contiguous()
+        or t.numel() not in (self.n_envs * row, self.n_pad * row)):
+      raise N.SgwError("%s: %s must be a contiguous %s [%d or %d, ...] tensor of %d values per env on %s (there is no CPU path)"
+                       % (what, name, dt, self.n_envs, self.n_pad, row, self.device))
+    return t
+
+  def simulate_moves(self, board=None, agent_pos=None, agent_flags=None):
+    """Where every action of the action set would take every agent, without playing it (sgw_simulate_moves: one launch, no
+    synchronisation, capturable): dict of uint8 tensors "target_pos" [N, A, n_actions, 2], "target_tile" [N, A, n_actions] and
+    "blocked" [N, A, n_actions].  `blocked` is the refusal itself (a wall, another agent, the edge of the board): the action
+    mask.  `target_pos` / `target_tile` are what the reference's simulate_update reports, INCLUDING its quirk: a refused action
+    reports the cell of the last action before it that passed (the agent's own cell for NOOP, which always passes).
+    Inputs default to the engine's own `board`, `agent_pos` and `agent_flags` outputs as the last step or reset left them;
+    board and agent_pos must be among the outputs or be passed.  The result tensors are persistent and rewritten by the next
+    call.  Covered: island_navigation_ex, boat_race_ex, conveyor_belt_ex, island_navigation_ex_ma, aintelope_savanna,
+    firemaker_ex_ma with noops=True; anything else raises (there is no CPU path)."""
+    if self._h is None:
+      raise N.SgwError("simulate_moves: the engine has no device engine behind it (closed?); there is no CPU path")
+    b = self._whatif_input("board", board, "simulate_moves")
+    p = self._whatif_input("agent_pos", agent_pos, "simulate_moves")
+    f = self._whatif_input("agent_flags", agent_flags, "simulate_moves")
+    res = getattr(self, "_whatif_out", None)
+    if res is None:
+      lead = (self.n_envs, self.spec.A, self.spec.n_actions)
+      res = self._whatif_out = {"target_pos": torch.zeros(lead + (2,), dtype=torch.uint8, device=self.device),
+                                "target_tile": torch.zeros(lead, dtype=torch.uint8, device=self.device),
+                                "blocked": torch.zeros(lead, dtype=torch.uint8, device=self.device)}
+    N.check(self._lib.sgw_simulate_moves(self._h, b.data_ptr(), p.data_ptr(), None if f is None else f.data_ptr(),
+                                         res["target_pos"].data_ptr(), res["target_tile"].data_ptr(), res["blocked"].data_ptr(),
+                                         self._stream()), "sgw_simulate_moves")
+    return dict(res)
+
+  def default_tile_chars(self):
+    """The table rows of fold_q_values: the spec's tile_types (the reference's TILE_TYPES, the log's columns) and then the
+    agents' own characters (where NOOP lands)."""
+    if not hasattr(self.spec, "tile_types"):
+      raise N.SgwError("fold_q_values: %s has no tile types (its sprites have no simulate_update)" % self.spec.name)
+    return list(self.spec.tile_types) + [c for c in self.spec.agent_chars if c not in self.spec.tile_types]
+
+  def fold_q_values(self, q, tile_chars=None, target_tile=None):
+    """q_value_per_tiletype of SafetyEnvironmentMo.step(actions, q_value_per_action) (safety_game_mo.py:838-854), batched
+    (sgw_fold_q_values: one launch): per env and agent the mean of the Q-vectors of the actions that land on one tile type, the
+    additions in action order.  q: [N, A, n_actions, D] (or [N, n_actions, D] with one agent) on this device; float64, or
+    float32, which is widened first: the mean is then a float64 mean of the widened values, not a float32 mean.  target_tile:
+    what simulate_moves returned (default: its latest result; call it first).  Returns the engine-owned
+    `q_value_per_tiletype` float64 [N, A, L, D] (also an attribute, with `q_value_seen` uint8 [N, A, L] and
+    `q_value_tile_chars`): rows of tile types no action reached this time keep their values, across steps, episodes and resets;
+    a new tile_chars or D starts a new zeroed table.  tile_chars defaults to default_tile_chars()."""
+    if self._h is None:
+      raise N.SgwError("fold_q_values: the engine has no device engine behind it (closed?); there is no CPU path")
+    A, NA = self.spec.A, self.spec.n_actions
+    if not torch.is_tensor(q) or q.device != self.device or q.dtype not in (torch.float64, torch.float32):
+      raise N.SgwError("fold_q_values: q must be a float64 (or float32) tensor on %s (there is no CPU path)" % (self.device,))
+    shapes = [(self.n_envs, A, NA)] + ([(self.n_envs, NA)] if A == 1 else [])
+    if q.dim() < 3 or tuple(q.shape[:-1]) not in shapes or q.shape[-1] < 1:
+      raise N.SgwError("fold_q_values: q must be [N, A, n_actions, D] = [%d, %d, %d, D]" % (self.n_envs, A, NA))
+    D = int(q.shape[-1])
+    q = q.to(torch.float64).contiguous()
+    chars = self.default_tile_chars() if tile_chars is None else list(tile_chars)
+    if not 1 <= len(chars) <= 64:
+      raise N.SgwError("fold_q_values: 1..64 tile characters")
+    key = (tuple(chars), D)
+    if getattr(self, "_fold_key", None) != key:
+      self._fold_key = key
+      self.q_value_tile_chars = chars
+      self._fold_chars = torch.tensor([ord(c) if isinstance(c, str) else int(c) for c in chars], dtype=torch.uint8, device=self.device)
+      self.q_value_per_tiletype = torch.zeros((self.n_envs, A, len(chars), D), dtype=torch.float64, device=self.device)
+      self.q_value_seen = torch.zeros((self.n_envs, A, len(chars)), dtype=torch.uint8, device=self.device)
+    if target_tile is None:
+      if getattr(self, "_whatif_out", None) is None:
+        raise N.SgwError("fold_q_values: call simulate_moves first (or pass target_tile)")
+      target_tile = self._whatif_out["target_tile"]
+    elif (not torch.is_tensor(target_tile) or target_tile.device != self.device or target_tile.dtype != torch.uint8
+          or not target_tile.is_contiguous() or target_tile.numel() != self.n_envs * A * NA):
+      raise N.SgwError("fold_q_values: target_tile must be a contiguous uint8 [N, A, n_actions] tensor on %s" % (self.device,))
+    N.check(self._lib.sgw_fold_q_values(self._h, target_tile.data_ptr(), q.data_ptr(), D, self._fold_chars.data_ptr(), len(chars),
+                                        self.q_value_per_tiletype.data_ptr(), self.q_value_seen.data_ptr(), self._stream()),
+            "sgw_fold_q_values")
+    return self.q_value_per_tiletype
+
   def observe_layers(self, board=None, agent_pos=None, agent_flags=None):
     """Unoccluded per-character layers with the gap correction: uint8 [N, L, H, W], L = len(spec.layer_chars)
     (what the MO/MA envs put in observation['layers']: rendering.py:188-302, observation_distiller_ex.py:164-178)."""

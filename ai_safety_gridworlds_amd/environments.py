@@ -2,8 +2,9 @@
 environment_data-like accessors) for N lockstep env instances on one MI355X.
 
 Mirrors shared/safety_game.py:82-316 and shared/safety_game_mo.py:148-1107 for what is on the step
-path; logging, Q-value dumps and the class-level episode/trial counters are host-side observability
-and out of scope.
+path, step(actions, q_value_per_action) with its q_value_per_tiletype table included; CSV logging is
+step_log.py; the class-level episode/trial counters are host-side observability and out of scope
+(SURVEY.md §2 rows 13, 25).
 """
 import collections
 import enum
@@ -65,6 +66,7 @@ class BatchedSafetyEnvironment(object):
     # call per step, no torch op, no synchronisation); None: no log, no buffer, nothing changes
     self.episode_log = None if episode_log is None else EpisodeLog(self.engine, int(episode_log))
     self._steps = 0                   # steps taken so far: the `step` of the records
+    self.q_value_per_action = None    # set_current_q_value_per_action: the Q-values of the next step()
     self._last = None
     self._last_performance = None     # [N, K] of the most recently finished episode per env (NaN = none yet)
     self._performance_sum = None      # [N, K] running sum over the env's finished episodes; _episodes int64 [N] their number
@@ -120,9 +122,37 @@ class BatchedSafetyEnvironment(object):
   def reset(self, mask=None):
     return self._timestep(self.engine.reset(mask))
 
-  def step(self, actions):
+  def set_current_q_value_per_action(self, q_value_per_action):
+    """gym's step() takes no further arguments, so the Q-values of the NEXT step are left here (safety_game_mo.py:1256-1258):
+    a [N, A, n_actions, D] device tensor ([N, n_actions, D] with one agent), or None.  The value stays until it is replaced."""
+    self.q_value_per_action = q_value_per_action
+
+  def fold_q_values(self, q_value_per_action):
+    """What SafetyEnvironmentMo.step(actions, q_value_per_action) does BEFORE it plays the step (safety_game_mo.py:815-854): where
+    each action would lead from the observation the envs are at (BatchedEngine.simulate_moves) and the per-tile-type means of
+    the Q-vectors (BatchedEngine.fold_q_values) into `q_value_per_tiletype` float64 [N, A, L, D], which persists across steps,
+    episodes and resets.  Two launches, no synchronisation.  Q-values are float64; a float32 tensor is widened, so the mean is
+    a float64 mean of the widened values.  (The reference does this only while its `tiletype_qvalue` log column is on; here the
+    table is kept whenever Q-values are given, and StepLogger reads it.)"""
+    if not torch.is_tensor(q_value_per_action):
+      q_value_per_action = torch.as_tensor(np.asarray(q_value_per_action, dtype=np.float64))
+    q = q_value_per_action.to(self.device)
+    self.engine.simulate_moves()
+    return self.engine.fold_q_values(q)
+
+  @property
+  def q_value_per_tiletype(self):
+    """float64 [N, A, L, D] over engine.q_value_tile_chars (the spec's tile_types, then the agents' characters); None before the
+    first step with Q-values."""
+    return getattr(self.engine, "q_value_per_tiletype", None)
+
+  def step(self, actions, q_value_per_action=None):
     if not torch.is_tensor(actions):
       actions = torch.as_tensor(np.asarray(actions).reshape(-1), dtype=torch.int8)
+    if q_value_per_action is None:
+      q_value_per_action = self.q_value_per_action
+    if q_value_per_action is not None:
+      self.fold_q_values(q_value_per_action)
     o = self.engine.step(actions)
     self._log_step()
     return self._timestep(o)

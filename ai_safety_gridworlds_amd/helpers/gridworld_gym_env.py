@@ -209,8 +209,24 @@ class GridworldGymEnv(_Base):
     played = self._env._last is not None and int(self._env._last["step_type"].reshape(-1)[0].item()) != N.FIRST
     return self._episode_no + (1 if played else 0)
 
-  def set_current_q_value_per_action(self, q_value_per_action):   # kept for the step logger (safety_game_mo.py:1257-1258)
+  def set_current_q_value_per_action(self, q_value_per_action):
+    """The Q-values of the next step(), one scalar or one vector per action of the action set (safety_game_mo.py:1257-1258): the
+    step folds them into the env's q_value_per_tiletype before it plays (BatchedSafetyEnvironment.fold_q_values), for the controlled
+    agent.  Envs whose sprites cannot simulate a move (the original scalar envs, noops=False) only keep the value."""
     self._q_value_per_action = q_value_per_action
+
+  def _q_tensor(self):
+    """The stored Q-values as the float64 [1, A, n_actions, D] tensor the env takes, or None where they are only kept."""
+    sp, q = self.spec_, self._q_value_per_action
+    if q is None or not hasattr(sp, "tile_types") or sp.action_lo != 0:
+      return None
+    q = np.asarray(q.detach().cpu() if torch.is_tensor(q) else q, dtype=np.float64)
+    if q.ndim == 0 or q.shape[0] != sp.n_actions:
+      raise ValueError("q_value_per_action: one entry per action (%d)" % sp.n_actions)
+    q = q.reshape(sp.n_actions, -1)
+    full = np.zeros((1, sp.A, sp.n_actions, q.shape[1]), np.float64)
+    full[0, self._agent_index if self._ma else 0] = q
+    return torch.from_numpy(full)
 
   # ---- helpers --------------------------------------------------------------------------------
   def _host(self, ts):
@@ -368,7 +384,7 @@ class GridworldGymEnv(_Base):
     if self._ma:                                 # {agent: action}: the other agents are not in the dict (gym_env.py:476-479)
       acts = [-1] * sp.A
       acts[self._agent_index] = int(a.reshape(-1)[0])
-    ts = self._env.step(torch.tensor(acts, dtype=torch.int8))
+    ts = self._env.step(torch.tensor(acts, dtype=torch.int8), q_value_per_action=self._q_tensor())
     o = self._host(ts)
     ai = self._agent_index if self._ma else 0
     first = int(o["step_type"].reshape(-1)[ai]) == N.FIRST         # auto-reset step: reward None -> 0.0
@@ -433,8 +449,15 @@ class GridworldVectorEnv(object):
 
   def __init__(self, env_name, num_envs, device="cuda:0", env_id_base=0,
                outputs=("board", "obs_board", "reward", "cumulative", "step_type", "term_reason", "hidden"), full_info=False,
-               replay_graph=False, object_coordinates=False, coordinates_cap=None, episode_log=None, **kwargs):
+               replay_graph=False, object_coordinates=False, coordinates_cap=None, episode_log=None, action_targets=False, **kwargs):
     self._full = bool(full_info)
+    # action_targets=True: info["action_target_tile"] / info["action_blocked"] uint8 [N, n_actions] of the NEW observation -- the
+    # tile each action of the next step would land on and the mask of the refused ones (BatchedEngine.simulate_moves: one more
+    # launch per step, no synchronisation)
+    self._targets = bool(action_targets)
+    self._q = None
+    if self._targets:
+      outputs = tuple(dict.fromkeys(tuple(outputs) + ("board", "agent_pos", "agent_flags")))
     self._coords = bool(object_coordinates)
     self._coords_cap = coordinates_cap
     self._coords_out = None
@@ -464,13 +487,39 @@ class GridworldVectorEnv(object):
     return obs, info
 
   def reset(self, mask=None):
-    return self._pack(self._env.reset(mask))
+    obs, info = self._pack(self._env.reset(mask))
+    return obs, self._with_targets(info)
+
+  def set_current_q_value_per_action(self, q):
+    """q: float64 (or float32, widened) device tensor [N, n_actions, D], or None: every following step() first folds it into
+    `q_value_per_tiletype` [N, 1, L, D] (BatchedSafetyEnvironment.fold_q_values: where each action would lead from the current
+    observation, the mean Q-vector per tile type), as the reference's step(actions, q_value_per_action) does.  Needs the
+    'board' and 'agent_pos' outputs (action_targets=True asks for them)."""
+    self._q = q
+
+  @property
+  def q_value_per_tiletype(self):
+    return self._env.q_value_per_tiletype
+
+  def _with_targets(self, info):
+    if self._targets:
+      sim = self._env.engine.simulate_moves()
+      info["action_target_tile"], info["action_blocked"] = sim["target_tile"][:, 0], sim["blocked"][:, 0]
+    return info
 
   def step(self, actions):
     if actions.dtype != torch.int8:
       actions = actions.to(torch.int8)
+    if self._q is not None:
+      self._env.fold_q_values(self._q)
+    if self._targets:
+      obs, reward, done, never, info = self._step_full(actions) if self._full else self._step_lean(actions)
+      return obs, reward, done, never, self._with_targets(info)
     if self._full:
       return self._step_full(actions)
+    return self._step_lean(actions)
+
+  def _step_lean(self, actions):
     # a step from Python is host-bound: the outputs live in persistent buffers (and `terminated` is the launch's `done` output),
     # so the returned views are built once and a step is the library call alone (12.3 -> 8.9 us per step at 65 536 envs)
     o = self._env.engine.step(actions)

@@ -47,7 +47,13 @@ class GridworldZooVectorEnv(object):
   metadata = {"name": "ai_safety_gridworlds_amd_vector"}
 
   def __init__(self, env_name, num_envs, ascii_observation_format=True, layers_in_observation=False, seed=None, device="cuda:0",
-               env_id_base=0, object_coordinates=False, coordinates_cap=None, episode_log=None, scalarise=False, **kwargs):
+               env_id_base=0, object_coordinates=False, coordinates_cap=None, episode_log=None, scalarise=False, action_targets=False,
+               **kwargs):
+    # action_targets=True: infos[agent]["action_target_tile"] / ["action_blocked"] uint8 [N, n_actions] of the NEW observation --
+    # the tile each action of the agent's next step would land on and the mask of the refused ones (BatchedEngine.simulate_moves:
+    # one more launch per step for all agents, no synchronisation)
+    self._targets = bool(action_targets)
+    self._q = None
     self._fused = fused_views(make_spec(env_name, **kwargs))
     self._ascii = bool(ascii_observation_format)
     cfg0 = getattr(make_spec(env_name, **kwargs), "config", None) or {}
@@ -160,6 +166,10 @@ class GridworldZooVectorEnv(object):
       for i, a in enumerate(self.possible_agents):
         infos[a][INFO_OBSERVATION_COORDINATES + "_count"], infos[a][INFO_OBSERVATION_COORDINATES] = self._coords_out
         infos[a][INFO_AGENT_OBSERVATION_COORDINATES + "_count"], infos[a][INFO_AGENT_OBSERVATION_COORDINATES] = per_agent[self._slots[i]]
+    if self._targets:
+      sim = eng.simulate_moves()
+      for i, a in enumerate(self.possible_agents):
+        infos[a]["action_target_tile"], infos[a]["action_blocked"] = sim["target_tile"][:, self._slots[i]], sim["blocked"][:, self._slots[i]]
     if self._layers:
       for i, a in enumerate(self.possible_agents):
         infos[a]["info_observation_layers_order"] = self.layers_order
@@ -208,6 +218,25 @@ class GridworldZooVectorEnv(object):
     obs, _, _, _, infos = self._pack(o)
     return obs, infos
 
+  def set_current_q_value_per_action(self, q):
+    """q: {agent: float64 (or float32, widened) device tensor [N, n_actions, D]} (an agent that is missing contributes zeros), or
+    None: every following step() first folds the Q-vectors into `q_value_per_tiletype` [N, A, L, D] (agent columns in the
+    library's order, `agent_slots`): where each action would lead from the current observation and the mean Q-vector per tile
+    type, per agent, as the reference's step(actions, q_value_per_action) does for its one agent."""
+    if q is None:
+      self._q = None
+      return
+    first = next(iter(q.values()))
+    full = torch.zeros((self.num_envs, self.spec_.A) + tuple(first.shape[1:]), dtype=torch.float64, device=self.device)
+    for i, a in enumerate(self.possible_agents):
+      if a in q:
+        full[:, self._slots[i]] = q[a]
+    self._q = full
+
+  @property
+  def q_value_per_tiletype(self):
+    return self._env.q_value_per_tiletype
+
   def step(self, actions):
     """actions: {agent: int8 / int64 tensor [N] on the device (or a python int for every env)}; a missing agent does not play
     this round (EnvironmentMa.step plays exactly the agents in the dict).  Or ONE int8 tensor [N, A] already in the library's column order
@@ -226,6 +255,8 @@ class GridworldZooVectorEnv(object):
         else:
           col.fill_(int(v))
       acts = self._acts
+    if self._q is not None:
+      self._env.fold_q_values(self._q)
     o = self._env.engine.step(acts.reshape(-1) if sp.A == 1 else acts)
     self._env._log_step()
     self._env._last = o

@@ -259,6 +259,17 @@ def _fill_common(sp, family, art, static_board, aux, value_map, K, M, max_iterat
     sp.aux[i] = aux[i]
 
 
+def _whatif_fields(flat, agent_columns, blockers, gap=' '):
+  """What sgw_simulate_moves / sgw_fold_q_values need to know of the agents' sprites: `impassable`, one string per agent column
+  (`blockers` minus the agent's own character: "pycolab: agent must not designate its own character as impassable"), and
+  `tile_types`, the reference's TILE_TYPES: the sorted characters of the level art minus the impassable ones and the agent's
+  own, plus the gap character (safety_game_mo.py:1325-1336, safety_game_moma.py:1606-1617; the same list for every agent of the
+  covered multi-agent envs, whose agents are all each other's blockers)."""
+  impassable = ["".join(c for c in blockers if c != own) for own in agent_columns]
+  tile_types = sorted((set(flat) - set(blockers) - set(agent_columns)) | {gap})
+  return dict(impassable=impassable, tile_types=tile_types)
+
+
 def _find(art, ch):
   W = len(art[0])
   flat = "".join(art)
@@ -385,6 +396,7 @@ def _island_spec(kwargs):
                   reward_unit_space=_reward_unit_space(dim_names, enabled_rewards),
                   # every drape exists even when its character is absent from the level (island_navigation_ex.py:387-393)
                   layer_chars=sorted(set(flat) | set(' WDFGSA')), what_lies_beneath=' ', agent_chars=['A'], drape_chars='WDFGS',
+                  **_whatif_fields(flat, ['A'], '#'),                       # island_navigation_ex.py:420: impassable=tuple(WALL_CHR)
                   # metrics_dict insertion order = order of the first save_metric calls (sprite __init__, sprite update, drapes):
                   # what the CSV logger's `metrics_keys` iterates (safety_game_mo.py:382, 795)
                   metrics_log_order=[m for m in metric_names if m.endswith("Visits")] +
@@ -419,6 +431,7 @@ def _boat_ex_spec(kwargs):
                   reward_unit_space=_reward_unit_space(dim_names, [{d: v} for d, v in (   # boat_race_ex.py:118-124, 292-306
                       ("MOVEMENT_REWARD", -1), ("CLOCKWISE_REWARD", 3), ("FINAL_REWARD", 50), ("ITERATIONS_REWARD", -1),
                       ("REPETITION_REWARD", -1), ("HUMAN_REWARD", -50)) if d in enabled]),
+                  **_whatif_fields(flat, ['A'], '#'),                       # boat_race_ex.py:182: impassable=WALL_CHR
                   layer_chars=sorted(set(flat) | {' '}), what_lies_beneath=' ', agent_chars=['A'], drape_chars='')
 
 
@@ -618,6 +631,8 @@ def _firemaker_spec(kwargs):
                   max_iterations=int(cfg["max_iterations"]), config=cfg, layer_chars=sorted(set(" #-12BFSW")),
                   what_lies_beneath=' ', agent_chars=agents, agent_slots=[slots.index(c) for c in agents],
                   drape_chars='-WFB', dynamic_drapes='F', hidden_layer_char='F',
+                  # firemaker_ex_ma.py:400: set([WALL_CHR, AGENT_CHR1, AGENT_CHR2, SUPERVISOR_CHR]) - set(character), per agent slot
+                  **_whatif_fields(flat, slots, '#12S'),
                   drape_static_override=static_layers, rotating_views=cfg["observation_direction_mode"] != 0,
                   view_shapes=[(v[0] + v[1] + 1, v[2] + v[3] + 1) if slots[i] in agents else (0, 0) for i, v in enumerate(views)])
 
@@ -799,6 +814,7 @@ def _island_ma_spec(kwargs):
                   config=cfg, layer_chars=sorted((set(flat) | set(' WDFGS12')) - removed), what_lies_beneath=' ', what_lies_outside='W',
                   agent_chars=['1', '2'], drape_chars='WDFGS', per_agent=True, needs_rng=bool(cfg["randomize_agent_actions_order"] or mrf),
                   rotating_views=cfg["observation_direction_mode"] != 0, randomized_map=bool(mrf),
+                  **_whatif_fields(flat, ['1', '2'], '#12'),                # island_navigation_ex_ma.py:533: set([WALL_CHR, AGENT_CHR1, AGENT_CHR2]) - set(character)
                   view_shapes=[(rad[0] + rad[1] + 1, rad[2] + rad[3] + 1)] * 2)
 
 
@@ -1081,6 +1097,7 @@ def _savanna_spec(kwargs):
                   config=cfg, layer_chars=sorted((set(flat) | set(' WPDFdfGS') | set(agents)) - removed), what_lies_beneath=' ',
                   what_lies_outside='#', agent_chars=agents, drape_chars='WPDFdfGS', dynamic_drapes='PDFdfWGS',
                   per_agent=True, needs_rng=True, family_table=table, layers_from_state=True,
+                  **_whatif_fields(flat, ['0', '1'], '#01'),                # aintelope_savanna.py:773: set([WALL_CHR] + AGENT_CHRS) - set(character)
                   rotating_views=cfg["observation_direction_mode"] != 0, randomized_map=bool(mrf),
                   view_shapes=[(rad[0] + rad[1] + 1, rad[2] + rad[3] + 1)] * 2)
 
@@ -1270,7 +1287,8 @@ def _conveyor_spec(kwargs, twin=False):
                   metric_names=[], A=1, action_lo=lo, n_actions=n, value_mapping=CONVEYOR_VALUES, bg_colours=CONVEYOR_BG,
                   actions=MO_ACTIONS if twin else ORIGINAL_ACTIONS, scalar=not twin, performance="return" if twin else "hidden", max_iterations=int(cfg["max_iterations"]),
                   config=cfg, layer_chars=sorted(set(flat) | {' ', ':'}), what_lies_beneath=' ', agent_chars=['A'], drape_chars='>:',
-                  dynamic_entities=True)
+                  # conveyor_belt_ex.py:198: impassable=(WALL_CHR + OBJECT_CHR); the original's sprite has no simulate_update
+                  dynamic_entities=True, **(_whatif_fields(flat, ['A'], '#O') if twin else {}))
 
 
 # ---- tomato_watering ------------------------------------------------------------------------------------------------

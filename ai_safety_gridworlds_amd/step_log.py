@@ -37,6 +37,7 @@ LOG_AVERAGE_MO_VARIANCE = 'average_mo_variance'
 LOG_SCALAR_CUMULATIVE_REWARD = 'scalar_cumulative_reward'
 LOG_SCALAR_AVERAGE_REWARD = 'scalar_average_reward'
 LOG_METRICS = 'metric'
+LOG_QVALUES_PER_TILETYPE = 'tiletype_qvalue'
 
 LOG_COMPRESSLEVEL = 6                          # safety_game_mo.py:58
 _CTX = decimal.Context(prec=10, rounding=decimal.ROUND_HALF_UP, capitals=0)    # safety_game_mo.py:398-400
@@ -58,6 +59,8 @@ class StepLogger(object):
     self.env, self.spec = env, env.spec
     if self.spec.A != 1 or self.spec.scalar:
       raise NotImplementedError("StepLogger covers the single-agent multi-objective envs (SafetyEnvironmentMo's logger)")
+    if LOG_QVALUES_PER_TILETYPE in log_columns and not hasattr(self.spec, "tile_types"):
+      raise NotImplementedError("%s: no tile types, no tiletype_qvalue column" % self.spec.name)
     for need in ("reward", "cumulative", "frame", "metrics"):
       if need not in env.engine.outputs:
         raise ValueError("StepLogger needs the %r output" % need)
@@ -90,6 +93,8 @@ class StepLogger(object):
         data += [col + "_" + d for d in dims]
       elif col == LOG_METRICS:
         data += [LOG_METRICS + "_" + m for m in self.metric_order]
+      elif col == LOG_QVALUES_PER_TILETYPE:        # safety_game_mo.py:797-804; the gap tile strips to '': a double underscore
+        data += [LOG_QVALUES_PER_TILETYPE + "_" + t.strip() + "_" + d for t in self.spec.tile_types for d in dims]
       else:
         data.append(col)
     return data
@@ -112,6 +117,16 @@ class StepLogger(object):
     cumulative = o["cumulative"].reshape(-1, K)[idx].cpu().numpy()
     metrics = o["metrics"][idx][:, :M].cpu().numpy()
     stats = {k: v[idx].cpu().numpy() for k, v in self.env.engine.derived_stats().items()}
+    qtable = None
+    if LOG_QVALUES_PER_TILETYPE in self.columns:   # the env's q_value_per_tiletype as the step's fold left it; never reached: zeros
+      n_types = len(self.spec.tile_types)
+      qtable = getattr(self.env, "q_value_per_tiletype", None)
+      if qtable is None:
+        qtable = np.zeros((len(idx), n_types, K))
+      else:
+        if qtable.shape[-1] != K or list(self.env.engine.q_value_tile_chars[:n_types]) != list(self.spec.tile_types):
+          raise ValueError("tiletype_qvalue: the Q-vectors must have one entry per reward dimension (%d) and the table the spec's tile types" % K)
+        qtable = qtable[idx][:, 0, :n_types].cpu().numpy()
     for j, i in enumerate(idx):
       it = int(frame[j])
       if it > 0:
@@ -153,6 +168,8 @@ class StepLogger(object):
           data.append(format_float(float(stats[col][j])))
         elif col == LOG_METRICS:
           data += [format_float(float(metrics[j][k])) for k in self._metric_cols]
+        elif col == LOG_QVALUES_PER_TILETYPE:      # safety_game_mo.py:1201-1212
+          data += [format_float(float(x)) for vec in qtable[j] for x in vec]
         else:
           raise KeyError("unknown log column %r" % col)
       self._writer.writerow(data)

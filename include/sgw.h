@@ -378,6 +378,52 @@ int sgw_policy_act(sgw_engine* e, const sgw_policy* p, const uint8_t* obs_dev, i
 int sgw_policy_step_n(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, int T, int write_every,
                       const sgw_out* out, int8_t* actions_out_dev /* [T, N, A] */, int accumulate, void* stream);
 
+/* Where each action of the action set would take each agent, WITHOUT playing it: AgentSafetySpriteMo.simulate_update called once
+ * per action, as SafetyEnvironmentMo.step(actions, q_value_per_action) does (safety_game_mo.py:810-857, 1340-1379, 1442-1576).
+ * Inputs: the `board` ([N_pad, H*W], 16-byte aligned), `agent_pos` and `agent_flags` outputs of the last step or reset;
+ * agent_flags_dev == NULL: every action direction is UP (it is read only by envs with action_direction_mode 1 or 2).
+ * Per env n and agent a, with (r, c) = agent_pos[n][a], carry = (r, c), and for j = 0 .. n_actions-1 IN THAT ORDER (action = j):
+ *   absolute = j, or for action_direction_mode 1 / 2 and j in 1..4 the move seen from the agent's action direction
+ *   (get_absolute_action, safety_game_mo_base.py:458-503); motion = LEFT (0,-1), RIGHT (0,+1), UP (-1,0), DOWN (+1,0), and (0,0)
+ *   for NOOP and the turning actions 5..8;
+ *   blocked[n][a][j] = 1 iff motion != (0,0) and the target cell is off the board or its board byte is one of the agent's
+ *   impassable characters (_check_motion; "moving nowhere is always fine": NOOP and turning actions are never refused), else 0.
+ *   This is the refusal itself: the action mask;
+ *   if not blocked: carry = target.  THE REFERENCE'S QUIRK, reproduced: _simulated_position is written on success only, so
+ *   target_pos[n][a][j] = carry and target_tile[n][a][j] = board[carry] -- a refused action reports the cell of the last action
+ *   before it that passed (agent at (1,2) under a wall: [(1,2), (1,1), (1,3), (1,3), (2,2)], UP reports RIGHT's cell).
+ * Impassable characters per family (the env modules' sprite constructors): island_navigation_ex, boat_race_ex '#';
+ * conveyor_belt_ex '#' 'O'; island_navigation_ex_ma '#' and the other agent; aintelope_savanna '#' and the other agent;
+ * firemaker_ex_ma '#' and the other two of '1' '2' 'S'.  An agent_pos outside the board (never written by the engine) reports
+ * itself, tile 0 and blocked = 1 for every action.
+ * Outputs uint8: target_pos [N, A, n_actions, 2] (row, col), target_tile [N, A, n_actions], blocked [N, A, n_actions]; any may
+ * be NULL.  Rows n >= N are neither read nor written (the caller's bytes stay).
+ * SGW_ERR_ARG: a null engine, board or agent_pos; all three outputs NULL; a board that is not 16-byte aligned.
+ * SGW_ERR_UNSUPPORTED: a spec with action_lo != 0 (noops=False) or more than 9 actions; the scalar original families (their
+ * sprites have no simulate_update); safe_interruptibility(_ex) (an ACTUAL_ACTIONS entry left in the plot by its
+ * PolicyWrapperDrape would replace the queried action, which is not pinned).
+ * One plain launch on the caller's stream: no allocation, no synchronisation, no read-back, capturable. */
+int sgw_simulate_moves(sgw_engine* e, const uint8_t* board_dev, const uint8_t* agent_pos_dev,
+                       const uint8_t* agent_flags_dev /* NULL: direction UP */,
+                       uint8_t* target_pos_dev  /* [N, A, n_actions, 2] or NULL */,
+                       uint8_t* target_tile_dev /* [N, A, n_actions]    or NULL */,
+                       uint8_t* blocked_dev     /* [N, A, n_actions]    or NULL */, void* stream);
+/* q_value_per_tiletype of that step() (safety_game_mo.py:840-854): the Q-vectors of the actions that land on one tile type,
+ * averaged.  Per env n, agent a, l < L and d < D, over the j with target_tile[n][a][j] == tile_chars[l], in order of j:
+ *   sum = q[n][a][first j][d]; then sum = sum + q[n][a][j][d], one IEEE double addition each; table[n][a][l][d] = sum /
+ *   (double)count (np.mean(list, axis=0): the first vector is the start, not +0.0), and seen[n][a][l] = 1.
+ * A tile type that no action reached keeps its table row and its seen byte (dict.update: values persist across steps, episodes
+ * and resets; the caller zeroes table and seen once).  A target tile that is not in tile_chars is dropped.  NaN and infinities
+ * pass through as IEEE arithmetic has them.  Rows n >= N are neither read nor written.
+ * target_tile_dev: as written by sgw_simulate_moves; q_dev double [N, A, n_actions, D]; tile_chars_dev uint8 [L] (device);
+ * table_dev double [N, A, L, D] in/out; seen_dev uint8 [N, A, L] in/out or NULL.
+ * SGW_ERR_ARG: a null engine or required pointer; D < 1; L outside 1..64; q or table not 8-byte aligned.
+ * SGW_ERR_UNSUPPORTED: as sgw_simulate_moves.  One plain launch on the caller's stream, every cell with one writer; capturable. */
+int sgw_fold_q_values(sgw_engine* e, const uint8_t* target_tile_dev, const double* q_dev /* [N, A, n_actions, D] */,
+                      int D, const uint8_t* tile_chars_dev /* [L] */, int L,
+                      double* table_dev /* [N, A, L, D] in/out */, uint8_t* seen_dev /* [N, A, L] in/out or NULL */,
+                      void* stream);
+
 /* Per-env performance bookkeeping of SafetyEnvironment{,Mo}: _episodic_performances.append(...) at every LAST timestep
  * (safety_game.py:253-263, 301-302; safety_game_mo.py:1015-1016), get_last_performance (229-251) and get_overall_performance =
  * sum(performances) / len(performances) (194-208, 234-244; safety_game_mo.py:917-938).  perf_dev double [N, C] is the step's
