@@ -73,6 +73,17 @@ class Policy(C.Structure):
 
 POLICY_BOARD, POLICY_VIEWS = 0, 1
 
+
+class Td(C.Structure):
+  """Mirror of `struct sgw_td` (sgw_td_targets): device pointers (0 = NULL); `gamma` is a HOST double [C]."""
+  _fields_ = [("reward", C.c_void_p), ("step_type", C.c_void_p), ("term_reason", C.c_void_p), ("value", C.c_void_p),
+              ("value0", C.c_void_p), ("ret", C.c_void_p), ("adv", C.c_void_p), ("valid", C.c_void_p),
+              ("src_rows", C.c_int64), ("dst_rows", C.c_int64), ("T", C.c_int32), ("C", C.c_int32), ("flags", C.c_int32),
+              ("reserved_", C.c_int32), ("lambda_", C.c_double), ("gamma", C.POINTER(C.c_double))]
+
+
+TD_BOOTSTRAP_TRUNCATED = 1
+
 _lib = None
 
 
@@ -170,6 +181,9 @@ def lib():
   if hasattr(L, "sgw_simulate_moves"):                      # (as above: an older SGW_LIBRARY build cannot simulate moves)
     L.sgw_simulate_moves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgw_fold_q_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+  if hasattr(L, "sgw_td_targets"):                          # (as above: an older SGW_LIBRARY build has no learning targets)
+    L.sgw_sizeof_td.restype = C.c_int
+    L.sgw_td_targets.argtypes = [C.c_void_p, C.POINTER(Td), C.c_void_p]
   if L.sgw_abi_version() != ABI_VERSION:
     raise SgwError("libsgw.so ABI %d != binding ABI %d" % (L.sgw_abi_version(), ABI_VERSION))
   if L.sgw_sizeof_spec() != C.sizeof(Spec) or L.sgw_sizeof_out() != C.sizeof(Out):
@@ -182,6 +196,8 @@ def lib():
     raise SgwError("struct layout mismatch: sgw_episodes %d vs %d" % (L.sgw_sizeof_episodes(), C.sizeof(Episodes)))
   if hasattr(L, "sgw_policy_act") and L.sgw_sizeof_policy() != C.sizeof(Policy):
     raise SgwError("struct layout mismatch: sgw_policy %d vs %d" % (L.sgw_sizeof_policy(), C.sizeof(Policy)))
+  if hasattr(L, "sgw_td_targets") and L.sgw_sizeof_td() != C.sizeof(Td):
+    raise SgwError("struct layout mismatch: sgw_td %d vs %d" % (L.sgw_sizeof_td(), C.sizeof(Td)))
   _lib = L
   return L
 
@@ -197,7 +213,8 @@ EXPORTS = [
     "sgw_copy_envs", "sgw_out_row_bytes",
     "sgw_scalarise",
     "sgw_sizeof_policy", "sgw_policy_act", "sgw_policy_step_n",
-    "sgw_simulate_moves", "sgw_fold_q_values"]
+    "sgw_simulate_moves", "sgw_fold_q_values",
+    "sgw_sizeof_td", "sgw_td_targets"]
 
 
 def check(rc, what=""):

@@ -36,6 +36,7 @@
 #include "sgw_scalarise.hpp"
 #include "sgw_policy.hpp"
 #include "sgw_whatif.hpp"
+#include "sgw_targets.hpp"
 
 using namespace sgw;
 
@@ -1750,6 +1751,48 @@ int sgw_fold_q_values(sgw_engine* e, const uint8_t* target_tile_dev, const doubl
   a.n = e->n_envs; a.A = e->spec.A; a.n_actions = e->spec.n_actions; a.D = D; a.L = L;
   HIP_TRY(hipSetDevice(e->device));
   hipLaunchKernelGGL(k_fold_q_values, dim3((unsigned)blocks), dim3(WHATIF_THREADS_MAX), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+// ---- learning targets from rollout buffers: sgw_td_targets (sgw_targets.hpp) ---------------------------------------------------
+int sgw_sizeof_td(void) { return (int)sizeof(sgw_td); }
+
+int sgw_td_targets(sgw_engine* e, const sgw_td* td, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_td_targets: null engine");
+  if (!td) return fail(SGW_ERR_ARG, "sgw_td_targets: null sgw_td");
+  if (!td->reward || !td->step_type || !td->gamma) return fail(SGW_ERR_ARG, "sgw_td_targets: reward, step_type and gamma are required");
+  if (!td->ret && !td->adv && !td->valid) return fail(SGW_ERR_ARG, "sgw_td_targets: no output");
+  if (td->adv && (!td->value || !td->value0)) return fail(SGW_ERR_ARG, "sgw_td_targets: adv needs value and value0");
+  if (td->flags & ~SGW_TD_BOOTSTRAP_TRUNCATED) return fail(SGW_ERR_ARG, "sgw_td_targets: unknown flag bits");
+  const bool boot = (td->flags & SGW_TD_BOOTSTRAP_TRUNCATED) != 0;
+  if (boot && !td->term_reason) return fail(SGW_ERR_ARG, "sgw_td_targets: SGW_TD_BOOTSTRAP_TRUNCATED needs term_reason");
+  if (td->T < 1) return fail(SGW_ERR_ARG, "sgw_td_targets: T < 1");
+  if (td->C < 1 || td->C > SGW_MAX_K) return fail(SGW_ERR_ARG, "sgw_td_targets: C outside 1..SGW_MAX_K");
+  if (td->src_rows < e->n_envs || td->dst_rows < e->n_envs) return fail(SGW_ERR_ARG, "sgw_td_targets: src_rows / dst_rows < n_envs");
+  if (((uintptr_t)td->reward | (uintptr_t)td->value | (uintptr_t)td->value0 | (uintptr_t)td->ret | (uintptr_t)td->adv) & 7)
+    return fail(SGW_ERR_ARG, "sgw_td_targets: a double array is not 8-byte aligned");
+  const void* in_d[3] = {td->reward, td->value, td->value0};
+  for (const void* in : in_d)
+    if (in && (in == td->ret || in == td->adv)) return fail(SGW_ERR_ARG, "sgw_td_targets: an output pointer equals an input pointer");
+  if (td->valid && (td->valid == td->step_type || td->valid == td->term_reason))
+    return fail(SGW_ERR_ARG, "sgw_td_targets: an output pointer equals an input pointer");
+  if (td->ret && td->ret == td->adv) return fail(SGW_ERR_ARG, "sgw_td_targets: ret and adv are the same array");
+  TdArgs a; memset(&a, 0, sizeof(a));
+  a.reward = td->reward; a.step_type = td->step_type; a.term_reason = boot ? td->term_reason : nullptr;
+  a.value = td->value; a.value0 = td->adv ? td->value0 : nullptr;          // value0 is read for adv only
+  a.ret = td->ret; a.adv = td->adv; a.valid = td->valid;
+  a.src_rows = td->src_rows; a.dst_rows = td->dst_rows;
+  a.T = td->T; a.A = e->spec.A; a.C = td->C; a.bootstrap = boot ? 1 : 0; a.lambda = td->lambda;
+  a.R = (int)out_row_bytes(e->spec, OF_term_reason);                                // term_reason: one column, or one per agent
+  if (a.R < 1) a.R = 1;
+  for (int c = 0; c < td->C; ++c) a.gamma[c] = td->gamma[c];
+  a.n_elems = e->n_envs * a.A * (long long)a.C;
+  const long long blocks = (a.n_elems + TD_THREADS - 1) / TD_THREADS;
+  if (blocks > 0x7fffffffLL) return fail(SGW_ERR_ARG, "sgw_td_targets: too many (env, agent, column) lanes for one launch");
+  if (blocks == 0) return SGW_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_td_targets, dim3((unsigned)blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return SGW_OK;
 }

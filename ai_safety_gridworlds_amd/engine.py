@@ -712,7 +712,7 @@ class BatchedEngine(object):
       karr = self._karr = (C.c_int32 * N.MAX_AGENTS)(*(ks + [0] * (N.MAX_AGENTS - len(ks))))
     return karr
 
-  def _padded_source(self, name, t, T):
+  def _padded_source(self, name, t, T, what="scalarise"):
     """Data pointer of `t` as the [T, N_pad, row] buffer of output `name`: the padded buffer itself, or the [T, N, ...] view of it
     that a write_every call returned (same first byte, the padded strides)."""
     dt, shp = _dtype_shape(self.spec, name)
@@ -724,8 +724,8 @@ class BatchedEngine(object):
     elif ok:
       ok = t.is_contiguous() and t.shape[0] in (self.n_envs, self.n_pad) and t.numel() == t.shape[0] * row
     if not ok:
-      raise N.SgwError("scalarise: buffers[%r] must be the %s [%s%d or %d, ...] output buffer of this engine on %s (there is no CPU path)"
-                       % (name, dt, "%d, " % T if T > 1 else "", self.n_envs, self.n_pad, self.device))
+      raise N.SgwError("%s: buffers[%r] must be the %s [%s%d or %d, ...] output buffer of this engine on %s (there is no CPU path)"
+                       % (what, name, dt, "%d, " % T if T > 1 else "", self.n_envs, self.n_pad, self.device))
     return t.data_ptr()
 
   def scalarise(self, T=1, buffers=None):
@@ -780,6 +780,78 @@ class BatchedEngine(object):
     N.check(self._lib.sgw_scalarise(self._h, rows.data_ptr(), None, None, 1, self._k_agent(), out.data_ptr(), None, None, self._stream()),
             "sgw_scalarise")
     return out[:, 0] if A == 1 else out
+
+  # -- learning targets ------------------------------------------------------------------------
+  def td_targets(self, T, gamma, lam=None, values=None, value0=None, buffers=None, bootstrap_truncated=False, scalar=False):
+    """Discounted returns-to-go and GAE(lambda) advantages of the engine's [T, N_pad, ...] buffers of a write_every call (step_n,
+    rollout, replay, policy_step_n), from ONE library call (sgw_td_targets: one launch, no synchronisation, capturable), per env,
+    agent and reward column, cut at episode ends by the reference's conventions (include/sgw.h spells the rule out): a FIRST row
+    is an auto-reset that consumed the step slot, a DEAD row an agent that finished before the others -- neither is a transition
+    (valid False, 0.0, nothing flows across); a LAST row ends the recursion, and with bootstrap_truncated=True a LAST row whose
+    term_reason is MAX_STEPS bootstraps from its own value instead.
+    gamma: a float or a sequence of C floats (C = K, or 1 with scalar=True, which runs over scalarise(T)["scalar_reward"], summed
+    here by the same sgw_scalarise launch); lam: lambda of the advantages (None = 1.0).  values [T, N(, A)(, C)]: V(observation
+    after step t), value0 [N(, A)(, C)]: V(observation before step 0) -- the caller's contiguous float64 tensors on this device;
+    the returns then end on values[T-1] instead of 0.0, and with value0 the advantages are computed too.
+    buffers: {"reward", "step_type"(, "term_reason" with bootstrap_truncated)} to read instead of the engine's own.
+    Returns {"returns": float64 [T, N(, A), C], "advantages": the same (values and value0 given), "valid": bool [T, N(, A)]}.
+    The result tensors are persistent per (T, C) and rewritten by the next call.  There is no CPU path."""
+    T = int(T)
+    if T < 1:
+      raise ValueError("td_targets: T must be >= 1")
+    if self._h is None:
+      raise N.SgwError("td_targets: the engine has no device engine behind it (closed?); there is no CPU path")
+    A, n = self.spec.A, self.n_envs
+    Cn = 1 if scalar else self.spec.K
+    need = ["reward", "step_type"] + (["term_reason"] if bootstrap_truncated else [])
+    if buffers is None:
+      if self._T != T or any(k not in self._bufs for k in need):
+        raise N.SgwError("td_targets(T=%d) needs the %s outputs of %s (the engine holds T=%d buffers of %s)"
+                         % (T, ", ".join(repr(k) for k in need), "a single step" if T == 1 else "a write_every call over %d steps" % T,
+                            self._T, sorted(self._bufs)))
+      ptr = {k: self._bufs[k].data_ptr() for k in need}
+    else:
+      for k in need:
+        if k not in buffers:
+          raise N.SgwError("td_targets: buffers needs %s" % ", ".join(repr(k) for k in need))
+      ptr = {k: self._padded_source(k, buffers[k], T, "td_targets") for k in need}
+    g = [float(gamma)] * Cn if np.ndim(gamma) == 0 else [float(x) for x in gamma]
+    if len(g) != Cn:
+      raise ValueError("td_targets: gamma must be a float or %d floats (one per reward column)" % Cn)
+    if value0 is not None and values is None:
+      raise ValueError("td_targets: value0 without values")
+    for name, v, numel in (("values", values, T * n * A * Cn), ("value0", value0, n * A * Cn)):
+      if v is not None and not (torch.is_tensor(v) and v.device == self.device and v.dtype == torch.float64 and v.is_contiguous()
+                                and v.numel() == numel):
+        raise N.SgwError("td_targets: %s must be a contiguous float64 tensor of %d elements on %s (there is no CPU path)"
+                         % (name, numel, self.device))
+    cache = self.__dict__.setdefault("_targets", {})
+    c = cache.get((T, Cn))
+    if c is None:
+      ret, adv = (torch.zeros((T, n, A, Cn), dtype=torch.float64, device=self.device) for _ in range(2))
+      valid = torch.zeros((T, n, A), dtype=torch.uint8, device=self.device)
+      c = cache[(T, Cn)] = (ret, adv, valid)
+    ret, adv, valid = c
+    reward_ptr = ptr["reward"]
+    if scalar:       # scalarise(T)["scalar_reward"]: the same launch, asked for that sum alone (needs neither 'cumulative' nor 'frame')
+      sr = cache.get(("scalar_reward", T))
+      if sr is None:
+        sr = cache[("scalar_reward", T)] = torch.zeros((T, self.n_pad, A), dtype=torch.float64, device=self.device)
+      N.check(self._lib.sgw_scalarise(self._h, reward_ptr, None, None, T, self._k_agent(), sr.data_ptr(), None, None, self._stream()),
+              "sgw_scalarise")
+      reward_ptr = sr.data_ptr()
+    want_adv = value0 is not None
+    garr = (C.c_double * Cn)(*g)
+    td = N.Td(reward=reward_ptr, step_type=ptr["step_type"], term_reason=ptr.get("term_reason"),
+              value=None if values is None else values.data_ptr(), value0=value0.data_ptr() if want_adv else None,
+              ret=ret.data_ptr(), adv=adv.data_ptr() if want_adv else None, valid=valid.data_ptr(),
+              src_rows=self.n_pad, dst_rows=n, T=T, C=Cn, flags=N.TD_BOOTSTRAP_TRUNCATED if bootstrap_truncated else 0,
+              reserved_=0, lambda_=1.0 if lam is None else float(lam), gamma=garr)
+    N.check(self._lib.sgw_td_targets(self._h, C.byref(td), self._stream()), "sgw_td_targets")
+    res = {"returns": ret[:, :, 0] if A == 1 else ret, "valid": (valid[:, :, 0] if A == 1 else valid).view(torch.bool)}
+    if want_adv:
+      res["advantages"] = adv[:, :, 0] if A == 1 else adv
+    return res
 
   # -- closed loop: table policies (policy.py) ------------------------------------------------
   def _policy_source(self, policy, what):

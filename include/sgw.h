@@ -424,6 +424,58 @@ int sgw_fold_q_values(sgw_engine* e, const uint8_t* target_tile_dev, const doubl
                       double* table_dev /* [N, A, L, D] in/out */, uint8_t* seen_dev /* [N, A, L] in/out or NULL */,
                       void* stream);
 
+/* Learning targets from rollout buffers: the discounted return-to-go and the GAE-lambda advantage, per env, agent and reward
+ * column, by the backward recursion over the T rows of a write_every call (sgw_step_n / sgw_rollout / sgw_replay /
+ * sgw_policy_step_n), cut at episode ends by the reference's conventions rather than Gym's:
+ *   - an auto-reset consumes a step slot: that row is FIRST, its action was discarded and its reward is 0; it belongs to no
+ *     transition (valid = 0) and nothing flows across it;
+ *   - `terminated` (step_type LAST) is also reported at max-steps; only term_reason tells SGW_MAX_STEPS from SGW_TERMINATED;
+ *   - in the per-agent families an agent goes LAST -> DEAD while the others play on: its DEAD rows are no transitions either.
+ * Each element (n < N, a < A, c < C) is independent.  With g = gamma[c] and gl = g * lambda (one multiplication), every `*`, `+`,
+ * `-` below ONE IEEE double operation rounded on its own (nothing is fused or reassociated):
+ *   carry_ret = value ? value[T-1][n][a][c] : 0.0;  carry_adv = 0.0                       (what lies beyond the buffer)
+ *   for t = T-1 .. 0:
+ *     st = step_type[t][n][a];  r = reward[t][n][a][c]
+ *     if st == SGW_MID:        cont = 1
+ *     else if st == SGW_LAST:  cont = 2 if (flags & SGW_TD_BOOTSTRAP_TRUNCATED) and term_reason[t][n][min(a, R-1)] == SGW_MAX_STEPS,
+ *                              else 0
+ *     else (SGW_FIRST, SGW_DEAD or any other byte):
+ *       ret[t] = +0.0; adv[t] = +0.0; valid[t] = 0; carry_ret = +0.0; carry_adv = +0.0; continue
+ *     valid[t] = 1
+ *     v     = value ? value[t] : 0.0                      V(the observation after step t)
+ *     vprev = t > 0 ? value[t-1] : value0                 V(the observation the action of step t was chosen on); read for adv only
+ *     cont == 1:  ret[t] = r + g * carry_ret;  adv[t] = ((r + g * v) - vprev) + gl * carry_adv
+ *     cont == 2:  ret[t] = r + g * v;          adv[t] = (r + g * v) - vprev     (truncated: bootstrapped from its own row;
+ *                                                                                nothing flows in from the next episode)
+ *     cont == 0:  ret[t] = r;                  adv[t] = r - vprev               (terminated: r itself, a -0.0 stays -0.0)
+ *     carry_ret = ret[t];  carry_adv = adv[t]
+ * NaN and infinities pass through as IEEE arithmetic has them.  A and N are the engine's; R = sgw_out_row_bytes(e, 5), the
+ * columns of the term_reason output (A for island_navigation_ex_ma and aintelope_savanna, 1 elsewhere).  Element (n, a, c) of step t sits at
+ * ((t * rows + n) * A + a) * C + c with rows = src_rows for reward / step_type / term_reason and dst_rows for value / value0 /
+ * ret / adv / valid: N_pad for the engine's buffers, N for plain tensors.  Rows n >= N of every array are neither read nor written
+ * (the caller's bytes stay).  C is the K of the `reward` output, or 1 over sgw_scalarise's scalar_reward.
+ * SGW_ERR_ARG: a null engine or struct; a null reward, step_type or gamma; all three outputs NULL; adv without value and value0;
+ * SGW_TD_BOOTSTRAP_TRUNCATED without term_reason; unknown flag bits; T < 1; C outside 1..SGW_MAX_K; src_rows or dst_rows < N; a
+ * double array that is not 8-byte aligned; an output pointer equal to an input pointer (or ret == adv).
+ * One plain launch on the caller's stream: no allocation, no synchronisation, no read-back, capturable. */
+#define SGW_TD_BOOTSTRAP_TRUNCATED 1
+typedef struct sgw_td {
+  const double*  reward;       /* [T, src_rows, A, C]  the `reward` output (C = K), or sgw_scalarise's scalar_reward (C = 1) */
+  const uint8_t* step_type;    /* [T, src_rows, A] */
+  const uint8_t* term_reason;  /* [T, src_rows, R], R = sgw_out_row_bytes(e, 5); required with BOOTSTRAP_TRUNCATED, else may be NULL */
+  const double*  value;        /* [T, dst_rows, A, C] or NULL (ret then ends on 0.0; adv needs it) */
+  const double*  value0;       /* [dst_rows, A, C]; required for adv */
+  double*  ret;                /* [T, dst_rows, A, C] or NULL */
+  double*  adv;                /* [T, dst_rows, A, C] or NULL */
+  uint8_t* valid;              /* [T, dst_rows, A] or NULL */
+  int64_t src_rows, dst_rows;  /* env rows per step: N_pad for engine buffers, N for plain torch tensors; each >= N */
+  int32_t T, C, flags, reserved_;
+  double lambda;
+  const double* gamma;         /* HOST double [C], read at call time */
+} sgw_td;
+int sgw_sizeof_td(void);
+int sgw_td_targets(sgw_engine* e, const sgw_td* td, void* stream);
+
 /* Per-env performance bookkeeping of SafetyEnvironment{,Mo}: _episodic_performances.append(...) at every LAST timestep
  * (safety_game.py:253-263, 301-302; safety_game_mo.py:1015-1016), get_last_performance (229-251) and get_overall_performance =
  * sum(performances) / len(performances) (194-208, 234-244; safety_game_mo.py:917-938).  perf_dev double [N, C] is the step's
