@@ -383,7 +383,7 @@ struct IslandT : IslandDefs {
   // (the per-event-vector variant needs > 256 registers in the fused rollout: two env-waves keep its paired workgroup at 4 wavefronts)
   static constexpr int ENV_WAVES_MAX = GENERAL ? 2 : SGW_ISLAND_EW;
   struct Ctx { SgwPowStageT<ENV_WAVES_MAX * WAVE> pow; };
-  // the pow tables' global loads are issued with the level tables', ahead of the state loads; LDS is written afterwards
+  // the pow tables' global loads are issued with the prologue's other loads, behind the state's (engine_body); LDS is written afterwards
   static __device__ void init_issue(Ctx& cx) { sgw_pow_stage_issue<ENV_WAVES_MAX * WAVE>(cx.pow); }
   static __device__ void init_ctx(Ctx& cx, const Lds& l) { sgw_pow_stage_commit<ENV_WAVES_MAX * WAVE>(cx.pow, l.extra); }
   static __device__ void init_args(Ctx&, const Lds& l, const KArgs& a) {      // before k_engine's staging barrier

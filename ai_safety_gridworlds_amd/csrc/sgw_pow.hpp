@@ -108,7 +108,10 @@ SGW_POW_DEV_FN double sgw_glibc_pow(double x, double y) { return sgw_glibc_pow_t
 constexpr int SGW_POW_LDS_BYTES = (128 * 3 + 256) * 8;
 // 320 pieces of 16 bytes (192 log + 128 exp) over THREADS threads: ceil(320 / THREADS) unconditional loads per thread, piece
 // (t + j * THREADS) mod 320 (the wrap-around rewrites a few pieces with the same bytes; no branch for the loads to sink into)
-template <int THREADS> struct SgwPowStageT { static constexpr int NP = (320 + THREADS - 1) / THREADS; uint4 v[NP]; };
+// The pieces are plain vector VALUES, like TableQuad (sgw_common.hpp): HIP's uint4 class is copied through a stack slot
+// when something opaque (the kernarg touch) sits between `issue` and `commit`.
+typedef uint32_t SgwPowPiece __attribute__((vector_size(16)));
+template <int THREADS> struct SgwPowStageT { static constexpr int NP = (320 + THREADS - 1) / THREADS; SgwPowPiece v[NP]; };
 using SgwPowStage = SgwPowStageT<256>;
 template <int THREADS>
 __device__ inline int sgw_pow_piece(int j) {       // a workgroup with more threads than THREADS repeats the same pieces
@@ -117,18 +120,28 @@ __device__ inline int sgw_pow_piece(int j) {       // a workgroup with more thre
 }
 template <int THREADS>
 __device__ inline void sgw_pow_stage_issue(SgwPowStageT<THREADS>& st) {               // loads only, unconditional
-  const uint4* lg = reinterpret_cast<const uint4*>(SGW_POW_LOG_TAB);     // 192 x 16 B
-  const uint4* ex = reinterpret_cast<const uint4*>(SGW_POW_EXP_TAB);     // 128 x 16 B
+#if defined(__HIP_DEVICE_COMPILE__)
+  // The compiler knows that the two tables are constant memory and moves loads of them across anything, a memory clobber
+  // included: left alone they sink below the kernarg touch towards `commit` and start a second round trip after the touch's.
+  // Behind an empty asm the addresses are two global pointers like any other (still address space 1: global_load, not
+  // flat_load, which would count in lgkmcnt too) and the loads stay where the source puts them.
+  typedef const SgwPowPiece __attribute__((address_space(1)))* Src;
+  Src lg = (Src)SGW_POW_LOG_TAB, ex = (Src)SGW_POW_EXP_TAB;
+  asm volatile("" : "+s"(lg), "+s"(ex));
+#else
+  const SgwPowPiece* lg = reinterpret_cast<const SgwPowPiece*>(SGW_POW_LOG_TAB);     // 192 x 16 B
+  const SgwPowPiece* ex = reinterpret_cast<const SgwPowPiece*>(SGW_POW_EXP_TAB);     // 128 x 16 B
+#endif
 #pragma unroll
   for (int j = 0; j < SgwPowStageT<THREADS>::NP; ++j) {
     const int i = sgw_pow_piece<THREADS>(j);
-    const uint4* src = i < 192 ? lg + i : ex + (i - 192);
+    const auto src = i < 192 ? lg + i : ex + (i - 192);
     st.v[j] = *src;
   }
 }
 template <int THREADS>
 __device__ inline void sgw_pow_stage_commit(const SgwPowStageT<THREADS>& st, void* lds) {
-  uint4* dst = reinterpret_cast<uint4*>(lds);
+  SgwPowPiece* dst = reinterpret_cast<SgwPowPiece*>(lds);
 #pragma unroll
   for (int j = 0; j < SgwPowStageT<THREADS>::NP; ++j) dst[sgw_pow_piece<THREADS>(j)] = st.v[j];
 }
