@@ -83,6 +83,7 @@ class Td(C.Structure):
 
 
 TD_BOOTSTRAP_TRUNCATED = 1
+APPLY_CLEAR = 1
 
 _lib = None
 
@@ -184,6 +185,12 @@ def lib():
   if hasattr(L, "sgw_td_targets"):                          # (as above: an older SGW_LIBRARY build has no learning targets)
     L.sgw_sizeof_td.restype = C.c_int
     L.sgw_td_targets.argtypes = [C.c_void_p, C.POINTER(Td), C.c_void_p]
+  if hasattr(L, "sgw_policy_scores"):                       # (as above: an older SGW_LIBRARY build cannot learn tables)
+    L.sgw_policy_scores.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgw_policy_accumulate.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgw_policy_apply.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
   if L.sgw_abi_version() != ABI_VERSION:
     raise SgwError("libsgw.so ABI %d != binding ABI %d" % (L.sgw_abi_version(), ABI_VERSION))
   if L.sgw_sizeof_spec() != C.sizeof(Spec) or L.sgw_sizeof_out() != C.sizeof(Out):
@@ -214,7 +221,8 @@ EXPORTS = [
     "sgw_scalarise",
     "sgw_sizeof_policy", "sgw_policy_act", "sgw_policy_step_n",
     "sgw_simulate_moves", "sgw_fold_q_values",
-    "sgw_sizeof_td", "sgw_td_targets"]
+    "sgw_sizeof_td", "sgw_td_targets",
+    "sgw_policy_scores", "sgw_policy_accumulate", "sgw_policy_apply"]
 
 
 def check(rc, what=""):

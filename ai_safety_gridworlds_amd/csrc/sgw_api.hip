@@ -37,6 +37,7 @@
 #include "sgw_policy.hpp"
 #include "sgw_whatif.hpp"
 #include "sgw_targets.hpp"
+#include "sgw_learn.hpp"
 
 using namespace sgw;
 
@@ -1793,6 +1794,133 @@ int sgw_td_targets(sgw_engine* e, const sgw_td* td, void* stream) {
   if (blocks == 0) return SGW_OK;
   HIP_TRY(hipSetDevice(e->device));
   hipLaunchKernelGGL(k_td_targets, dim3((unsigned)blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+}  // extern "C"
+
+// ---- learning a table policy: sgw_policy_scores, sgw_policy_accumulate, sgw_policy_apply (sgw_learn.hpp) -----------------------
+// the T + 1 observations O[0] = obs0, O[s] = row s-1 of obs: required pointers, rows and the 16-byte alignment of every O[s]
+static int learn_observations(const sgw_engine* e, const PolicyLaunch& L, const char* who, const uint8_t* obs0, const uint8_t* obs,
+                              int64_t obs_rows, int T) {
+  if (!obs0) return fail(SGW_ERR_ARG, "%s: null obs0", who);
+  if (T > 0 && !obs) return fail(SGW_ERR_ARG, "%s: null obs with T >= 1", who);
+  if (T > 0 && obs_rows < e->n_envs) return fail(SGW_ERR_ARG, "%s: obs_rows < n_envs", who);
+  if (((uintptr_t)obs0) & 15) return fail(SGW_ERR_ARG, "%s: obs0 is not 16-byte aligned (the rows move as 16-byte accesses)", who);
+  if (T > 0 && ((((uintptr_t)obs) & 15) || (T > 1 && ((obs_rows * (long long)L.a.row_bytes) & 15))))
+    return fail(SGW_ERR_ARG, "%s: a row block of obs is not 16-byte aligned (the rows move as 16-byte accesses)", who);
+  return SGW_OK;
+}
+
+extern "C" {
+
+int sgw_policy_scores(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, const uint8_t* obs_dev, int64_t obs_rows, int T,
+                      const int8_t* actions_dev, float* scores_dev, double* vmax_dev, double* chosen_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_scores: null engine");
+  if (T < 0) return fail(SGW_ERR_ARG, "sgw_policy_scores: T < 0");
+  if (!scores_dev && !vmax_dev && !chosen_dev) return fail(SGW_ERR_ARG, "sgw_policy_scores: no output");
+  if (chosen_dev && T > 0 && !actions_dev) return fail(SGW_ERR_ARG, "sgw_policy_scores: chosen needs actions");
+  PolicyLaunch L;
+  int rc = policy_plan(e, p, "sgw_policy_scores", L);
+  if (rc) return rc;
+  rc = learn_observations(e, L, "sgw_policy_scores", obs0_dev, obs_dev, obs_rows, T);
+  if (rc) return rc;
+  if ((((uintptr_t)scores_dev) & 3) || (((uintptr_t)vmax_dev | (uintptr_t)chosen_dev) & 7))
+    return fail(SGW_ERR_ARG, "sgw_policy_scores: a misaligned output array");
+  const long long groups = L.blocks, blocks = groups * ((long long)T + 1);
+  if (blocks > 0x7fffffffLL) return fail(SGW_ERR_ARG, "sgw_policy_scores: too many (observation, env group) blocks for one launch");
+  if (blocks == 0) return SGW_OK;
+  ScoreArgs a; memset(&a, 0, sizeof(a));
+  a.obs0 = obs0_dev; a.obs = obs_dev; a.code_of = p->code_of; a.weights = p->weights; a.bias = p->bias; a.policy_of_env = p->policy_of_env;
+  a.actions = actions_dev; a.scores = scores_dev; a.vmax = vmax_dev; a.chosen = T > 0 ? chosen_dev : nullptr;
+  a.n = e->n_envs; a.obs_rows = obs_rows; a.groups = groups;
+  a.T = T; a.row_bytes = L.a.row_bytes; a.envs_per_block = L.a.envs_per_block; a.A = L.a.A; a.P = L.a.P; a.G = L.a.G; a.C = L.a.C;
+  a.n_actions = L.a.n_actions; a.action_lo = L.a.action_lo;
+  for (int ag = 0; ag < SGW_MAX_AGENTS; ++ag) { a.c_a[ag] = L.a.c_a[ag]; a.off_a[ag] = L.a.off_a[ag]; }
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_policy_scores, dim3((unsigned)blocks), dim3(L.threads), L.lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+int sgw_policy_accumulate(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, const uint8_t* obs_dev, int64_t obs_rows, int T,
+                          const int8_t* actions_dev, const double* coef_dev, int frac_bits, int64_t* acc_weights_dev,
+                          int64_t* acc_bias_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: null engine");
+  if (T < 1) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: T < 1");
+  if (!actions_dev || !coef_dev || !acc_weights_dev) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: actions, coef and acc_weights are required");
+  if (frac_bits < 0 || frac_bits > 52) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: frac_bits outside 0..52");
+  PolicyLaunch L;
+  int rc = policy_plan(e, p, "sgw_policy_accumulate", L);
+  if (rc) return rc;
+  rc = learn_observations(e, L, "sgw_policy_accumulate", obs0_dev, obs_dev, obs_rows, T - 1);   // O[T] is not read
+  if (rc) return rc;
+  if (((uintptr_t)coef_dev | (uintptr_t)acc_weights_dev | (uintptr_t)acc_bias_dev) & 7)
+    return fail(SGW_ERR_ARG, "sgw_policy_accumulate: coef or an accumulator is not 8-byte aligned");
+  const void* inputs[] = {obs0_dev, obs_dev, actions_dev, coef_dev, p->code_of, p->weights, p->bias, p->policy_of_env, p->step_dev};
+  for (const void* in : inputs)
+    if (in && (in == acc_weights_dev || in == acc_bias_dev)) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: an accumulator aliases an input");
+  if (acc_weights_dev == acc_bias_dev) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: acc_weights and acc_bias are the same array");
+  if ((long long)T * e->n_envs >= (1LL << 32)) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: T * n_envs >= 2^32 (an int64 sum could wrap)");
+  AccArgs a; memset(&a, 0, sizeof(a));
+  int E = 64;
+  while (E > 16 && (long long)E * L.a.row_bytes > LEARN_MAX_ROW_LDS) E >>= 1;
+  if ((long long)E * L.a.row_bytes > LEARN_MAX_ROW_LDS) return fail(SGW_ERR_UNSUPPORTED, "sgw_policy_accumulate: the observation row is too long to stage");
+  const int A = L.a.A, G = L.a.G, NA = L.a.n_actions, P = L.a.P;
+  int max_c = 1;
+  for (int ag = 0; ag < A; ++ag) max_c = L.a.c_a[ag] > max_c ? L.a.c_a[ag] : max_c;
+  int R = max_c;                                                            // P > 1: no bins, one slice per agent
+  if (P == 1) {
+    const int fit = (LEARN_MAX_BIN_LDS - NA * 8) / (G * NA * 8);            // >= 2: G <= 64, NA <= 16
+    R = fit < max_c ? fit : max_c;
+  }
+  int slices = 0;
+  for (int ag = 0; ag < SGW_MAX_AGENTS; ++ag) {
+    a.slice0[ag] = slices;
+    if (ag < A) { const int k = (L.a.c_a[ag] + R - 1) / R; slices += k > 0 ? k : 1; }
+    a.c_a[ag] = L.a.c_a[ag]; a.off_a[ag] = L.a.off_a[ag];
+  }
+  const long long groups = (e->n_envs + E - 1) / E, tiles = groups * T;
+  if (tiles == 0) return SGW_OK;
+  long long per_slice = LEARN_BLOCKS / slices;
+  if (per_slice < 1) per_slice = 1;
+  if (per_slice > tiles) per_slice = tiles;
+  a.obs0 = obs0_dev; a.obs = obs_dev; a.code_of = p->code_of; a.policy_of_env = p->policy_of_env; a.actions = actions_dev; a.coef = coef_dev;
+  a.acc_w = reinterpret_cast<unsigned long long*>(acc_weights_dev); a.acc_b = reinterpret_cast<unsigned long long*>(acc_bias_dev);
+  a.n = e->n_envs; a.obs_rows = obs_rows; a.groups = groups; a.tiles = tiles; a.scale = ldexp(1.0, frac_bits);
+  a.row_bytes = L.a.row_bytes; a.envs_per_block = E; a.A = A; a.P = P; a.G = G; a.C = L.a.C; a.n_actions = NA; a.action_lo = L.a.action_lo;
+  a.R = R; a.blocks_per_slice = (int)per_slice;
+  const size_t lds = ((size_t)E * a.row_bytes + 15) / 16 * 16 + 256 + (size_t)E * 12 + (P == 1 ? ((size_t)R * G * NA + NA) * 8 : 0);
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_policy_accumulate, dim3((unsigned)(per_slice * slices)), dim3(LEARN_THREADS), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+int sgw_policy_apply(sgw_engine* e, const sgw_policy* p, double lr, int frac_bits, int64_t* acc_weights_dev, int64_t* acc_bias_dev,
+                     int flags, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_apply: null engine");
+  if (!acc_weights_dev) return fail(SGW_ERR_ARG, "sgw_policy_apply: null acc_weights");
+  if (frac_bits < 0 || frac_bits > 52) return fail(SGW_ERR_ARG, "sgw_policy_apply: frac_bits outside 0..52");
+  if (flags & ~SGW_APPLY_CLEAR) return fail(SGW_ERR_ARG, "sgw_policy_apply: unknown flag bits");
+  PolicyLaunch L;
+  const int rc = policy_plan(e, p, "sgw_policy_apply", L);
+  if (rc) return rc;
+  if (((uintptr_t)acc_weights_dev | (uintptr_t)acc_bias_dev) & 7) return fail(SGW_ERR_ARG, "sgw_policy_apply: an accumulator is not 8-byte aligned");
+  if ((const void*)acc_weights_dev == (const void*)p->weights || (acc_bias_dev && ((const void*)acc_bias_dev == (const void*)p->bias || acc_bias_dev == acc_weights_dev)))
+    return fail(SGW_ERR_ARG, "sgw_policy_apply: an accumulator aliases a table");
+  ApplyArgs a; memset(&a, 0, sizeof(a));
+  a.weights = const_cast<float*>(p->weights); a.bias = const_cast<float*>(p->bias);
+  a.acc_w = reinterpret_cast<long long*>(acc_weights_dev); a.acc_b = reinterpret_cast<long long*>(acc_bias_dev);
+  const long long slices = (long long)L.a.P * L.a.A;
+  a.n_w = slices * L.a.C * L.a.G * L.a.n_actions;
+  a.n_b = (p->bias && acc_bias_dev) ? slices * L.a.n_actions : 0;
+  a.lr = lr; a.inv_scale = ldexp(1.0, -frac_bits); a.clear = (flags & SGW_APPLY_CLEAR) ? 1 : 0;
+  long long blocks = (a.n_w + a.n_b + LEARN_THREADS - 1) / LEARN_THREADS;
+  if (blocks > 4096) blocks = 4096;                                         // the kernel strides
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_policy_apply, dim3((unsigned)blocks), dim3(LEARN_THREADS), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return SGW_OK;
 }

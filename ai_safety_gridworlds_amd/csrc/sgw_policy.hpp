@@ -49,13 +49,11 @@ struct PolicyArgs {
   int off_a[SGW_MAX_AGENTS];     // byte offset of agent a's cells in the env's row
 };
 
-// The action INDEX (0 .. NA-1) of one (env, agent).  o: the agent's C_a observation bytes; w: the agent's table
-// [C][G][NA] of the env's policy; b: its bias [NA] or nullptr.
+// The score vector of one (env, agent): the bias, then one float32 addition per cell in cell order.  The one statement of the
+// accumulation: policy_choose (the actor) and sgw_policy_scores (sgw_learn.hpp) both call it.
 template <int NA>
-__host__ __device__ inline int policy_choose(const uint8_t* o, int C_a, const uint8_t* code_of, const float* w, const float* b, int G,
-                                             unsigned long long explore_below, unsigned long long seed, long long env_id,
-                                             long long step, int agent) {
-  float score[NA];
+__host__ __device__ __forceinline__ void policy_score(float (&score)[NA], const uint8_t* o, int C_a, const uint8_t* code_of, const float* w,
+                                                      const float* b, int G) {
 #pragma unroll
   for (int j = 0; j < NA; ++j) score[j] = b ? b[j] : 0.0f;
 #pragma unroll 4
@@ -64,11 +62,29 @@ __host__ __device__ inline int policy_choose(const uint8_t* o, int C_a, const ui
 #pragma unroll
     for (int j = 0; j < NA; ++j) score[j] = score[j] + cell[j];
   }
+}
+
+// the first maximum of a score vector (a NaN never displaces the incumbent); top: its score
+template <int NA>
+__host__ __device__ __forceinline__ int policy_first_max(const float (&score)[NA], float& top) {
   int best = 0;
-  float top = score[0];
+  top = score[0];
 #pragma unroll
   for (int j = 1; j < NA; ++j)
     if (score[j] > top) { top = score[j]; best = j; }
+  return best;
+}
+
+// The action INDEX (0 .. NA-1) of one (env, agent).  o: the agent's C_a observation bytes; w: the agent's table
+// [C][G][NA] of the env's policy; b: its bias [NA] or nullptr.
+template <int NA>
+__host__ __device__ inline int policy_choose(const uint8_t* o, int C_a, const uint8_t* code_of, const float* w, const float* b, int G,
+                                             unsigned long long explore_below, unsigned long long seed, long long env_id,
+                                             long long step, int agent) {
+  float score[NA];
+  policy_score<NA>(score, o, C_a, code_of, w, b, G);
+  float top;
+  int best = policy_first_max<NA>(score, top);
   if (explore_below != 0) {
     const U4 r = philox4x32_10((uint32_t)step, TAG_POLICY, (uint32_t)agent, (uint32_t)((uint64_t)env_id >> 32), (uint32_t)seed,
                                (uint32_t)env_id);

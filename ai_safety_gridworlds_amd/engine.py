@@ -894,6 +894,17 @@ class BatchedEngine(object):
     outputs).  The buffers are persistent per (T, write_every), so from the third identical call on (T >= 8) the 2T + 1 launches
     are one graph replay; the policy's tensors are read through their pointers, so weights rewritten in place take effect.
     Source 'views' needs a spec whose step launch writes the windows itself (fused_views)."""
+    return self._policy_step_n(policy, T, write_every, accumulate, False)
+
+  def policy_rollout(self, policy, T, write_every=True, accumulate=False):
+    """policy_step_n that KEEPS the observation the first action was chosen on.  With write_every the last step overwrites the
+    buffer row that observation was read from, so a learner has lost O[0] by the time policy_step_n returns; here the observation
+    rows are first copied (on the engine's stream) into a persistent side buffer, the call reads that buffer as its first
+    observation, and it is returned as "obs0" uint8 [N, row]: the O[0] of policy_scores / policy_accumulate.  Everything else is
+    policy_step_n's."""
+    return self._policy_step_n(policy, T, write_every, accumulate, True)
+
+  def _policy_step_n(self, policy, T, write_every, accumulate, keep_obs0):
     T = int(T)
     if T < 1:
       raise ValueError("policy_step_n: T must be >= 1")
@@ -911,11 +922,165 @@ class BatchedEngine(object):
     acts = tapes.get(T)
     if acts is None:
       acts = tapes[T] = torch.zeros((T, self.n_envs, self.spec.A), dtype=torch.int8, device=self.device)
+    if keep_obs0:
+      side = self._obs0_side(policy)
+      side.copy_(obs0)
+      obs0 = side
     N.check(self._lib.sgw_policy_step_n(self._h, C.byref(policy.native()), obs0.data_ptr(), T, 1 if write_every else 0, C.byref(self._out),
                                         acts.data_ptr(), 1 if accumulate else 0, self._stream()), "sgw_policy_step_n")
     res = self._views()
     res["actions"] = acts
+    if keep_obs0:
+      res["obs0"] = obs0[:self.n_envs]
     return res
+
+  # -- learning a table policy (csrc/sgw_learn.hpp) ---------------------------------------------
+  def _obs0_side(self, policy):
+    """The persistent [N_pad, row] copy of the observation a policy_rollout call started from, per source."""
+    sides = self.__dict__.setdefault("_obs0_sides", {})
+    side = sides.get(policy.source)
+    if side is None:
+      src = self._policy_source(policy, "policy_step_n")
+      side = sides[policy.source] = torch.zeros_like(src)
+    return side
+
+  def _learn_observations(self, policy, T, obs0, obs, actions, what, need_actions):
+    """(obs0 pointer, obs pointer or None, obs_rows, actions tensor or None) of the T + 1 observations O[0..T] a learning call
+    reads: the caller's tensors, or what the last policy_rollout(policy, T) left in the engine."""
+    src = self._policy_source(policy, what)
+    row, n, n_pad = src.shape[-1], self.n_envs, self.n_pad
+
+    def rows_of(t, lead, name):
+      ok = torch.is_tensor(t) and t.device == self.device and t.dtype == torch.uint8 and t.is_contiguous()
+      if ok and t.numel() == lead * n * row:
+        return n
+      if ok and t.numel() == lead * n_pad * row:
+        return n_pad
+      raise N.SgwError("%s: %s must be a contiguous uint8 [%s%d or %d, %d] tensor on %s (there is no CPU path)"
+                       % (what, name, "%d, " % lead if lead > 1 else "", n, n_pad, row, self.device))
+
+    if obs0 is None:
+      if T == 0:
+        obs0 = src
+      else:
+        obs0 = self.__dict__.get("_obs0_sides", {}).get(policy.source)
+        if obs0 is None:
+          raise N.SgwError("%s: no obs0: pass it, or run policy_rollout(policy, T) first" % what)
+    else:
+      rows_of(obs0, 1, "obs0")
+    obs_ptr, obs_rows = None, n
+    if T > 0:
+      if obs is None:
+        if self._T != T or policy.source not in self._bufs:
+          raise N.SgwError("%s(T=%d) needs the %r output of a write_every call over %d steps (the engine holds T=%d buffers)"
+                           % (what, T, policy.source, T, self._T))
+        obs_ptr, obs_rows = self._bufs[policy.source].data_ptr(), n_pad
+      else:
+        obs_rows = rows_of(obs, T, "obs")
+        obs_ptr = obs.data_ptr()
+    if actions is None and need_actions:
+      actions = self.__dict__.get("_policy_tapes", {}).get(T)
+      if actions is None and need_actions == "required":
+        raise N.SgwError("%s: no actions: pass the int8 [T, N, A] tape, or run policy_rollout(policy, T) first" % what)
+    if actions is not None and not (torch.is_tensor(actions) and actions.device == self.device and actions.dtype == torch.int8
+                                    and actions.is_contiguous() and actions.numel() == T * n * self.spec.A):
+      raise N.SgwError("%s: actions must be a contiguous int8 [%d, %d, %d] tensor on %s (there is no CPU path)"
+                       % (what, T, n, self.spec.A, self.device))
+    return obs0.data_ptr(), obs_ptr, obs_rows, actions
+
+  def policy_scores(self, policy, T=0, obs0=None, obs=None, actions=None):
+    """The score vectors a TablePolicy computes on the T + 1 observations O[0..T] of a closed-loop call (sgw_policy_scores: one
+    launch, no synchronisation, capturable): {"scores": float32 [T+1, N, A, n_actions], "vmax": float64 [T+1, N, A] (the score of
+    the greedy action: vmax[1:] and vmax[0] are td_targets' values and value0), "chosen": float64 [T, N, A] (the score of the
+    action played, with a tape)}.  obs0 uint8 [N or N_pad, row]: O[0]; obs uint8 [T, N or N_pad, row]: O[1..T]; actions int8
+    [T, N, A].  Defaults: what policy_rollout(policy, T) left in the engine (T == 0: the engine's current
+    observation).  The result tensors are persistent per T and rewritten by the next call.  There is no CPU path."""
+    T = int(T)
+    if T < 0:
+      raise ValueError("policy_scores: T must be >= 0")
+    if self._h is None:
+      raise N.SgwError("policy_scores: the engine has no device engine behind it (closed?); there is no CPU path")
+    p0, p1, rows, actions = self._learn_observations(policy, T, obs0, obs, actions, "policy_scores", "optional" if T > 0 else None)
+    n, A = self.n_envs, self.spec.A
+    cache = self.__dict__.setdefault("_score_bufs", {})
+    c = cache.get((T, policy.n_actions))
+    if c is None:
+      c = cache[(T, policy.n_actions)] = (torch.zeros((T + 1, n, A, policy.n_actions), dtype=torch.float32, device=self.device),
+                                          torch.zeros((T + 1, n, A), dtype=torch.float64, device=self.device),
+                                          torch.zeros((T, n, A), dtype=torch.float64, device=self.device))
+    scores, vmax, chosen = c
+    want_chosen = actions is not None and T > 0
+    N.check(self._lib.sgw_policy_scores(self._h, C.byref(policy.native()), p0, p1, rows, T, actions.data_ptr() if want_chosen else None,
+                                        scores.data_ptr(), vmax.data_ptr(), chosen.data_ptr() if want_chosen else None, self._stream()),
+            "sgw_policy_scores")
+    res = {"scores": scores, "vmax": vmax}
+    if want_chosen:
+      res["chosen"] = chosen
+    return res
+
+  def policy_accumulate(self, policy, coef, T, obs0, obs=None, actions=None, frac_bits=24):
+    """Adds the fixed-point gradient sums of T x N x A transitions into the policy's int64 accumulators (sgw_policy_accumulate: one
+    launch, no synchronisation, capturable): with q = rint(coef[t, n, a] * 2^frac_bits) (saturated at +-(2^31 - 1), NaN -> 0) and
+    j the action played, acc_bias[p, a, j] += q and acc_weights[p, a, c, code(o[c]), j] += q for every cell c of the observation
+    the action was chosen on.  Integer sums: the same bits whatever the order, run after run.  coef: float64 [T, N, A]; obs0 / obs
+    / actions as for policy_scores (None: what the last policy_rollout left).  Calls add up until policy_apply(clear=True)."""
+    T = int(T)
+    if T < 1:
+      raise ValueError("policy_accumulate: T must be >= 1")
+    if self._h is None:
+      raise N.SgwError("policy_accumulate: the engine has no device engine behind it (closed?); there is no CPU path")
+    frac_bits = int(frac_bits)
+    if policy.acc_frac_bits is not None and policy.acc_frac_bits != frac_bits:
+      raise N.SgwError("policy_accumulate: the accumulators hold sums with frac_bits=%d; apply them (clear=True) before frac_bits=%d"
+                       % (policy.acc_frac_bits, frac_bits))
+    n, A = self.n_envs, self.spec.A
+    if not (torch.is_tensor(coef) and coef.device == self.device and coef.dtype == torch.float64 and coef.is_contiguous()
+            and coef.numel() == T * n * A):
+      raise N.SgwError("policy_accumulate: coef must be a contiguous float64 [%d, %d, %d] tensor on %s (there is no CPU path)"
+                       % (T, n, A, self.device))
+    p0, p1, rows, actions = self._learn_observations(policy, T, obs0, obs, actions, "policy_accumulate", "required")
+    N.check(self._lib.sgw_policy_accumulate(self._h, C.byref(policy.native()), p0, p1, rows, T, actions.data_ptr(), coef.data_ptr(), frac_bits,
+                                            policy.acc_weights.data_ptr(), policy.acc_bias.data_ptr(), self._stream()),
+            "sgw_policy_accumulate")
+    policy.acc_frac_bits = frac_bits
+
+  def policy_apply(self, policy, lr, clear=True):
+    """weights += lr * acc_weights * 2^-frac_bits (and the bias alike), in place, from ONE launch (sgw_policy_apply): per element
+    w = float32(float64(w) + lr * (float64(acc) * 2^-frac_bits)); an element whose sum is 0 is not written.  frac_bits is the one
+    the sums were accumulated with.  clear=True zeroes the accumulators behind the update."""
+    if self._h is None:
+      raise N.SgwError("policy_apply: the engine has no device engine behind it (closed?); there is no CPU path")
+    self._policy_source(policy, "policy_apply")
+    frac_bits = 24 if policy.acc_frac_bits is None else policy.acc_frac_bits
+    N.check(self._lib.sgw_policy_apply(self._h, C.byref(policy.native()), float(lr), frac_bits, policy.acc_weights.data_ptr(),
+                                       policy.acc_bias.data_ptr(), N.APPLY_CLEAR if clear else 0, self._stream()), "sgw_policy_apply")
+    if clear:
+      policy.acc_frac_bits = None
+
+  def q_learn(self, policy, T, gamma, lr, bootstrap_truncated=False, frac_bits=24):
+    """One iteration of tabular / linear Q-learning over T closed-loop steps of every env, all on the device and on one stream:
+      1. policy_rollout(policy, T)                                  the epsilon-greedy rollout, O[0] kept
+      2. policy_scores(T)                                           vmax[s] = max_j Q(O[s], j), chosen[t] = Q(O[t], action[t])
+      3. td_targets(T, gamma, lam=0.0, values=vmax[1:], value0=vmax[0], scalar=True)
+      4. delta = (advantages + vmax[:-1]) - chosen, 0 where not valid    (advantages + vmax[t] = r + gamma * max Q(O[t+1]), cut at
+                                                                          episode ends; FIRST rows after an auto-reset and DEAD
+                                                                          agents carry 0 and are skipped)
+      5. policy_accumulate(delta)                                   the integer gradient sums
+      6. policy_apply(lr)                                           weights += lr * sums
+    Returns the rollout's dict with "delta" float64 [T, N, A] and "valid" bool [T, N, A] added.  There is no CPU path."""
+    T = int(T)
+    traj = self.policy_rollout(policy, T)
+    sc = self.policy_scores(policy, T)
+    vmax, chosen = sc["vmax"], sc["chosen"]
+    n, A = self.n_envs, self.spec.A
+    td = self.td_targets(T, gamma, lam=0.0, values=vmax[1:], value0=vmax[0], bootstrap_truncated=bootstrap_truncated, scalar=True)
+    adv, valid = td["advantages"].reshape(T, n, A), td["valid"].reshape(T, n, A)
+    delta = (adv + vmax[:-1]) - chosen
+    delta = torch.where(valid, delta, torch.zeros((), dtype=torch.float64, device=self.device))
+    self.policy_accumulate(policy, delta, T, None, frac_bits=frac_bits)
+    self.policy_apply(policy, lr, clear=True)
+    traj["delta"], traj["valid"] = delta, valid
+    return traj
 
   # -- what each action would do (csrc/sgw_whatif.hpp) ----------------------------------------
   def _whatif_input(self, name, t, what):

@@ -80,6 +80,24 @@ class TablePolicy(object):
     self.policy_of_env = None
     self.step = torch.zeros(1, dtype=torch.int64, device=dev)
     self._struct = None
+    self._acc = None          # (acc_weights, acc_bias): the int64 gradient sums, allocated on first use
+    self.acc_frac_bits = None  # the frac_bits of the sums now in the accumulators (None: they are zero)
+
+  @property
+  def acc_weights(self):
+    """int64 [P, A, C, G, n_actions]: the fixed-point gradient sums of policy_accumulate (zeroed; allocated on first use)."""
+    return self._accumulators()[0]
+
+  @property
+  def acc_bias(self):
+    """int64 [P, A, n_actions]: the bias's gradient sums."""
+    return self._accumulators()[1]
+
+  def _accumulators(self):
+    if self._acc is None:
+      self._acc = (torch.zeros(tuple(self.weights.shape), dtype=torch.int64, device=self.device),
+                   torch.zeros(tuple(self.bias.shape), dtype=torch.int64, device=self.device))
+    return self._acc
 
   def code(self, ch):
     """The code of a byte (0 for every byte that is not among chars)."""

@@ -476,6 +476,59 @@ typedef struct sgw_td {
 int sgw_sizeof_td(void);
 int sgw_td_targets(sgw_engine* e, const sgw_td* td, void* stream);
 
+/* Learning a table policy on the device.  The table is a Q-table that is linear in the one-hot observation: score[j] = Q(s, j).
+ * Three calls close the loop rollout -> scores -> targets -> gradient sums -> update for any rule of the form
+ * weights += lr * sum(coef * one-hot), with no host round trip and the same bits on every run.
+ * OBSERVATIONS, as sgw_policy_step_n plays: T + 1 observations O[0 .. T]; O[0] = obs0_dev ([>= N, row_bytes]), O[s] for s >= 1 =
+ * row s-1 of obs_dev ([T, obs_rows, row_bytes]; obs_rows = N_pad for the engine's buffers, N for plain tensors, >= N).  row_bytes,
+ * C_a and the agents' byte offsets are those of sgw_policy_act for the policy's source.  Every O[s] that a call reads must be
+ * 16-byte aligned.  Rows n >= N are neither read nor written anywhere.  p = policy_of_env ? policy_of_env[n] : 0.  actions_dev is
+ * the int8 [T, N, A] tape sgw_policy_step_n wrote: the action of step t was chosen on O[t].
+ *
+ * sgw_policy_scores: the score vector sgw_policy_act computes and discards -- the same float32 additions in the same order (bias
+ * first, then cells c = 0 .. C_a-1) -- for every observation, env and agent.  T >= 0 (obs_dev may be NULL at T == 0).  Outputs, any
+ * may be NULL but not all:
+ *   scores float32 [T+1, N, A, n_actions]
+ *   vmax   double  [T+1, N, A] = (double)score[best], best the first maximum of sgw_policy_act's scan (a NaN never displaces)
+ *   chosen double  [T, N, A]   = (double)score_of_O[t][actions[t][n][a] - action_lo]; needs actions_dev; an action outside the
+ *                                spec's range gives +0.0
+ * A policy index p outside 0 .. P-1 gives +0.0 everywhere for that env; an agent without a window (C_a == 0) gets its bias.
+ * vmax[1:] and vmax[0] are sgw_td_targets' value and value0 (C = 1) as they stand.
+ * SGW_ERR_ARG: as sgw_policy_act, and: T < 0; a null obs0 (or obs with T >= 1); obs_rows < N; all outputs NULL; chosen without
+ * actions; a misaligned array.  One launch: no allocation, no synchronisation, capturable. */
+int sgw_policy_scores(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, const uint8_t* obs_dev, int64_t obs_rows, int T,
+                      const int8_t* actions_dev /* [T, N, A] or NULL */, float* scores_dev, double* vmax_dev, double* chosen_dev,
+                      void* stream);
+/* The transpose of the score sum, in FIXED POINT.  For every transition (t < T, n < N, a < A), with j = actions[t][n][a] -
+ * action_lo, o = agent a's bytes in O[t] and coef_dev double [T, N, A]:
+ *   x = coef * 2^frac_bits                       (frac_bits 0 .. 52)
+ *   q = 0 if x is NaN;  q = 2^31 - 1 if x >= 2147483647.0;  q = -(2^31 - 1) if x <= -2147483647.0;
+ *   q = (int64)rint(x) otherwise (ties to even)
+ * The transition is skipped when p is outside 0 .. P-1, when j is outside 0 .. n_actions-1 or when q == 0; otherwise
+ *   acc_bias[p][a][j] += q                                       (when acc_bias_dev is given)
+ *   acc_weights[p][a][c][code_of[o[c]]][j] += q                  for every c < C_a
+ * acc_weights_dev int64 [P, A, C, n_codes, n_actions] and acc_bias_dev int64 [P, A, n_actions] are in/out and caller-owned: zero
+ * them once, calls add up.  |q| < 2^31 and T * N < 2^32, so no sum wraps; the sums are integers, so they do not depend on the
+ * order of the additions: any schedule is correct and two runs give the same bits (float atomics would not; a fixed float order
+ * would serialise the additions of a bin).  O[T] is not read.
+ * SGW_ERR_ARG: as sgw_policy_act, and: a null actions, coef or acc_weights; T < 1; T * N >= 2^32; frac_bits outside 0 .. 52; a
+ * misaligned array; an accumulator that equals an input pointer or the other accumulator.  SGW_ERR_UNSUPPORTED: as
+ * sgw_policy_act, and an observation row of more than 2048 bytes.  One launch on the caller's stream: no allocation, no
+ * synchronisation, capturable. */
+int sgw_policy_accumulate(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, const uint8_t* obs_dev, int64_t obs_rows,
+                          int T, const int8_t* actions_dev, const double* coef_dev, int frac_bits, int64_t* acc_weights_dev,
+                          int64_t* acc_bias_dev /* or NULL */, void* stream);
+/* The update, per element of the policy's weights (and of its bias, when the policy has one and acc_bias_dev is given); the
+ * tables are WRITTEN through the policy's pointers:
+ *   acc == 0: the element is not written (its bits stay, a -0.0 included)
+ *   else w = (float)((double)w + lr * ((double)acc * 2^-frac_bits)): one rounding int64 -> double, an exact scaling, one double
+ *   multiplication, one double addition, one rounding to float; nothing is fused.
+ * SGW_APPLY_CLEAR zeroes the accumulators behind the update.  SGW_ERR_ARG: as sgw_policy_act, and: a null acc_weights; frac_bits
+ * outside 0 .. 52; unknown flag bits; a misaligned accumulator; an accumulator that equals a table.  One launch, capturable. */
+#define SGW_APPLY_CLEAR 1
+int sgw_policy_apply(sgw_engine* e, const sgw_policy* p, double lr, int frac_bits, int64_t* acc_weights_dev,
+                     int64_t* acc_bias_dev /* or NULL */, int flags, void* stream);
+
 /* Per-env performance bookkeeping of SafetyEnvironment{,Mo}: _episodic_performances.append(...) at every LAST timestep
  * (safety_game.py:253-263, 301-302; safety_game_mo.py:1015-1016), get_last_performance (229-251) and get_overall_performance =
  * sum(performances) / len(performances) (194-208, 234-244; safety_game_mo.py:917-938).  perf_dev double [N, C] is the step's
