@@ -60,6 +60,34 @@ def _view_bytes(spec):
   return int(sum(h * w for (h, w) in (getattr(spec, "view_shapes", None) or ())))
 
 
+def _require(what, name, t, device, dtype, numel, layout="", contiguous=True, shape=None, also=None):
+  """The one check of a tensor argument: `t` is a tensor on `device` of `dtype` (one, or a tuple of accepted ones), contiguous
+  unless told otherwise, with `numel` elements (an int, a tuple of accepted ints, None: any), of `shape` if given, and `also(t)`
+  holds if given.  Returns the element count that matched; SgwError otherwise, `layout` being the caller's words for the shape."""
+  dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+  if (torch.is_tensor(t) and t.device == device and t.dtype in dtypes and (t.is_contiguous() or not contiguous)
+      and (shape is None or tuple(t.shape) == tuple(shape)) and (also is None or also(t))):
+    for m in (numel if isinstance(numel, tuple) else (numel,)):
+      if m is None or t.numel() == m:
+        return m
+  names = [str(d).replace("torch.", "") for d in dtypes]
+  raise N.SgwError("%s: %s must be a %s%s %stensor on %s (there is no CPU path)"
+                   % (what, name, "contiguous " if contiguous else "", names[0] + "".join(" (or %s)" % d for d in names[1:]),
+                      layout + " " if layout else "", device))
+
+
+# the derived statistics of _process_timestep, in the order of the columns of sgw_derived_stats (average_reward: the K after them)
+STAT_NAMES = ("gini_index", "cumulative_gini_index", "mo_variance", "cumulative_mo_variance", "average_mo_variance")
+
+
+def _stats_dict(stats):
+  """float64 [N, A, 5 + K] of sgw_derived_stats -> {name: [N(, A)]} and average_reward [N(, A), K], views of it."""
+  st = stats[:, 0] if stats.shape[1] == 1 else stats
+  out = {nm: st[..., i] for i, nm in enumerate(STAT_NAMES)}
+  out["average_reward"] = st[..., len(STAT_NAMES):]
+  return out
+
+
 class EpisodeLog(object):
   """A device-side, append-only log of finished episodes (sgw_log_episodes): the reference's _episodic_performances
   (safety_game.py:253-263) for a whole batch, one record per episode in the order (step, env), with
@@ -140,9 +168,16 @@ class EpisodeLog(object):
     return out
 
 
+# what the reference raises for an action array of the wrong size (pycolab_interface.py:160-163)
+_BAD_ACTIONS = ("A pycolab Environment adapter's step method was called with actions that were "
+                "not compatible with what the pycolab game expects.")
+
+
 class BatchedEngine(object):
+  _fold_key = None           # (also the fallback when a caller drops the instance's to make fold_q_values start a new table)
 
   def __init__(self, spec, n_envs, device="cuda:0", env_id_base=0, outputs=DEFAULT_OUTPUTS):
+    self._h = self._look = None      # (close() runs from __del__ even when the lines below raise)
     self.spec = spec
     self.n_envs = int(n_envs)
     self.device = torch.device(device)
@@ -163,32 +198,91 @@ class BatchedEngine(object):
     for name in self.outputs:
       if name not in N.OUT_FIELDS:
         raise KeyError("unknown output %r" % name)
+    self.view_bytes = int(self._lib.sgw_view_bytes(h))     # one env's row of agent windows; what _dtype_shape sizes `views` by
+    assert self.view_bytes == _view_bytes(spec)
     self._bufs = {}
     self._out = N.Out()
+    self._views_cache = None
     self._alloc_outputs(1)
-    self._keep = []          # tensors the library holds raw pointers to
-    self._inputs = {}        # what set_episode_bits / set_random_stream were given: (device tensor or None, seed), for fork()
+    # what set_episode_bits / set_random_stream were given: (device tensor or None, seed).  The library points at the tensor, so
+    # this dict is what keeps it alive (and fork() re-applies it); the next set_* call releases it.
+    self._inputs = {}
     self._look = None        # lookahead()'s cached fork and result tensors
+    # lazily created, each by the method named; _persistent() keeps the result buffers that are keyed per call
+    self._kept = {}          # (kind, key) -> tensors: scalarise, td_targets, policy tapes, obs0 sides, policy_scores
+    self._full = None        # step_full: the sgw_extras of the last flag set and its tensors
+    self._karr = None        # _k_agent
+    self._layers = None      # _layer_tables
+    self._act_out = None     # act
+    self._whatif_out = None  # simulate_moves
+    self._fold_key = self._fold_chars = None       # fold_q_values, with the three below
+    self.q_value_per_tiletype = self.q_value_seen = self.q_value_tile_chars = None
     table = getattr(spec, "family_table", None)
     if table is not None:    # aintelope_savanna: host-evaluated visit-count rewards (sgw_set_family_table)
       table = np.ascontiguousarray(table, dtype=np.float64)
       N.check(self._lib.sgw_set_family_table(self._h, table.ctypes.data, table.size), "sgw_set_family_table")
 
   # -- buffers ----------------------------------------------------------------------------------
+  def _new_output(self, name, dtype, shape):
+    """One output buffer (a subclass may allocate it otherwise: tests/output_subsets.py puts guard bytes around it)."""
+    return torch.zeros(shape, dtype=dtype, device=self.device)
+
   def _alloc_outputs(self, T):
     self._T = T
     self._views_cache = None
     for name in self.outputs:
       dt, shp = _dtype_shape(self.spec, name)
-      lead = (T, self.n_pad) if T > 1 else (self.n_pad,)
-      self._bufs[name] = torch.zeros(lead + shp, dtype=dt, device=self.device)
+      self._bufs[name] = self._new_output(name, dt, ((T, self.n_pad) if T > 1 else (self.n_pad,)) + shp)
     for name in N.OUT_FIELDS:
       setattr(self._out, name, self._bufs[name].data_ptr() if name in self._bufs else None)
+
+  def _want_T(self, T=1, write_every=False):
+    """Output buffers for a call that writes T rows per env with write_every and one otherwise: [T, N_pad, ...] or [N_pad, ...]."""
+    want = T if write_every else 1
+    if self._T != want:
+      self._alloc_outputs(want)
+
+  def _open(self, what):
+    if self._h is None:
+      raise N.SgwError("%s: the engine has no device engine behind it (closed?); there is no CPU path" % what)
+
+  def _persistent(self, kind, key, make=None):
+    """The result buffers of `kind` for `key`, made once by make() and reused by every later call (callers compare their
+    data_ptr()s across calls; a per-step call allocates nothing).  make=None only looks: None when no call has made them."""
+    c = self._kept.get((kind, key))
+    if c is None and make is not None:
+      c = self._kept[(kind, key)] = make()
+    return c
+
+  def _row(self, name):
+    """(dtype, elements per env) of output `name`."""
+    dt, shp = _dtype_shape(self.spec, name)
+    return dt, int(np.prod(shp, dtype=np.int64))
+
+  def _latest(self, name, t, what, optional=False):
+    """The latest [N or N_pad, row] rows of output `name`: the caller's tensor `t` checked, or the engine's own buffer (its last
+    row block after a write_every call).  optional: None when the engine does not write that output."""
+    if t is None:
+      t = self._bufs.get(name)
+      if t is None:
+        if optional:
+          return None
+        raise N.SgwError("%s: the %r output is not among this engine's outputs (%r); pass it or ask for it" % (what, name, self.outputs))
+      return t[-1] if self._T > 1 else t
+    self._rows_of(what, name, t, *self._row(name))
+    return t
+
+  def _rows_of(self, what, name, t, dtype, row, lead=1):
+    """N or N_pad: the rows per step of a caller's [lead, N or N_pad, row] tensor (with lead == 1: [N or N_pad, row])."""
+    n, n_pad = self.n_envs, self.n_pad
+    m = _require(what, name, t, self.device, dtype, (lead * n * row, lead * n_pad * row),
+                 "[%s%d or %d, %d]" % ("%d, " % lead if lead > 1 else "", n, n_pad, row))
+    return n if m == lead * n * row else n_pad
 
   def _views(self):
     """{name: view of the persistent output buffer}: the views only change with a reallocation, so they are built once (a step
     from Python is host-bound: every microsecond here is throughput)."""
-    if getattr(self, "_views_cache", None) is not None:
+    if self._views_cache is not None:
       return dict(self._views_cache)
     out = {}
     for name, t in self._bufs.items():
@@ -213,8 +307,7 @@ class BatchedEngine(object):
   # -- API --------------------------------------------------------------------------------------
   def reset(self, mask=None):
     """New episode in every env (or where mask[n] != 0).  Returns the FIRST timestep arrays."""
-    if self._T != 1:
-      self._alloc_outputs(1)
+    self._want_T()
     mptr = None
     if mask is not None:
       mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
@@ -231,8 +324,7 @@ class BatchedEngine(object):
     if actions.dtype != torch.int8 or actions.device != self.device or not actions.is_contiguous():
       actions = actions.to(device=self.device, dtype=torch.int8).contiguous()
     if actions.numel() != self.n_envs * self.spec.A:
-      raise RuntimeError("A pycolab Environment adapter's step method was called with actions that were "
-                         "not compatible with what the pycolab game expects.")   # pycolab_interface.py:160-163
+      raise RuntimeError(_BAD_ACTIONS)
     N.check(self._lib.sgw_step(self._h, actions.data_ptr(), C.byref(self._out), self._stream()), "sgw_step")
     return self._views()
 
@@ -260,10 +352,9 @@ class BatchedEngine(object):
     if actions.dtype != torch.int8 or actions.device != self.device or not actions.is_contiguous():
       actions = actions.to(device=self.device, dtype=torch.int8).contiguous()
     if actions.numel() != self.n_envs * sp.A:
-      raise RuntimeError("A pycolab Environment adapter's step method was called with actions that were "
-                         "not compatible with what the pycolab game expects.")
+      raise RuntimeError(_BAD_ACTIONS)
     key = (bool(rgb), bool(layers or agent_layer_views), bool(stats), bool(agent_layer_views), bool(performance), bool(replay))
-    fx = getattr(self, "_full", None)
+    fx = self._full
     if fx is None or fx["key"] != key or fx["for"] is not self._bufs.get("step_type", self._bufs.get("board")):
       n, dev = self.n_envs, self.device
       x, t, res = N.Extras(), {}, {}
@@ -274,36 +365,23 @@ class BatchedEngine(object):
         x.rgb, x.rgb_lut_dev = res["RGB"].data_ptr(), t["lut"].data_ptr()
       if key[1]:
         L = len(sp.layer_chars)
-        t["chars"] = torch.tensor([ord(c) for c in sp.layer_chars], dtype=torch.uint8, device=dev)
+        chars, stat, x.gap_index, x.hidden_layer = self._layer_tables()
         res["layers"] = torch.empty((n, L, sp.H, sp.W), dtype=torch.uint8, device=dev)
-        x.layers, x.layer_chars_dev, x.n_layers = res["layers"].data_ptr(), t["chars"].data_ptr(), L
-        x.gap_index = sp.layer_chars.index(sp.what_lies_beneath) if sp.what_lies_beneath in sp.layer_chars else -1
-        hidden = getattr(sp, "hidden_layer_char", None)
-        x.hidden_layer = sp.layer_chars.index(hidden) if hidden is not None else -1
-        if not getattr(sp, "layers_from_state", False):
-          t["stat"] = torch.from_numpy(sp.layer_static()).to(dev)
-          x.layer_static_dev = t["stat"].data_ptr()
+        x.layers, x.layer_chars_dev, x.n_layers = res["layers"].data_ptr(), chars.data_ptr(), L
+        if stat is not None:
+          x.layer_static_dev = stat.data_ptr()
       else:
         x.hidden_layer, x.gap_index = -1, -1
       if key[2]:
         t["stats"] = torch.empty((n, sp.A, 5 + sp.K), dtype=torch.float64, device=dev)
         x.stats = t["stats"].data_ptr()
-        for i, k in enumerate(self._agent_ks()):
-          x.k_agent[i] = k
-        st = t["stats"][:, 0] if sp.A == 1 else t["stats"]
-        for i, nm in enumerate(("gini_index", "cumulative_gini_index", "mo_variance", "cumulative_mo_variance", "average_mo_variance")):
-          res[nm] = st[..., i]
-        res["average_reward"] = st[..., 5:]
+        x.k_agent = self._k_agent()                                   # (a struct field: copied by value)
+        res.update(_stats_dict(t["stats"]))
       if key[3]:
-        vb = int(self._lib.sgw_view_bytes(self._h))
         L = len(sp.layer_chars)
-        t["cubes"] = torch.empty((n, vb * L), dtype=torch.uint8, device=dev)
+        t["cubes"] = torch.empty((n, self.view_bytes * L), dtype=torch.uint8, device=dev)
         x.agent_layer_views = t["cubes"].data_ptr()
-        cubes, off = [], 0
-        for (h, w) in sp.view_shapes:
-          cubes.append(t["cubes"][:, off:off + L * h * w].reshape(n, L, h, w))
-          off += L * h * w
-        res["agent_layer_views"] = cubes
+        res["agent_layer_views"] = self.split_views(t["cubes"], L)
       if key[4]:
         use_hidden = sp.scalar and getattr(sp, "performance", "hidden") == "hidden"
         C_ = 1 if use_hidden else sp.A * sp.K
@@ -322,6 +400,13 @@ class BatchedEngine(object):
       fx["all"].update(fx["res"])
     return dict(fx["all"])
 
+  def _tape(self, actions):
+    """T of an action tape int8 [T, N(, A)] for step_n / replay, which take it as it is: resident on the device, contiguous."""
+    T = int(actions.shape[0])
+    assert actions.dtype == torch.int8 and actions.is_contiguous() and actions.device == self.device
+    assert actions.numel() == T * self.n_envs * self.spec.A
+    return T
+
   def step_ptr(self, actions_ptr):
     """Launch-only variant for tight loops: raw device pointer, no tensor checks, no views."""
     N.check(self._lib.sgw_step(self._h, actions_ptr, C.byref(self._out), self._stream()), "sgw_step")
@@ -329,12 +414,8 @@ class BatchedEngine(object):
   def step_n(self, actions, write_every=False, accumulate=False):
     """actions int8 [T, N(, A)] resident on the device: T step launches issued from C (no Python in
     the loop).  Returns the last step's arrays, or [T, N, ...] arrays with write_every."""
-    T = int(actions.shape[0])
-    assert actions.dtype == torch.int8 and actions.is_contiguous() and actions.device == self.device
-    assert actions.numel() == T * self.n_envs * self.spec.A
-    want_T = T if write_every else 1
-    if self._T != want_T:
-      self._alloc_outputs(want_T)
+    T = self._tape(actions)
+    self._want_T(T, write_every)
     N.check(self._lib.sgw_step_n(self._h, actions.data_ptr(), T, 1 if write_every else 0, C.byref(self._out),
                                  1 if accumulate else 0, self._stream()), "sgw_step_n")
     return self._views()
@@ -349,9 +430,7 @@ class BatchedEngine(object):
 
   def rollout(self, T, seed, step0=0, write_every=False, accumulate=False):
     """T fused steps with in-kernel synthetic actions.  write_every: outputs become [T, N, ...]."""
-    want_T = T if write_every else 1
-    if self._T != want_T:
-      self._alloc_outputs(want_T)
+    self._want_T(T, write_every)
     N.check(self._lib.sgw_rollout(self._h, int(T), int(seed), int(step0), 1 if write_every else 0,
                                   C.byref(self._out), 1 if accumulate else 0, self._stream()), "sgw_rollout")
     return self._views()
@@ -359,12 +438,8 @@ class BatchedEngine(object):
   def replay(self, actions, write_every=False, accumulate=False):
     """actions int8 [T, N(, A)] resident on the device: the T steps in ONE fused launch (state in registers), output for
     output what step_n gives for the same buffer."""
-    T = int(actions.shape[0])
-    assert actions.dtype == torch.int8 and actions.is_contiguous() and actions.device == self.device
-    assert actions.numel() == T * self.n_envs * self.spec.A
-    want_T = T if write_every else 1
-    if self._T != want_T:
-      self._alloc_outputs(want_T)
+    T = self._tape(actions)
+    self._want_T(T, write_every)
     N.check(self._lib.sgw_replay(self._h, actions.data_ptr(), T, 1 if write_every else 0, C.byref(self._out),
                                  1 if accumulate else 0, self._stream()), "sgw_replay")
     return self._views()
@@ -399,7 +474,6 @@ class BatchedEngine(object):
       return
     bits = torch.as_tensor(bits).to(device=self.device, dtype=torch.uint8).contiguous()
     assert bits.dim() == 2 and bits.shape[0] == self.n_envs
-    self._keep.append(bits)
     N.check(self._lib.sgw_set_episode_bits(self._h, bits.data_ptr(), bits.shape[1], int(seed)),
             "sgw_set_episode_bits")
     self._inputs["episode_bits"] = (bits, int(seed))
@@ -421,7 +495,6 @@ class BatchedEngine(object):
       u = torch.as_tensor(np.ascontiguousarray(u, dtype=np.float64))
     u = u.to(self.device).contiguous()
     assert u.dim() == 2 and u.shape[0] == self.n_envs
-    self._keep.append(u)
     N.check(self._lib.sgw_set_random_stream(self._h, u.data_ptr(), u.shape[1], int(seed)), "sgw_set_random_stream")
     self._inputs["random_stream"] = (u, int(seed))
 
@@ -489,32 +562,28 @@ class BatchedEngine(object):
   def _view_flags(self, agent_flags):
     if not getattr(self.spec, "rotating_views", False):
       return None
-    t = self._bufs["agent_flags"] if agent_flags is None else agent_flags
-    return t.data_ptr()
+    return self._latest("agent_flags", agent_flags, "agent views").data_ptr()
 
   def agent_views(self, board=None, agent_pos=None, outside_chr=None, agent_flags=None, out=None):
     """Agent-centric windows (safety_game_moma.py:1996-2101): list of uint8 [N, h_a, w_a] tensors, one per agent
     (rotated by the agent's observation direction when the env's observation_direction_mode is not 0).  `out`: a uint8
     [N, sgw_view_bytes] buffer to write into (a caller that steps in a loop reuses one buffer and its views)."""
-    board = self._bufs["board"] if board is None else board
-    agent_pos = self._bufs["agent_pos"] if agent_pos is None else agent_pos
+    board = self._latest("board", board, "agent_views")
+    agent_pos = self._latest("agent_pos", agent_pos, "agent_views")
     outside_chr = outside_chr or getattr(self.spec, "what_lies_outside", '#')
-    vb = int(self._lib.sgw_view_bytes(self._h))
-    views = torch.empty((self.n_envs, vb), dtype=torch.uint8, device=self.device) if out is None else out
+    views = torch.empty((self.n_envs, self.view_bytes), dtype=torch.uint8, device=self.device) if out is None else out
     N.check(self._lib.sgw_agent_views(self._h, board.data_ptr(), agent_pos.data_ptr(), self._view_flags(agent_flags),
                                       ord(outside_chr), views.data_ptr(), self._stream()), "sgw_agent_views")
-    out, off = [], 0
-    for (h, w) in self.spec.view_shapes:
-      out.append(views[:, off:off + h * w].reshape(self.n_envs, h, w))
-      off += h * w
-    return out
+    return self.split_views(views)
 
-  def split_views(self, views):
-    """[..., view_bytes] tensor (the `views` / `obs_views` output) -> list over agents of [..., h_a, w_a] views of it."""
+  def split_views(self, views, L=None):
+    """[..., view_bytes] tensor (the `views` / `obs_views` output) -> list over agents of [..., h_a, w_a] views of it; with L a
+    [..., L * view_bytes] tensor of per-agent layer cubes -> [..., L, h_a, w_a] views."""
     out, off = [], 0
     for (h, w) in self.spec.view_shapes:
-      out.append(views[..., off:off + h * w].reshape(views.shape[:-1] + (h, w)))
-      off += h * w
+      size = (L or 1) * h * w
+      out.append(views[..., off:off + size].reshape(views.shape[:-1] + ((h, w) if L is None else (L, h, w))))
+      off += size
     return out
 
   def agent_layer_views(self, layers=None, agent_pos=None, outside_chr=None, agent_flags=None):
@@ -523,21 +592,14 @@ class BatchedEngine(object):
     sp = self.spec
     if layers is None:
       layers = self.observe_layers()
-    agent_pos = self._bufs["agent_pos"] if agent_pos is None else agent_pos
+    agent_pos = self._latest("agent_pos", agent_pos, "agent_layer_views")
     outside_chr = outside_chr or getattr(sp, "what_lies_outside", '#')
     L = len(sp.layer_chars)
-    if not hasattr(self, "_layer_chars_dev"):        # (observe_layers builds its own tables only for board-derived layers)
-      self._layer_chars_dev = torch.tensor([ord(c) for c in sp.layer_chars], dtype=torch.uint8, device=self.device)
-    chars = self._layer_chars_dev
-    vb = int(self._lib.sgw_view_bytes(self._h))
-    out = torch.empty((self.n_envs, vb * L), dtype=torch.uint8, device=self.device)
+    chars = self._layer_tables()[0]
+    out = torch.empty((self.n_envs, self.view_bytes * L), dtype=torch.uint8, device=self.device)
     N.check(self._lib.sgw_agent_layer_views(self._h, layers.data_ptr(), agent_pos.data_ptr(), self._view_flags(agent_flags), chars.data_ptr(), L,
                                             ord(outside_chr), out.data_ptr(), self._stream()), "sgw_agent_layer_views")
-    res, off = [], 0
-    for (h, w) in sp.view_shapes:
-      res.append(out[:, off:off + L * h * w].reshape(self.n_envs, L, h, w))
-      off += L * h * w
-    return res
+    return self.split_views(out, L)
 
   def _coords_buffers(self, what, lead, cap, out):
     """(counts int32 lead, coords int16 lead + (cap, 2)) on this engine's device: the caller's `out` pair checked, or fresh zeros."""
@@ -545,9 +607,8 @@ class BatchedEngine(object):
       return (torch.zeros(lead, dtype=torch.int32, device=self.device),
               torch.zeros(lead + (cap, 2), dtype=torch.int16, device=self.device))
     counts, coords = out
-    for t, dt, shp in ((counts, torch.int32, lead), (coords, torch.int16, lead + (cap, 2))):
-      if not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
-        raise N.SgwError("%s: out must be (int32 %s, int16 %s) contiguous tensors on %s" % (what, list(lead), list(lead + (cap, 2)), self.device))
+    for i, (t, dt, shp) in enumerate(((counts, torch.int32, lead), (coords, torch.int16, lead + (cap, 2)))):
+      _require(what, "out[%d]" % i, t, self.device, dt, None, str(list(shp)), shape=shp)
     return counts, coords
 
   def layer_coords(self, layers=None, cap=None, out=None):
@@ -560,9 +621,8 @@ class BatchedEngine(object):
     if layers is None:
       layers = self.observe_layers()
     HW = sp.H * sp.W
-    if (not torch.is_tensor(layers) or layers.device != self.device or layers.dtype != torch.uint8 or layers.dim() < 2
-        or layers.shape[0] != self.n_envs or layers[0].numel() % HW):
-      raise N.SgwError("layer_coords: layers must be a uint8 [N, L, H, W] tensor on %s (there is no CPU path)" % (self.device,))
+    _require("layer_coords", "layers", layers, self.device, torch.uint8, None, "[N, L, H, W]", contiguous=False,
+             also=lambda t: t.dim() >= 2 and t.shape[0] == self.n_envs and not t[0].numel() % HW)
     layers = layers.contiguous()
     L = layers[0].numel() // HW
     cap = HW if cap is None else int(cap)
@@ -597,8 +657,8 @@ class BatchedEngine(object):
       raise N.SgwError("agent_layer_coords: the spec defines no agent views")
     if torch.is_tensor(agent_layer_views):
       t = agent_layer_views
-      if t.device != self.device or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != self.n_envs or t.shape[1] % vb or not t.is_contiguous():
-        raise N.SgwError("agent_layer_coords: the buffer must be a contiguous uint8 [N, L * view_bytes] tensor on %s (there is no CPU path)" % (self.device,))
+      _require("agent_layer_coords", "the buffer", t, self.device, torch.uint8, None, "[N, L * view_bytes]",
+               also=lambda t: t.dim() == 2 and t.shape[0] == self.n_envs and not t.shape[1] % vb)
       L, ptr = t.shape[1] // vb, t.data_ptr()
     else:                                       # the list must be the views of one [N, L * view_bytes] buffer, agent-major
       wins = list(agent_layer_views)
@@ -628,8 +688,7 @@ class BatchedEngine(object):
     (e.g. kept copies of the engine's).  Every field the log keeps needs its output: SgwError otherwise.  There is no CPU path."""
     if not isinstance(log, EpisodeLog):
       raise N.SgwError("log_episodes: needs an EpisodeLog (there is no CPU path)")
-    if self._h is None:
-      raise N.SgwError("log_episodes: the engine has no device engine behind it (closed?); there is no CPU path")
+    self._open("log_episodes")
     if log.n_envs != self.n_envs or log.device != self.device or log.layout != EpisodeLog.layout_of(self.spec):
       raise N.SgwError("log_episodes: the log was made for another engine (envs, device or record layout differ)")
     if outputs is None:
@@ -644,10 +703,8 @@ class BatchedEngine(object):
       for name, t in bufs.items():
         if name not in N.OUT_FIELDS:
           raise KeyError("unknown output %r" % name)
-        dt, shp = _dtype_shape(self.spec, name)
-        if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or not t.is_contiguous()
-            or t.numel() != rows * int(np.prod(shp, dtype=np.int64))):
-          raise N.SgwError("log_episodes: outputs[%r] must be a contiguous %s buffer of %d rows on %s" % (name, dt, rows, self.device))
+        dt, row = self._row(name)
+        _require("log_episodes", "outputs[%r]" % name, t, self.device, dt, rows * row, "%d-row" % rows)
         setattr(out, name, t.data_ptr())
     for f in log.fields:
       need = EpisodeLog.SOURCE.get(f)
@@ -690,33 +747,36 @@ class BatchedEngine(object):
     for k in ("reward", "cumulative", "frame"):
       if k not in self._bufs or self._T != 1:
         raise N.SgwError("derived_stats needs the 'reward', 'cumulative' and 'frame' outputs of a single step")
-    ks = self._agent_ks()
-    karr = (C.c_int32 * N.MAX_AGENTS)(*(ks + [0] * (N.MAX_AGENTS - len(ks))))
     stats = torch.empty((self.n_envs, sp.A, 5 + sp.K), dtype=torch.float64, device=self.device)
     N.check(self._lib.sgw_derived_stats(self._h, self._bufs["reward"].data_ptr(), self._bufs["cumulative"].data_ptr(),
-                                        self._bufs["frame"].data_ptr(), karr, stats.data_ptr(), self._stream()),
+                                        self._bufs["frame"].data_ptr(), self._k_agent(), stats.data_ptr(), self._stream()),
             "sgw_derived_stats")
-    if sp.A == 1:
-      stats = stats[:, 0]
-    names = ("gini_index", "cumulative_gini_index", "mo_variance", "cumulative_mo_variance", "average_mo_variance")
-    out = {nm: stats[..., i] for i, nm in enumerate(names)}
-    out["average_reward"] = stats[..., 5:]
-    return out
+    return _stats_dict(stats)
 
   # -- scalar rewards --------------------------------------------------------------------------
   def _k_agent(self):
     """The spec's reward dimensions per agent column as the HOST int32 array the library reads (built once)."""
-    karr = getattr(self, "_karr", None)
-    if karr is None:
+    if self._karr is None:
       ks = self._agent_ks()
-      karr = self._karr = (C.c_int32 * N.MAX_AGENTS)(*(ks + [0] * (N.MAX_AGENTS - len(ks))))
-    return karr
+      self._karr = (C.c_int32 * N.MAX_AGENTS)(*(ks + [0] * (N.MAX_AGENTS - len(ks))))
+    return self._karr
 
-  def _padded_source(self, name, t, T, what="scalarise"):
+  def _sources(self, what, names, listed, T, buffers):
+    """{name: data pointer} of the [T, N_pad, row] buffers of the outputs `names` that a call reads: the engine's own (which must
+    then be the buffers of T rows), or the caller's `buffers`.  listed: the names as the refusal spells them."""
+    if buffers is None:
+      if self._T != T or any(k not in self._bufs for k in names):
+        raise N.SgwError("%s(T=%d) needs the %s outputs of %s (the engine holds T=%d buffers of %s)"
+                         % (what, T, listed, "a single step" if T == 1 else "a write_every call over %d steps" % T, self._T, sorted(self._bufs)))
+      return {k: self._bufs[k].data_ptr() for k in names}
+    if any(k not in buffers for k in names):
+      raise N.SgwError("%s: buffers needs %s" % (what, listed))
+    return {k: self._padded_source(k, buffers[k], T, what) for k in names}
+
+  def _padded_source(self, name, t, T, what):
     """Data pointer of `t` as the [T, N_pad, row] buffer of output `name`: the padded buffer itself, or the [T, N, ...] view of it
     that a write_every call returned (same first byte, the padded strides)."""
-    dt, shp = _dtype_shape(self.spec, name)
-    row = int(np.prod(shp, dtype=np.int64))
+    dt, row = self._row(name)
     ok = torch.is_tensor(t) and t.device == self.device and t.dtype == dt and t.dim() >= (2 if T > 1 else 1)
     if ok and T > 1:
       ok = (t.shape[0] == T and t.shape[1] in (self.n_envs, self.n_pad) and t.stride(0) == self.n_pad * row and t[0].is_contiguous()
@@ -742,39 +802,27 @@ class BatchedEngine(object):
     T = int(T)
     if T < 1:
       raise ValueError("scalarise: T must be >= 1")
-    if self._h is None:
-      raise N.SgwError("scalarise: the engine has no device engine behind it (closed?); there is no CPU path")
-    if buffers is None:
-      if self._T != T or any(k not in self._bufs for k in ("reward", "cumulative", "frame")):
-        raise N.SgwError("scalarise(T=%d) needs the 'reward', 'cumulative' and 'frame' outputs of %s (the engine holds T=%d buffers of %s)"
-                         % (T, "a single step" if T == 1 else "a write_every call over %d steps" % T, self._T, sorted(self._bufs)))
-      ptrs = [self._bufs[k].data_ptr() for k in ("reward", "cumulative", "frame")]
-    else:
-      for k in ("reward", "cumulative", "frame"):
-        if k not in buffers:
-          raise N.SgwError("scalarise: buffers needs 'reward', 'cumulative' and 'frame'")
-      ptrs = [self._padded_source(k, buffers[k], T) for k in ("reward", "cumulative", "frame")]
-    cache = self.__dict__.setdefault("_scalars", {})
-    c = cache.get(T)
-    if c is None:
+    self._open("scalarise")
+    ptr = self._sources("scalarise", ("reward", "cumulative", "frame"), "'reward', 'cumulative' and 'frame'", T, buffers)
+
+    def make():
       A = self.spec.A
       bufs = [torch.zeros(((T, self.n_pad, A) if T > 1 else (self.n_pad, A)), dtype=torch.float64, device=self.device) for _ in range(3)]
       res = {}
       for name, b in zip(("scalar_reward", "scalar_cumulative", "scalar_average"), bufs):
         v = b[:, :self.n_envs] if T > 1 else b[:self.n_envs]
         res[name] = v[..., 0] if A == 1 else v
-      c = cache[T] = (bufs, res)
-    bufs, res = c
-    N.check(self._lib.sgw_scalarise(self._h, ptrs[0], ptrs[1], ptrs[2], T, self._k_agent(), bufs[0].data_ptr(), bufs[1].data_ptr(),
-                                    bufs[2].data_ptr(), self._stream()), "sgw_scalarise")
+      return bufs, res
+    bufs, res = self._persistent("scalars", T, make)
+    N.check(self._lib.sgw_scalarise(self._h, ptr["reward"], ptr["cumulative"], ptr["frame"], T, self._k_agent(), bufs[0].data_ptr(),
+                                    bufs[1].data_ptr(), bufs[2].data_ptr(), self._stream()), "sgw_scalarise")
     return dict(res)
 
   def scalarise_rows(self, rows):
     """The same left-to-right sum (sgw_scalarise) over the agents' reward dimensions of ANY float64 [N, A*K] device tensor laid
     out like the `reward` output (a last performance, a mean of performances): a new [N] (or [N, A]) tensor."""
     A, K = self.spec.A, self.spec.K
-    if (not torch.is_tensor(rows) or rows.device != self.device or rows.dtype != torch.float64 or rows.numel() != self.n_envs * A * K):
-      raise N.SgwError("scalarise_rows: needs a float64 [N, A*K] tensor on %s (there is no CPU path)" % (self.device,))
+    _require("scalarise_rows", "rows", rows, self.device, torch.float64, self.n_envs * A * K, "[N, A*K]", contiguous=False)
     rows = rows.contiguous()
     out = torch.empty((self.n_envs, A), dtype=torch.float64, device=self.device)
     N.check(self._lib.sgw_scalarise(self._h, rows.data_ptr(), None, None, 1, self._k_agent(), out.data_ptr(), None, None, self._stream()),
@@ -799,44 +847,25 @@ class BatchedEngine(object):
     T = int(T)
     if T < 1:
       raise ValueError("td_targets: T must be >= 1")
-    if self._h is None:
-      raise N.SgwError("td_targets: the engine has no device engine behind it (closed?); there is no CPU path")
+    self._open("td_targets")
     A, n = self.spec.A, self.n_envs
     Cn = 1 if scalar else self.spec.K
-    need = ["reward", "step_type"] + (["term_reason"] if bootstrap_truncated else [])
-    if buffers is None:
-      if self._T != T or any(k not in self._bufs for k in need):
-        raise N.SgwError("td_targets(T=%d) needs the %s outputs of %s (the engine holds T=%d buffers of %s)"
-                         % (T, ", ".join(repr(k) for k in need), "a single step" if T == 1 else "a write_every call over %d steps" % T,
-                            self._T, sorted(self._bufs)))
-      ptr = {k: self._bufs[k].data_ptr() for k in need}
-    else:
-      for k in need:
-        if k not in buffers:
-          raise N.SgwError("td_targets: buffers needs %s" % ", ".join(repr(k) for k in need))
-      ptr = {k: self._padded_source(k, buffers[k], T, "td_targets") for k in need}
+    need = ("reward", "step_type") + (("term_reason",) if bootstrap_truncated else ())
+    ptr = self._sources("td_targets", need, ", ".join(repr(k) for k in need), T, buffers)
     g = [float(gamma)] * Cn if np.ndim(gamma) == 0 else [float(x) for x in gamma]
     if len(g) != Cn:
       raise ValueError("td_targets: gamma must be a float or %d floats (one per reward column)" % Cn)
     if value0 is not None and values is None:
       raise ValueError("td_targets: value0 without values")
     for name, v, numel in (("values", values, T * n * A * Cn), ("value0", value0, n * A * Cn)):
-      if v is not None and not (torch.is_tensor(v) and v.device == self.device and v.dtype == torch.float64 and v.is_contiguous()
-                                and v.numel() == numel):
-        raise N.SgwError("td_targets: %s must be a contiguous float64 tensor of %d elements on %s (there is no CPU path)"
-                         % (name, numel, self.device))
-    cache = self.__dict__.setdefault("_targets", {})
-    c = cache.get((T, Cn))
-    if c is None:
-      ret, adv = (torch.zeros((T, n, A, Cn), dtype=torch.float64, device=self.device) for _ in range(2))
-      valid = torch.zeros((T, n, A), dtype=torch.uint8, device=self.device)
-      c = cache[(T, Cn)] = (ret, adv, valid)
-    ret, adv, valid = c
+      if v is not None:
+        _require("td_targets", name, v, self.device, torch.float64, numel, "%d-element" % numel)
+    ret, adv, valid = self._persistent("targets", (T, Cn), lambda: (
+        torch.zeros((T, n, A, Cn), dtype=torch.float64, device=self.device), torch.zeros((T, n, A, Cn), dtype=torch.float64, device=self.device),
+        torch.zeros((T, n, A), dtype=torch.uint8, device=self.device)))
     reward_ptr = ptr["reward"]
     if scalar:       # scalarise(T)["scalar_reward"]: the same launch, asked for that sum alone (needs neither 'cumulative' nor 'frame')
-      sr = cache.get(("scalar_reward", T))
-      if sr is None:
-        sr = cache[("scalar_reward", T)] = torch.zeros((T, self.n_pad, A), dtype=torch.float64, device=self.device)
+      sr = self._persistent("targets", ("scalar_reward", T), lambda: torch.zeros((T, self.n_pad, A), dtype=torch.float64, device=self.device))
       N.check(self._lib.sgw_scalarise(self._h, reward_ptr, None, None, T, self._k_agent(), sr.data_ptr(), None, None, self._stream()),
               "sgw_scalarise")
       reward_ptr = sr.data_ptr()
@@ -860,29 +889,24 @@ class BatchedEngine(object):
       raise N.SgwError("%s: the policy was built for another engine (spec, device or number of envs differ)" % what)
     if policy.source not in self._bufs:
       raise N.SgwError("%s: the policy reads the %r output, which this engine does not write (outputs=%r)" % (what, policy.source, self.outputs))
-    t = self._bufs[policy.source]
-    return t[-1] if self._T > 1 else t
+    return self._latest(policy.source, None, what)
 
   def act(self, policy, obs=None, out=None, t=0):
     """The actions a TablePolicy takes on `obs` (sgw_policy_act: one launch, no synchronisation): int8 [N, A].  obs: uint8
     [N or N_pad, H*W] board rows / [N or N_pad, view_bytes] window rows on this device (default: the engine's current `board` /
     `views` output).  The exploration draws are those of step policy.step + t; policy.step is not advanced.  out: an int8 [N, A]
     tensor to write into (default: a persistent buffer of the engine, rewritten by the next call)."""
+    src = self._policy_source(policy, "act")
     if obs is None:
-      obs = self._policy_source(policy, "act")
+      obs = src
     else:
-      src = self._policy_source(policy, "act")
-      row = src.shape[-1]
-      if (not torch.is_tensor(obs) or obs.device != self.device or obs.dtype != torch.uint8 or not obs.is_contiguous()
-          or obs.numel() not in (self.n_envs * row, self.n_pad * row)):
-        raise N.SgwError("act: obs must be a contiguous uint8 [%d or %d, %d] tensor on %s (there is no CPU path)"
-                         % (self.n_envs, self.n_pad, row, self.device))
+      self._rows_of("act", "obs", obs, torch.uint8, src.shape[-1])
     if out is None:
-      out = getattr(self, "_act_out", None)
-      if out is None:
-        out = self._act_out = torch.zeros((self.n_envs, self.spec.A), dtype=torch.int8, device=self.device)
-    elif out.dtype != torch.int8 or out.device != self.device or not out.is_contiguous() or out.numel() != self.n_envs * self.spec.A:
-      raise N.SgwError("act: out must be a contiguous int8 [N, A] tensor on %s" % (self.device,))
+      if self._act_out is None:
+        self._act_out = torch.zeros((self.n_envs, self.spec.A), dtype=torch.int8, device=self.device)
+      out = self._act_out
+    else:
+      _require("act", "out", out, self.device, torch.int8, self.n_envs * self.spec.A, "[N, A]")
     N.check(self._lib.sgw_policy_act(self._h, C.byref(policy.native()), obs.data_ptr(), int(t), out.data_ptr(), self._stream()),
             "sgw_policy_act")
     return out.reshape(self.n_envs, self.spec.A)
@@ -911,17 +935,12 @@ class BatchedEngine(object):
     if policy.source == "views" and not fused_views(self.spec):
       raise N.SgwError("policy_step_n: this spec's windows do not come from the step launch (fused_views is false): "
                        "the closed loop over windows is not available for it")
-    obs0 = self._policy_source(policy, "policy_step_n")
-    want_T = T if write_every else 1
-    if self._T != want_T:                   # the new buffers start from the observation the envs are at
-      keep = obs0.clone()
-      self._alloc_outputs(want_T)
-      obs0 = self._policy_source(policy, "policy_step_n")
+    obs0, held = self._policy_source(policy, "policy_step_n"), self._T
+    self._want_T(T, write_every)
+    if self._T != held:                     # the new buffers start from the observation the envs are at
+      keep, obs0 = obs0, self._policy_source(policy, "policy_step_n")
       obs0.copy_(keep)
-    tapes = self.__dict__.setdefault("_policy_tapes", {})
-    acts = tapes.get(T)
-    if acts is None:
-      acts = tapes[T] = torch.zeros((T, self.n_envs, self.spec.A), dtype=torch.int8, device=self.device)
+    acts = self._persistent("tape", T, lambda: torch.zeros((T, self.n_envs, self.spec.A), dtype=torch.int8, device=self.device))
     if keep_obs0:
       side = self._obs0_side(policy)
       side.copy_(obs0)
@@ -937,37 +956,22 @@ class BatchedEngine(object):
   # -- learning a table policy (csrc/sgw_learn.hpp) ---------------------------------------------
   def _obs0_side(self, policy):
     """The persistent [N_pad, row] copy of the observation a policy_rollout call started from, per source."""
-    sides = self.__dict__.setdefault("_obs0_sides", {})
-    side = sides.get(policy.source)
-    if side is None:
-      src = self._policy_source(policy, "policy_step_n")
-      side = sides[policy.source] = torch.zeros_like(src)
-    return side
+    return self._persistent("obs0", policy.source, lambda: torch.zeros_like(self._policy_source(policy, "policy_step_n")))
 
   def _learn_observations(self, policy, T, obs0, obs, actions, what, need_actions):
     """(obs0 pointer, obs pointer or None, obs_rows, actions tensor or None) of the T + 1 observations O[0..T] a learning call
     reads: the caller's tensors, or what the last policy_rollout(policy, T) left in the engine."""
     src = self._policy_source(policy, what)
     row, n, n_pad = src.shape[-1], self.n_envs, self.n_pad
-
-    def rows_of(t, lead, name):
-      ok = torch.is_tensor(t) and t.device == self.device and t.dtype == torch.uint8 and t.is_contiguous()
-      if ok and t.numel() == lead * n * row:
-        return n
-      if ok and t.numel() == lead * n_pad * row:
-        return n_pad
-      raise N.SgwError("%s: %s must be a contiguous uint8 [%s%d or %d, %d] tensor on %s (there is no CPU path)"
-                       % (what, name, "%d, " % lead if lead > 1 else "", n, n_pad, row, self.device))
-
     if obs0 is None:
       if T == 0:
         obs0 = src
       else:
-        obs0 = self.__dict__.get("_obs0_sides", {}).get(policy.source)
+        obs0 = self._persistent("obs0", policy.source)
         if obs0 is None:
           raise N.SgwError("%s: no obs0: pass it, or run policy_rollout(policy, T) first" % what)
     else:
-      rows_of(obs0, 1, "obs0")
+      self._rows_of(what, "obs0", obs0, torch.uint8, row)
     obs_ptr, obs_rows = None, n
     if T > 0:
       if obs is None:
@@ -976,16 +980,14 @@ class BatchedEngine(object):
                            % (what, T, policy.source, T, self._T))
         obs_ptr, obs_rows = self._bufs[policy.source].data_ptr(), n_pad
       else:
-        obs_rows = rows_of(obs, T, "obs")
+        obs_rows = self._rows_of(what, "obs", obs, torch.uint8, row, T)
         obs_ptr = obs.data_ptr()
     if actions is None and need_actions:
-      actions = self.__dict__.get("_policy_tapes", {}).get(T)
+      actions = self._persistent("tape", T)
       if actions is None and need_actions == "required":
         raise N.SgwError("%s: no actions: pass the int8 [T, N, A] tape, or run policy_rollout(policy, T) first" % what)
-    if actions is not None and not (torch.is_tensor(actions) and actions.device == self.device and actions.dtype == torch.int8
-                                    and actions.is_contiguous() and actions.numel() == T * n * self.spec.A):
-      raise N.SgwError("%s: actions must be a contiguous int8 [%d, %d, %d] tensor on %s (there is no CPU path)"
-                       % (what, T, n, self.spec.A, self.device))
+    if actions is not None:
+      _require(what, "actions", actions, self.device, torch.int8, T * n * self.spec.A, "[%d, %d, %d]" % (T, n, self.spec.A))
     return obs0.data_ptr(), obs_ptr, obs_rows, actions
 
   def policy_scores(self, policy, T=0, obs0=None, obs=None, actions=None):
@@ -998,17 +1000,12 @@ class BatchedEngine(object):
     T = int(T)
     if T < 0:
       raise ValueError("policy_scores: T must be >= 0")
-    if self._h is None:
-      raise N.SgwError("policy_scores: the engine has no device engine behind it (closed?); there is no CPU path")
+    self._open("policy_scores")
     p0, p1, rows, actions = self._learn_observations(policy, T, obs0, obs, actions, "policy_scores", "optional" if T > 0 else None)
     n, A = self.n_envs, self.spec.A
-    cache = self.__dict__.setdefault("_score_bufs", {})
-    c = cache.get((T, policy.n_actions))
-    if c is None:
-      c = cache[(T, policy.n_actions)] = (torch.zeros((T + 1, n, A, policy.n_actions), dtype=torch.float32, device=self.device),
-                                          torch.zeros((T + 1, n, A), dtype=torch.float64, device=self.device),
-                                          torch.zeros((T, n, A), dtype=torch.float64, device=self.device))
-    scores, vmax, chosen = c
+    scores, vmax, chosen = self._persistent("scores", (T, policy.n_actions), lambda: (
+        torch.zeros((T + 1, n, A, policy.n_actions), dtype=torch.float32, device=self.device),
+        torch.zeros((T + 1, n, A), dtype=torch.float64, device=self.device), torch.zeros((T, n, A), dtype=torch.float64, device=self.device)))
     want_chosen = actions is not None and T > 0
     N.check(self._lib.sgw_policy_scores(self._h, C.byref(policy.native()), p0, p1, rows, T, actions.data_ptr() if want_chosen else None,
                                         scores.data_ptr(), vmax.data_ptr(), chosen.data_ptr() if want_chosen else None, self._stream()),
@@ -1027,17 +1024,13 @@ class BatchedEngine(object):
     T = int(T)
     if T < 1:
       raise ValueError("policy_accumulate: T must be >= 1")
-    if self._h is None:
-      raise N.SgwError("policy_accumulate: the engine has no device engine behind it (closed?); there is no CPU path")
+    self._open("policy_accumulate")
     frac_bits = int(frac_bits)
     if policy.acc_frac_bits is not None and policy.acc_frac_bits != frac_bits:
       raise N.SgwError("policy_accumulate: the accumulators hold sums with frac_bits=%d; apply them (clear=True) before frac_bits=%d"
                        % (policy.acc_frac_bits, frac_bits))
     n, A = self.n_envs, self.spec.A
-    if not (torch.is_tensor(coef) and coef.device == self.device and coef.dtype == torch.float64 and coef.is_contiguous()
-            and coef.numel() == T * n * A):
-      raise N.SgwError("policy_accumulate: coef must be a contiguous float64 [%d, %d, %d] tensor on %s (there is no CPU path)"
-                       % (T, n, A, self.device))
+    _require("policy_accumulate", "coef", coef, self.device, torch.float64, T * n * A, "[%d, %d, %d]" % (T, n, A))
     p0, p1, rows, actions = self._learn_observations(policy, T, obs0, obs, actions, "policy_accumulate", "required")
     N.check(self._lib.sgw_policy_accumulate(self._h, C.byref(policy.native()), p0, p1, rows, T, actions.data_ptr(), coef.data_ptr(), frac_bits,
                                             policy.acc_weights.data_ptr(), policy.acc_bias.data_ptr(), self._stream()),
@@ -1048,8 +1041,7 @@ class BatchedEngine(object):
     """weights += lr * acc_weights * 2^-frac_bits (and the bias alike), in place, from ONE launch (sgw_policy_apply): per element
     w = float32(float64(w) + lr * (float64(acc) * 2^-frac_bits)); an element whose sum is 0 is not written.  frac_bits is the one
     the sums were accumulated with.  clear=True zeroes the accumulators behind the update."""
-    if self._h is None:
-      raise N.SgwError("policy_apply: the engine has no device engine behind it (closed?); there is no CPU path")
+    self._open("policy_apply")
     self._policy_source(policy, "policy_apply")
     frac_bits = 24 if policy.acc_frac_bits is None else policy.acc_frac_bits
     N.check(self._lib.sgw_policy_apply(self._h, C.byref(policy.native()), float(lr), frac_bits, policy.acc_weights.data_ptr(),
@@ -1083,23 +1075,6 @@ class BatchedEngine(object):
     return traj
 
   # -- what each action would do (csrc/sgw_whatif.hpp) ----------------------------------------
-  def _whatif_input(self, name, t, what):
-    """The [N or N_pad, row] rows of output `name` that a what-if call reads: the caller's tensor, or the engine's latest."""
-    if t is None:
-      if name not in self._bufs:
-        if name == "agent_flags":
-          return None                       # (optional: without it every action direction reads UP)
-        raise N.SgwError("%s: the %r output is not among this engine's outputs (%r); pass it or ask for it" % (what, name, self.outputs))
-      t = self._bufs[name]
-      return t[-1] if self._T > 1 else t
-    dt, shp = _dtype_shape(self.spec, name)
-    row = int(np.prod(shp, dtype=np.int64))
-    if (not torch.is_tensor(t) or t.device != self.device or t.dtype != dt or not t.is_contiguous()
-        or t.numel() not in (self.n_envs * row, self.n_pad * row)):
-      raise N.SgwError("%s: %s must be a contiguous %s [%d or %d, ...] tensor of %d values per env on %s (there is no CPU path)"
-                       % (what, name, dt, self.n_envs, self.n_pad, row, self.device))
-    return t
-
   def simulate_moves(self, board=None, agent_pos=None, agent_flags=None):
     """Where every action of the action set would take every agent, without playing it (sgw_simulate_moves: one launch, no
     synchronisation, capturable): dict of uint8 tensors "target_pos" [N, A, n_actions, 2], "target_tile" [N, A, n_actions] and
@@ -1110,12 +1085,11 @@ class BatchedEngine(object):
     board and agent_pos must be among the outputs or be passed.  The result tensors are persistent and rewritten by the next
     call.  Covered: island_navigation_ex, boat_race_ex, conveyor_belt_ex, island_navigation_ex_ma, aintelope_savanna,
     firemaker_ex_ma with noops=True; anything else raises (there is no CPU path)."""
-    if self._h is None:
-      raise N.SgwError("simulate_moves: the engine has no device engine behind it (closed?); there is no CPU path")
-    b = self._whatif_input("board", board, "simulate_moves")
-    p = self._whatif_input("agent_pos", agent_pos, "simulate_moves")
-    f = self._whatif_input("agent_flags", agent_flags, "simulate_moves")
-    res = getattr(self, "_whatif_out", None)
+    self._open("simulate_moves")
+    b = self._latest("board", board, "simulate_moves")
+    p = self._latest("agent_pos", agent_pos, "simulate_moves")
+    f = self._latest("agent_flags", agent_flags, "simulate_moves", optional=True)      # (without it every action direction reads UP)
+    res = self._whatif_out
     if res is None:
       lead = (self.n_envs, self.spec.A, self.spec.n_actions)
       res = self._whatif_out = {"target_pos": torch.zeros(lead + (2,), dtype=torch.uint8, device=self.device),
@@ -1142,11 +1116,9 @@ class BatchedEngine(object):
     `q_value_per_tiletype` float64 [N, A, L, D] (also an attribute, with `q_value_seen` uint8 [N, A, L] and
     `q_value_tile_chars`): rows of tile types no action reached this time keep their values, across steps, episodes and resets;
     a new tile_chars or D starts a new zeroed table.  tile_chars defaults to default_tile_chars()."""
-    if self._h is None:
-      raise N.SgwError("fold_q_values: the engine has no device engine behind it (closed?); there is no CPU path")
+    self._open("fold_q_values")
     A, NA = self.spec.A, self.spec.n_actions
-    if not torch.is_tensor(q) or q.device != self.device or q.dtype not in (torch.float64, torch.float32):
-      raise N.SgwError("fold_q_values: q must be a float64 (or float32) tensor on %s (there is no CPU path)" % (self.device,))
+    _require("fold_q_values", "q", q, self.device, (torch.float64, torch.float32), None, contiguous=False)
     shapes = [(self.n_envs, A, NA)] + ([(self.n_envs, NA)] if A == 1 else [])
     if q.dim() < 3 or tuple(q.shape[:-1]) not in shapes or q.shape[-1] < 1:
       raise N.SgwError("fold_q_values: q must be [N, A, n_actions, D] = [%d, %d, %d, D]" % (self.n_envs, A, NA))
@@ -1156,56 +1128,55 @@ class BatchedEngine(object):
     if not 1 <= len(chars) <= 64:
       raise N.SgwError("fold_q_values: 1..64 tile characters")
     key = (tuple(chars), D)
-    if getattr(self, "_fold_key", None) != key:
+    if self._fold_key != key:
       self._fold_key = key
       self.q_value_tile_chars = chars
       self._fold_chars = torch.tensor([ord(c) if isinstance(c, str) else int(c) for c in chars], dtype=torch.uint8, device=self.device)
       self.q_value_per_tiletype = torch.zeros((self.n_envs, A, len(chars), D), dtype=torch.float64, device=self.device)
       self.q_value_seen = torch.zeros((self.n_envs, A, len(chars)), dtype=torch.uint8, device=self.device)
     if target_tile is None:
-      if getattr(self, "_whatif_out", None) is None:
+      if self._whatif_out is None:
         raise N.SgwError("fold_q_values: call simulate_moves first (or pass target_tile)")
       target_tile = self._whatif_out["target_tile"]
-    elif (not torch.is_tensor(target_tile) or target_tile.device != self.device or target_tile.dtype != torch.uint8
-          or not target_tile.is_contiguous() or target_tile.numel() != self.n_envs * A * NA):
-      raise N.SgwError("fold_q_values: target_tile must be a contiguous uint8 [N, A, n_actions] tensor on %s" % (self.device,))
+    else:
+      _require("fold_q_values", "target_tile", target_tile, self.device, torch.uint8, self.n_envs * A * NA, "[N, A, n_actions]")
     N.check(self._lib.sgw_fold_q_values(self._h, target_tile.data_ptr(), q.data_ptr(), D, self._fold_chars.data_ptr(), len(chars),
                                         self.q_value_per_tiletype.data_ptr(), self.q_value_seen.data_ptr(), self._stream()),
             "sgw_fold_q_values")
     return self.q_value_per_tiletype
 
+  def _layer_tables(self):
+    """(the characters of spec.layer_chars as uint8 [L] on the device, the static-layer table on the device (None where the layers
+    come from the engine state), gap_index, hidden_layer): what every producer of observation layers hands the library; built once."""
+    if self._layers is None:
+      sp = self.spec
+      chars = torch.tensor([ord(c) for c in sp.layer_chars], dtype=torch.uint8, device=self.device)
+      stat = None if getattr(sp, "layers_from_state", False) else torch.from_numpy(sp.layer_static()).to(self.device)
+      gap = sp.layer_chars.index(sp.what_lies_beneath) if sp.what_lies_beneath in sp.layer_chars else -1
+      hidden = getattr(sp, "hidden_layer_char", None)
+      self._layers = (chars, stat, gap, sp.layer_chars.index(hidden) if hidden is not None else -1)
+    return self._layers
+
   def observe_layers(self, board=None, agent_pos=None, agent_flags=None):
     """Unoccluded per-character layers with the gap correction: uint8 [N, L, H, W], L = len(spec.layer_chars)
     (what the MO/MA envs put in observation['layers']: rendering.py:188-302, observation_distiller_ex.py:164-178)."""
     sp = self.spec
-    if getattr(sp, "layers_from_state", False):   # aintelope_savanna: drapes overlap, the board shows only the top one
-      if board is not None:
-        raise N.SgwError("observe_layers: this family's layers come from the engine state (current step), not from a board")
-      chars = torch.tensor([ord(c) for c in sp.layer_chars], dtype=torch.uint8, device=self.device)
-      out = torch.empty((self.n_envs, len(sp.layer_chars), sp.H, sp.W), dtype=torch.uint8, device=self.device)
-      N.check(self._lib.sgw_state_layers(self._h, chars.data_ptr(), len(sp.layer_chars), 1, out.data_ptr(), self._stream()),
-              "sgw_state_layers")
-      return out
-    if board is None:
-      board = self._bufs["board"][:self.n_envs]
-    board = board.reshape(-1, sp.H * sp.W).contiguous()
-    if not hasattr(self, "_layer_tables"):
-      chars = torch.tensor([ord(c) for c in sp.layer_chars], dtype=torch.uint8, device=self.device)
-      stat = torch.from_numpy(sp.layer_static()).to(self.device)
-      self._layer_tables = (chars, stat)
-    chars, stat = self._layer_tables
+    chars, stat, gap, hidx = self._layer_tables()
     L = len(sp.layer_chars)
     out = torch.empty((self.n_envs, L, sp.H, sp.W), dtype=torch.uint8, device=self.device)
-    gap = sp.layer_chars.index(sp.what_lies_beneath) if sp.what_lies_beneath in sp.layer_chars else -1
-    hidden = getattr(sp, "hidden_layer_char", None)
+    if stat is None:                              # aintelope_savanna: drapes overlap, the board shows only the top one
+      if board is not None:
+        raise N.SgwError("observe_layers: this family's layers come from the engine state (current step), not from a board")
+      N.check(self._lib.sgw_state_layers(self._h, chars.data_ptr(), L, 1, out.data_ptr(), self._stream()), "sgw_state_layers")
+      return out
+    board = self._latest("board", None, "observe_layers") if board is None else board.reshape(-1, sp.H * sp.W).contiguous()
     pp = fp = None
-    hidx = -1
-    if hidden is not None:                       # a dynamic drape that can lie under a sprite (firemaker fire)
-      if agent_pos is None and "agent_pos" in self._bufs and "agent_flags" in self._bufs:
-        agent_pos, agent_flags = self._bufs["agent_pos"], self._bufs["agent_flags"]
+    if hidx >= 0:                                 # a dynamic drape that can lie under a sprite (firemaker fire)
+      if agent_pos is None:
+        agent_pos, agent_flags = (self._latest(k, None, "observe_layers", optional=True) for k in ("agent_pos", "agent_flags"))
       if agent_pos is None or agent_flags is None:
         raise N.SgwError("observe_layers: this family needs the 'agent_pos' and 'agent_flags' outputs")
-      pp, fp, hidx = agent_pos.data_ptr(), agent_flags.data_ptr(), sp.layer_chars.index(hidden)
+      pp, fp = agent_pos.data_ptr(), agent_flags.data_ptr()
     N.check(self._lib.sgw_observe_layers(self._h, board.data_ptr(), chars.data_ptr(), stat.data_ptr(), L, gap,
                                          pp, fp, hidx, out.data_ptr(), self._stream()), "sgw_observe_layers")
     return out
@@ -1279,8 +1250,7 @@ class BatchedEngine(object):
     return new
 
   def _drop_lookahead(self):
-    look = getattr(self, "_look", None)
-    self._look = None
+    look, self._look = self._look, None
     if look is not None:
       look["engine"].close()
 
@@ -1326,9 +1296,8 @@ class BatchedEngine(object):
     N.check(self._lib.sgw_set_state(self._h, st.data_ptr(), self._stream()), "sgw_set_state")
 
   def close(self):
-    if getattr(self, "_look", None) is not None:
-      self._drop_lookahead()
-    if getattr(self, "_h", None):
+    self._drop_lookahead()
+    if self._h:
       self._lib.sgw_destroy(self._h)
       self._h = None
 
@@ -1350,6 +1319,7 @@ class EngineGroup(object):
   """
 
   def __init__(self, engines):
+    self._h = None
     self.engines = list(engines)
     if not self.engines:
       raise ValueError("EngineGroup needs at least one engine")
@@ -1360,12 +1330,10 @@ class EngineGroup(object):
     N.check(self._lib.sgw_group_create(hs, len(self.engines), C.byref(h)), "sgw_group_create")
     self._h = h
 
-  def _outs(self, want_T_of):
+  def _outs(self, T, write_every):
     outs = (N.Out * len(self.engines))()
     for i, e in enumerate(self.engines):
-      want_T = want_T_of(e)
-      if e._T != want_T:
-        e._alloc_outputs(want_T)
+      e._want_T(T, write_every)
       for name in N.OUT_FIELDS:
         setattr(outs[i], name, getattr(e._out, name))
     return outs
@@ -1376,20 +1344,20 @@ class EngineGroup(object):
     for e, a in zip(self.engines, actions):
       assert a.dtype == torch.int8 and a.is_contiguous() and a.device == e.device and int(a.shape[0]) == T
       assert a.numel() == T * e.n_envs * e.spec.A
-    outs = self._outs(lambda e: T if write_every else 1)
+    outs = self._outs(T, write_every)
     ptrs = (C.c_void_p * len(self.engines))(*[a.data_ptr() for a in actions])
     N.check(self._lib.sgw_group_step_n(self._h, ptrs, T, 1 if write_every else 0, outs, 1 if accumulate else 0,
                                        self.engines[0]._stream()), "sgw_group_step_n")
     return [e._views() for e in self.engines]
 
   def rollout(self, T, seed, step0=0, write_every=False, accumulate=False):
-    outs = self._outs(lambda e: T if write_every else 1)
+    outs = self._outs(T, write_every)
     N.check(self._lib.sgw_group_rollout(self._h, int(T), int(seed), int(step0), 1 if write_every else 0, outs,
                                         1 if accumulate else 0, self.engines[0]._stream()), "sgw_group_rollout")
     return [e._views() for e in self.engines]
 
   def close(self):
-    if getattr(self, "_h", None):
+    if self._h:
       self._lib.sgw_group_destroy(self._h)
       self._h = None
 

@@ -123,8 +123,7 @@ class GridworldZooVectorEnv(object):
       if self._fused:                                              # the step launch wrote the windows (ascii or value-mapped)
         views = eng.split_views(o["views" if self._ascii else "obs_views"])
       else:
-        vb = int(eng._lib.sgw_view_bytes(eng._h))
-        self._view_buf = torch.empty((n, vb), dtype=torch.uint8, device=self.device)
+        self._view_buf = torch.empty((n, eng.view_bytes), dtype=torch.uint8, device=self.device)
         views = eng.agent_views(out=self._view_buf)
       st, tr = o["step_type"].reshape(n, -1), o["term_reason"].reshape(n, -1)
       self._done = o["done"].reshape(n, -1).view(torch.bool)

@@ -9,7 +9,7 @@ wraps every output buffer in guard bytes so that a store that leaves its buffer 
 import numpy as np
 
 from ai_safety_gridworlds_amd import _native as N
-from ai_safety_gridworlds_amd.engine import DEFAULT_OUTPUTS, BatchedEngine, _dtype_shape
+from ai_safety_gridworlds_amd.engine import DEFAULT_OUTPUTS, BatchedEngine
 
 BENCH_OUTPUTS = ("board", "reward", "step_type", "term_reason", "safety", "frame")    # bench.py's headline output set
 WINDOW_EXTRAS = ("obs_views", "obs_dir", "act_dir")
@@ -120,22 +120,20 @@ class GuardedEngine(BatchedEngine):
   from N up to N_pad belong to the buffer and are scratch by contract: they are not checked."""
 
   def _alloc_outputs(self, T):
-    import torch
-    self._broken = getattr(self, "_broken", set()) | set(self._broken_now())
-    self._T = T
-    self._views_cache = None
+    self._broken = getattr(self, "_broken", set()) | set(self._broken_now())       # the buffers about to be replaced: a last look
     self._raw = {}
-    for name in self.outputs:
-      dt, shp = _dtype_shape(self.spec, name)
-      lead = (T, self.n_pad) if T > 1 else (self.n_pad,)
-      nbytes = int(np.prod(lead + shp, dtype=np.int64)) * torch.empty((), dtype=dt).element_size()
-      raw = torch.full((GUARD + nbytes + GUARD,), FILL, dtype=torch.uint8, device=self.device)
-      raw[GUARD:GUARD + nbytes].zero_()
-      self._raw[name] = (raw, nbytes)
-      self._bufs[name] = raw[GUARD:GUARD + nbytes].view(dt).reshape(lead + shp)
-      assert self._bufs[name].data_ptr() == raw.data_ptr() + GUARD and self._bufs[name].data_ptr() % 16 == 0
-    for name in N.OUT_FIELDS:
-      setattr(self._out, name, self._bufs[name].data_ptr() if name in self._bufs else None)
+    BatchedEngine._alloc_outputs(self, T)
+
+  def _new_output(self, name, dtype, shape):
+    """The dtype and shape BatchedEngine asks for, as the zeroed middle of a guarded allocation."""
+    import torch
+    nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
+    raw = torch.full((GUARD + nbytes + GUARD,), FILL, dtype=torch.uint8, device=self.device)
+    raw[GUARD:GUARD + nbytes].zero_()
+    self._raw[name] = (raw, nbytes)
+    buf = raw[GUARD:GUARD + nbytes].view(dtype).reshape(shape)
+    assert buf.data_ptr() == raw.data_ptr() + GUARD and buf.data_ptr() % 16 == 0
+    return buf
 
   def _broken_now(self):
     import torch

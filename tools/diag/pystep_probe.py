@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, "/root/repo")
+import sys, time, os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from ai_safety_gridworlds_amd.engine import BatchedEngine
 from ai_safety_gridworlds_amd.specs import make_spec
