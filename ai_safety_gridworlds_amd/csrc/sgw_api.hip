@@ -1004,11 +1004,12 @@ int sgw_replay(sgw_engine* e, const int8_t* actions_dev, int T, int write_every,
   return rc ? rc : launch(e, a, (hipStream_t)stream);
 }
 
+constexpr int FILL_ACTIONS_MAX_BLOCKS = 4096;      // k_fill_actions strides over the rest
 int sgw_fill_actions(sgw_engine* e, int T, uint64_t seed, int64_t step0, int8_t* actions_dev, void* stream) {
   if (!e || !actions_dev || T < 1) return fail(SGW_ERR_ARG, "sgw_fill_actions: bad argument");
   HIP_TRY(hipSetDevice(e->device));
   long long total = (long long)T * e->n_envs * e->spec.A;
-  int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  int blocks = (int)((total + 255) / 256 < FILL_ACTIONS_MAX_BLOCKS ? (total + 255) / 256 : FILL_ACTIONS_MAX_BLOCKS);
   hipLaunchKernelGGL(k_fill_actions, dim3(blocks), dim3(256), 0, (hipStream_t)stream, actions_dev, e->n_envs,
                      e->spec.A, T, seed, step0, e->env_id_base, e->spec.action_lo, e->spec.n_actions);
   HIP_TRY(hipGetLastError());
@@ -1181,6 +1182,12 @@ static int check_rotation(const sgw_engine* e, const ViewSpec& v, const uint8_t*
   return SGW_OK;
 }
 
+// grid caps of the window launches: every kernel below walks what is left in a stride loop (tests/grid_caps.py has a row for each)
+constexpr int AGENT_VIEWS_SMALL_MAX_BLOCKS = 65536, AGENT_LAYER_VIEWS_SMALL_MAX_BLOCKS = 65536;      // one thread per output byte
+constexpr int AGENT_VIEWS_LDS_MAX_BLOCKS = 8192, AGENT_VIEWS_LDS_GROUP_ENVS = 4;                     // one-wave workgroups, GROUP_ENVS envs per pass
+constexpr int AGENT_LAYER_VIEWS_LDS_MAX_BLOCKS = 4096;                                               // a workgroup per env
+constexpr int AGENT_VIEWS_WAVE_MAX_BLOCKS = 65536, AGENT_LAYER_VIEWS_WAVE_MAX_BLOCKS = 65536;        // four waves, a wave per window
+
 int sgw_agent_views(sgw_engine* e, const uint8_t* board_dev, const uint8_t* agent_pos_dev, const uint8_t* agent_flags_dev,
                     uint8_t outside_chr, uint8_t* views_dev, void* stream) {
   if (!e || !board_dev || !agent_pos_dev || !views_dev) return fail(SGW_ERR_ARG, "sgw_agent_views: null argument");
@@ -1190,7 +1197,7 @@ int sgw_agent_views(sgw_engine* e, const uint8_t* board_dev, const uint8_t* agen
   HIP_TRY(hipSetDevice(e->device));
   if (views_all_small(v)) {                                              // every window <= 64 cells: one thread per byte
     long long total = e->n_envs * (long long)v.total;
-    int blocks = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+    int blocks = (int)((total + 255) / 256 < AGENT_VIEWS_SMALL_MAX_BLOCKS ? (total + 255) / 256 : AGENT_VIEWS_SMALL_MAX_BLOCKS);
     hipLaunchKernelGGL(k_agent_views_small, dim3(blocks), dim3(256), 0, (hipStream_t)stream, board_dev, agent_pos_dev,
                        agent_flags_dev, e->n_envs, v, outside_chr, views_dev);
     HIP_TRY(hipGetLastError());
@@ -1200,11 +1207,11 @@ int sgw_agent_views(sgw_engine* e, const uint8_t* board_dev, const uint8_t* agen
     // one wave per env: the board and the env's row of windows in LDS, the row out as dword stores at its byte address (the layer-cube
     // kernel with one plane; round 2's k_agent_views -- a wave per window, cells loaded from global memory -- took 26 us for 16 384 envs)
     const int lay_bytes = (e->ks.HW + 15) / 16 * 16, img_bytes = (v.total + 15) / 16 * 16 + 16;      // (+ 16: the image sits at its row's 16-byte phase)
-    constexpr int G = 4;      // envs a one-wave workgroup takes per pass (k_agent_layer_views_lds; 16 384 envs: G = 2 18.9, G = 4 17.8, G = 8 24.8 us)
+    constexpr int G = AGENT_VIEWS_LDS_GROUP_ENVS;      // envs a one-wave workgroup takes per pass (k_agent_layer_views_lds; 16 384 envs: G = 2 18.9, G = 4 17.8, G = 8 24.8 us)
     const size_t lds = 128 + 16 * G + (size_t)G * ((size_t)lay_bytes + (size_t)img_bytes);       // table | per-env words | G x (planes | image)
     if (lds <= 64 * 1024) {
       const long long groups = (e->n_envs + G - 1) / G;
-      const int blocks = (int)(groups < 8192 ? groups : 8192);           // (each walks its groups; 4 096..16 384 workgroups measured the same, fewer are slower)
+      const int blocks = (int)(groups < AGENT_VIEWS_LDS_MAX_BLOCKS ? groups : AGENT_VIEWS_LDS_MAX_BLOCKS);           // (each walks its groups; 4 096..16 384 workgroups measured the same, fewer are slower)
       hipLaunchKernelGGL(k_agent_layer_views_lds<G>, dim3(blocks), dim3(WAVE), lds, (hipStream_t)stream, board_dev, agent_pos_dev, agent_flags_dev,
                          (long long)e->n_envs, v, (const uint8_t*)nullptr, 1, outside_chr, views_dev, lay_bytes, img_bytes, 1);
       HIP_TRY(hipGetLastError());
@@ -1212,7 +1219,7 @@ int sgw_agent_views(sgw_engine* e, const uint8_t* board_dev, const uint8_t* agen
     }
   }
   long long total = e->n_envs * (long long)v.A * WAVE;                   // one wave per (env, agent) window
-  int blocks = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+  int blocks = (int)((total + 255) / 256 < AGENT_VIEWS_WAVE_MAX_BLOCKS ? (total + 255) / 256 : AGENT_VIEWS_WAVE_MAX_BLOCKS);
   const int lds_per_wave = view_stage_bytes(v);
   hipLaunchKernelGGL(k_agent_views, dim3(blocks), dim3(256), 4 * lds_per_wave, (hipStream_t)stream, board_dev, agent_pos_dev,
                      agent_flags_dev, e->n_envs, v, outside_chr, views_dev, lds_per_wave);
@@ -1230,7 +1237,7 @@ int sgw_agent_layer_views(sgw_engine* e, const uint8_t* layers_dev, const uint8_
   HIP_TRY(hipSetDevice(e->device));
   if (views_all_small(v)) {
     long long total = e->n_envs * (long long)v.total * n_layers;
-    int blocks = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+    int blocks = (int)((total + 255) / 256 < AGENT_LAYER_VIEWS_SMALL_MAX_BLOCKS ? (total + 255) / 256 : AGENT_LAYER_VIEWS_SMALL_MAX_BLOCKS);
     hipLaunchKernelGGL(k_agent_layer_views_small, dim3(blocks), dim3(256), 0, (hipStream_t)stream, layers_dev, agent_pos_dev,
                        agent_flags_dev, e->n_envs, v, layer_chars_dev, n_layers, outside_chr, out_dev);
     HIP_TRY(hipGetLastError());
@@ -1240,14 +1247,14 @@ int sgw_agent_layer_views(sgw_engine* e, const uint8_t* layers_dev, const uint8_
   const int lay_bytes = (n_layers * e->ks.HW + 15) / 16 * 16, img_bytes = (v.total * n_layers + 15) / 16 * 16 + 16;
   const size_t lds = 128 + 16 + (size_t)lay_bytes + (size_t)img_bytes;
   if (lds <= 64 * 1024) {
-    const int blocks = (int)(e->n_envs < 4096 ? e->n_envs : 4096);
+    const int blocks = (int)(e->n_envs < AGENT_LAYER_VIEWS_LDS_MAX_BLOCKS ? e->n_envs : AGENT_LAYER_VIEWS_LDS_MAX_BLOCKS);
     hipLaunchKernelGGL(k_agent_layer_views_lds<1>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, layers_dev, agent_pos_dev, agent_flags_dev,
                        (long long)e->n_envs, v, layer_chars_dev, n_layers, outside_chr, out_dev, lay_bytes, img_bytes, 0);
     HIP_TRY(hipGetLastError());
     return SGW_OK;
   }
   long long total = e->n_envs * (long long)v.A * n_layers * WAVE;        // (rows too large for LDS) one wave per (env, agent, layer) window
-  int blocks = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+  int blocks = (int)((total + 255) / 256 < AGENT_LAYER_VIEWS_WAVE_MAX_BLOCKS ? (total + 255) / 256 : AGENT_LAYER_VIEWS_WAVE_MAX_BLOCKS);
   const int lds_per_wave = view_stage_bytes(v);
   hipLaunchKernelGGL(k_agent_layer_views, dim3(blocks), dim3(256), 4 * lds_per_wave, (hipStream_t)stream, layers_dev, agent_pos_dev,
                      agent_flags_dev, e->n_envs, v, layer_chars_dev, n_layers, outside_chr, out_dev, lds_per_wave);
@@ -1257,6 +1264,7 @@ int sgw_agent_layer_views(sgw_engine* e, const uint8_t* layers_dev, const uint8_
 
 // sgw_layer_coords / sgw_agent_layer_coords: the lane split and the reciprocals of k_plane_coords (sgw_coords.hpp) for planes of at most
 // max_cells cells, and the launch.  Plain launches on the caller's stream: nothing is allocated, nothing of the engine changes.
+constexpr int PLANE_COORDS_MAX_BLOCKS = 8192;      // 4 waves per workgroup; each wave walks its planes
 static int coords_launch(sgw_engine* e, bool rel, const uint8_t* planes, long long items, CoordGeom& g, int max_cells, int32_t* counts,
                          int16_t* coords, void* stream, const char* who) {
   if (((uintptr_t)counts | (uintptr_t)coords) & 3) return fail(SGW_ERR_ARG, "%s: counts and coords must be 4-byte aligned (a coordinate pair is one store)", who);
@@ -1273,7 +1281,7 @@ static int coords_launch(sgw_engine* e, bool rel, const uint8_t* planes, long lo
   if (items <= 0 || max_cells <= 0) return SGW_OK;
   HIP_TRY(hipSetDevice(e->device));
   const long long per_wave = WAVE >> g.seg_shift, waves = (items + per_wave - 1) / per_wave;
-  const unsigned blocks = (unsigned)((waves + 3) / 4 < 8192 ? (waves + 3) / 4 : 8192);      // 4 waves per workgroup; each wave walks its planes
+  const unsigned blocks = (unsigned)((waves + 3) / 4 < PLANE_COORDS_MAX_BLOCKS ? (waves + 3) / 4 : PLANE_COORDS_MAX_BLOCKS);
   if (rel) hipLaunchKernelGGL(k_plane_coords<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, planes, (unsigned)items, g, counts, coords);
   else hipLaunchKernelGGL(k_plane_coords<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, planes, (unsigned)items, g, counts, coords);
   HIP_TRY(hipGetLastError());
@@ -1898,6 +1906,7 @@ int sgw_policy_accumulate(sgw_engine* e, const sgw_policy* p, const uint8_t* obs
   return SGW_OK;
 }
 
+constexpr int POLICY_APPLY_MAX_BLOCKS = 4096;      // k_policy_apply strides over the rest
 int sgw_policy_apply(sgw_engine* e, const sgw_policy* p, double lr, int frac_bits, int64_t* acc_weights_dev, int64_t* acc_bias_dev,
                      int flags, void* stream) {
   if (!e) return fail(SGW_ERR_ARG, "sgw_policy_apply: null engine");
@@ -1918,7 +1927,7 @@ int sgw_policy_apply(sgw_engine* e, const sgw_policy* p, double lr, int frac_bit
   a.n_b = (p->bias && acc_bias_dev) ? slices * L.a.n_actions : 0;
   a.lr = lr; a.inv_scale = ldexp(1.0, -frac_bits); a.clear = (flags & SGW_APPLY_CLEAR) ? 1 : 0;
   long long blocks = (a.n_w + a.n_b + LEARN_THREADS - 1) / LEARN_THREADS;
-  if (blocks > 4096) blocks = 4096;                                         // the kernel strides
+  if (blocks > POLICY_APPLY_MAX_BLOCKS) blocks = POLICY_APPLY_MAX_BLOCKS;
   HIP_TRY(hipSetDevice(e->device));
   hipLaunchKernelGGL(k_policy_apply, dim3((unsigned)blocks), dim3(LEARN_THREADS), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());

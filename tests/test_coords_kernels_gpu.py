@@ -10,92 +10,13 @@ import pytest
 import torch
 
 from ai_safety_gridworlds_amd import _native as N
-from ai_safety_gridworlds_amd.specs import make_spec
+from tests.kernel_gpu_util import DEV, GUARD, S16, GeometryEngine, Guarded
+from tests.kernel_gpu_util import agent_rows as _agent_rows, planes as _planes, stream as _stream, want_agents as _want_agents
+from tests.kernel_gpu_util import want_global as _want_global
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-GUARD = 64                   # sentinel bytes before and after every output
-BYTE = 0xA5
-S16 = np.int16(-23131)       # 0xA5A5: what a sentinel-filled int16 reads
 ERR_ARG, ERR_UNSUPPORTED = -1, -3
-
-
-class GeometryEngine(object):
-  """An engine created through the C ABI for its GEOMETRY only (boat_race's spec with H, W, A and the view radii overridden):
-  the coordinate entry points read nothing else of it.  NEVER stepped or reset."""
-
-  def __init__(self, H, W, A=1, radii=None, n=64):
-    sp = N.Spec.from_buffer_copy(bytes(make_spec("boat_race").native))
-    sp.H, sp.W, sp.K, sp.A = H, W, 1, A
-    for a in range(N.MAX_AGENTS):
-      sp.start_cell[a] = 0
-      rad = radii[a] if radii is not None and a < len(radii) else (-1, -1, -1, -1)
-      for j in range(4):
-        sp.view_radius[a][j] = rad[j]
-    self.H, self.W, self.A, self.n = H, W, A, n
-    self.lib = N.lib()
-    h = C.c_void_p()
-    N.check(self.lib.sgw_create(C.byref(sp), n, 0, 0, C.byref(h)), "sgw_create")
-    self.h = h
-    self.n_pad = int(self.lib.sgw_n_pad(h))
-
-  def close(self):
-    if self.h:
-      self.lib.sgw_destroy(self.h)
-      self.h = None
-
-
-def _stream():
-  return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class Guarded(object):
-  """`n_pad` rows of `row` elements of `dtype` between two guards, every byte the sentinel; rows >= `rows` are padding."""
-
-  def __init__(self, rows, n_pad, row, dtype):
-    self.rows, self.row, self.dtype = rows, row, np.dtype(dtype)
-    self.body = n_pad * row * self.dtype.itemsize
-    self.t = torch.empty(GUARD + self.body + GUARD, dtype=torch.uint8, device=DEV)
-    self.fill()
-
-  def fill(self):
-    self.t.fill_(BYTE)
-
-  @property
-  def ptr(self):
-    return self.t.data_ptr() + GUARD
-
-  def get(self):
-    """The first `rows` rows, after checking the guards and the padding rows."""
-    torch.cuda.synchronize()
-    raw = self.t.cpu().numpy()
-    used = self.rows * self.row * self.dtype.itemsize
-    assert (raw[:GUARD] == BYTE).all(), "write before the output"
-    assert (raw[GUARD + used:] == BYTE).all(), "write into rows >= N or past the output"
-    return raw[GUARD:GUARD + used].view(self.dtype)
-
-
-def _planes(rng, shape):
-  """Random uint8 planes [..., cells]: per plane all-zero, all-set or ~0.3 dense; set bytes take values 1..255."""
-  lead, cells = shape[:-1], shape[-1]
-  kind = rng.integers(0, 4, lead)                                    # 0: empty, 1: full, 2-3: random
-  kind.reshape(-1)[:2] = (0, 1)[:kind.size]
-  dens = np.where(kind == 0, 0.0, np.where(kind == 1, 1.0, 0.3))[..., None]
-  on = rng.random(lead + (cells,)) < dens
-  return (on * rng.integers(1, 256, lead + (cells,))).astype(np.uint8)
-
-
-def _want_global(planes, H, W, cap):
-  n, L = planes.shape[:2]
-  counts = np.zeros((n, L), np.int32)
-  coords = np.full((n, L, cap, 2), S16, np.int16)
-  for i in range(n):
-    for l in range(L):
-      at = np.argwhere(planes[i, l].reshape(H, W))
-      counts[i, l] = len(at)
-      coords[i, l, :min(len(at), cap)] = at[:cap]
-  return counts, coords
 
 
 def _run_global(g, planes_dev_ptr, L, cap):
@@ -158,46 +79,6 @@ AGENT_CASES = [([R(1)], 2, 65, [1]),
 
 def _shapes(radii):
   return [(r[0] + r[1] + 1, r[2] + r[3] + 1) for r in radii]
-
-
-def _agent_rows(rng, shapes, L, n, agent_layer):
-  """Per env [agent][layer][h][w] rows; the agent's own plane by env: a single cell in the window's centre, in its first row /
-  last column, several random cells (the first in row-major order is the centre), or empty (the agent is absent)."""
-  rows = []
-  for (h, w) in shapes:
-    rows.append(_planes(rng, (n, L, h * w)))
-  for a, (h, w) in enumerate(shapes):
-    own = agent_layer[a]
-    if own < 0:
-      continue
-    for i in range(n):
-      p = np.zeros(h * w, np.uint8)
-      if i % 4 == 0:
-        p[(h // 2) * w + w // 2] = 1
-      elif i % 4 == 1:
-        p[w - 1] = 200
-      elif i % 4 == 2:
-        p[:] = (rng.random(h * w) < 0.2) * rng.integers(1, 256, h * w)
-      rows[a][i, own] = p
-  return rows
-
-
-def _want_agents(rows, shapes, L, n, agent_layer, cap):
-  A = len(shapes)
-  counts = np.full((n, A, L), -1, np.int32)
-  coords = np.full((n, A, L, cap, 2), S16, np.int16)
-  for a, (h, w) in enumerate(shapes):
-    for i in range(n):
-      me = np.argwhere(rows[a][i, agent_layer[a]].reshape(h, w)) if agent_layer[a] >= 0 else []
-      if len(me) == 0:
-        continue                                                     # the facades' []: counts stay -1, nothing is written
-      ay, ax = me[0]
-      for l in range(L):
-        at = np.argwhere(rows[a][i, l].reshape(h, w))
-        counts[i, a, l] = len(at)
-        rel = np.stack([at[:, 1] - ax, at[:, 0] - ay], axis=1) if len(at) else np.zeros((0, 2), np.int64)      # x first
-        coords[i, a, l, :min(len(at), cap)] = rel[:cap]
-  return counts, coords
 
 
 def _run_agents(g, views_ptr, L, agent_layer, cap):

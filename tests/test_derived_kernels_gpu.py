@@ -14,72 +14,12 @@ from ai_safety_gridworlds_amd import _native as N
 from ai_safety_gridworlds_amd.engine import BatchedEngine
 from ai_safety_gridworlds_amd.specs import make_spec
 from tests import derived_ref as R
+from tests.kernel_gpu_util import DEV, GUARD, POISON, GeometryEngine, Out
+from tests.kernel_gpu_util import boards as _boards, dev as _dev, flags as _flags, positions as _positions, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-GUARD = 64                  # poisoned bytes after every output
-POISON = 0xA5
 ERR_ARG, ERR_UNSUPPORTED = -1, -3
-
-
-class GeometryEngine(object):
-  """An engine created through the C ABI for its GEOMETRY only: boat_race's spec with H, W, K, A, the view radii and
-  start cells overridden.  The derived-observation entry points read nothing else of the engine, so these engines let the
-  tests reach shapes no registered env has.  They are NEVER stepped or reset: the family's step kernel would read a board
-  and tables that do not exist for that geometry."""
-
-  def __init__(self, H, W, K=1, A=1, radii=None, n=64):
-    sp = N.Spec.from_buffer_copy(bytes(make_spec("boat_race").native))
-    sp.H, sp.W, sp.K, sp.A = H, W, K, A
-    for a in range(N.MAX_AGENTS):
-      sp.start_cell[a] = 0
-      rad = radii[a] if radii is not None and a < len(radii) and radii[a] is not None else (-1, -1, -1, -1)
-      for j in range(4):
-        sp.view_radius[a][j] = rad[j]
-      for u in range(N.MAX_K):
-        sp.dim_slot[a][u] = -1
-    self.H, self.W, self.K, self.A, self.n = H, W, K, A, n
-    self.lib = N.lib()
-    h = C.c_void_p()
-    N.check(self.lib.sgw_create(C.byref(sp), n, 0, 0, C.byref(h)), "sgw_create")
-    self.h = h
-    self.n_pad = int(self.lib.sgw_n_pad(h))
-
-  def close(self):
-    if self.h:
-      self.lib.sgw_destroy(self.h)
-      self.h = None
-
-
-def _stream():
-  return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class Out(object):
-  """A device output of `rows` rows of `row_bytes` bytes (+ padding rows up to n_pad and GUARD bytes), all poisoned."""
-
-  def __init__(self, rows, n_pad, row_bytes):
-    self.rows, self.n_pad, self.row_bytes = rows, n_pad, row_bytes
-    self.t = torch.full((n_pad * row_bytes + GUARD,), POISON, dtype=torch.uint8, device=DEV)
-
-  @property
-  def ptr(self):
-    return self.t.data_ptr()
-
-  def get(self, dtype=np.uint8, shape=None):
-    """The first `rows` rows as `dtype`, after checking that nothing past them was written."""
-    torch.cuda.synchronize()
-    raw = self.t.cpu().numpy()
-    tail = raw[self.rows * self.row_bytes:]
-    assert (tail == POISON).all(), "write past the %d requested rows (first at byte %d of the tail)" % (
-        self.rows, int(np.argmax(tail != POISON)))
-    body = raw[:self.rows * self.row_bytes].view(dtype)
-    return body.reshape(shape) if shape is not None else body
-
-
-def _dev(a):
-  return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _unaligned(a):
@@ -194,14 +134,6 @@ PLANE_SHAPES = [(1, 1), (1, 2), (1, 3), (2, 2), (1, 5), (3, 5), (5, 5), (6, 7), 
                 (1, 255), (255, 1), (13, 13), (17, 17), (16, 20)]
 
 
-def _boards(rng, n, H, W, chars=None):
-  b = rng.integers(0, 128, (n, H, W)).astype(np.uint8)
-  if chars is not None:                                        # mostly the layer characters, so dynamic layers light up
-    pick = np.asarray(chars, np.uint8)[rng.integers(0, len(chars), (n, H, W))]
-    b = np.where(rng.random((n, H, W)) < 0.7, pick, b)
-  return b
-
-
 @pytest.mark.parametrize("H,W", PLANE_SHAPES)
 def test_observe_rgb_and_occluded_layers(H, W):
   """RGB planes and board == char layers; n = 65 reads the boards through a pointer one byte past a 16-byte boundary.  No
@@ -271,23 +203,6 @@ def test_observe_unoccluded_layers(H, W):
 
 
 # ---- sgw_agent_views / sgw_agent_layer_views ------------------------------------------------------------------------------
-def _positions(rng, n, A, H, W):
-  spots = [(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1), (0, W // 2), (H // 2, 0), (H - 1, W // 2), (H // 2, W - 1),
-           (H // 2, W // 2)]
-  pos = np.stack([rng.integers(0, H, (n, A)), rng.integers(0, W, (n, A))], -1)
-  for e in range(n):
-    for a in range(A):
-      if (e + a) % 3 != 2:
-        pos[e, a] = spots[(e * A + a) % len(spots)]
-  return pos.astype(np.uint8)
-
-
-def _flags(rng, n, A):
-  """Every observation direction (bits 3-4) for every agent, the other bits random (they must not matter)."""
-  d = (np.arange(n)[:, None] + np.arange(A)[None, :]) % 4
-  return ((d << 3) | rng.integers(0, 8, (n, A)) | (rng.integers(0, 8, (n, A)) << 5)).astype(np.uint8)
-
-
 SQ, ASYM = True, False
 WINDOW_CASES = [
     # (H, W, radii per agent, square windows, n, layers)                      branch (sgw_agent_views / _layer_views)
