@@ -34,14 +34,14 @@ def fused_views(spec):
   is larger than the board.  Their step launch CAN write larger windows too (a chunk of envs at a time), but one wavefront per 64
   envs is slower at it than the separate launch: 126 vs 92 us per round for default aintelope_savanna at 65 536 envs, 79 vs 53 us
   for island_navigation_ex_ma with radius 3 (profiles/r06_views_inlaunch.json), so the wrappers keep two launches there."""
-  if spec.family not in FUSED_VIEW_FAMILIES or not getattr(spec, "view_shapes", None):
+  if spec.family not in FUSED_VIEW_FAMILIES or not spec.view_shapes:
     return False
   return spec.family == N.FIREMAKER_EX_MA or all(h * w <= spec.H * spec.W for (h, w) in spec.view_shapes)
 
 
 def _dtype_shape(spec, name):
   HW, A, K, M = spec.H * spec.W, spec.A, spec.K, max(spec.M, 1)
-  per_agent = (A,) if getattr(spec, "per_agent", False) else ()     # agents terminate individually (island_navigation_ex_ma)
+  per_agent = (A,) if spec.per_agent else ()     # agents terminate individually (island_navigation_ex_ma)
   return {
       "board": (torch.uint8, (HW,)), "obs_board": (torch.float32, (HW,)),
       "reward": (torch.float64, (A * K,)), "cumulative": (torch.float64, (A * K,)),
@@ -57,7 +57,7 @@ def _dtype_shape(spec, name):
 
 def _view_bytes(spec):
   """Bytes of one env's row of agent windows (sgw_view_bytes): the windows of the agents that have one, concatenated."""
-  return int(sum(h * w for (h, w) in (getattr(spec, "view_shapes", None) or ())))
+  return int(sum(h * w for (h, w) in spec.view_shapes))
 
 
 def _require(what, name, t, device, dtype, numel, layout="", contiguous=True, shape=None, also=None):
@@ -105,7 +105,7 @@ class EpisodeLog(object):
   @staticmethod
   def layout_of(spec):
     """(A, K, M, R): what decides the record's shape."""
-    return (spec.A, spec.K, spec.M, spec.A if getattr(spec, "per_agent", False) else 1)
+    return (spec.A, spec.K, spec.M, spec.A if spec.per_agent else 1)
 
   def __init__(self, engine, cap, fields=FIELDS):
     self.fields = tuple(fields)
@@ -217,7 +217,7 @@ class BatchedEngine(object):
     self._whatif_out = None  # simulate_moves
     self._fold_key = self._fold_chars = None       # fold_q_values, with the three below
     self.q_value_per_tiletype = self.q_value_seen = self.q_value_tile_chars = None
-    table = getattr(spec, "family_table", None)
+    table = spec.family_table
     if table is not None:    # aintelope_savanna: host-evaluated visit-count rewards (sgw_set_family_table)
       table = np.ascontiguousarray(table, dtype=np.float64)
       N.check(self._lib.sgw_set_family_table(self._h, table.ctypes.data, table.size), "sgw_set_family_table")
@@ -331,7 +331,7 @@ class BatchedEngine(object):
   def _agent_ks(self):
     sp = self.spec
     if sp.A > 1:
-      slots = getattr(sp, "agent_slots", list(range(len(sp.agent_chars))))
+      slots = sp.agent_slots
       ks = [0] * sp.A                                  # by column of the library's layout; an absent agent has no dimensions
       for c, q in zip(sp.agent_chars, slots):
         ks[q] = len(sp.agent_dim_names[c])
@@ -383,7 +383,7 @@ class BatchedEngine(object):
         x.agent_layer_views = t["cubes"].data_ptr()
         res["agent_layer_views"] = self.split_views(t["cubes"], L)
       if key[4]:
-        use_hidden = sp.scalar and getattr(sp, "performance", "hidden") == "hidden"
+        use_hidden = sp.scalar and sp.performance == "hidden"
         C_ = 1 if use_hidden else sp.A * sp.K
         res["last_performance"] = torch.full((n, C_), float("nan"), dtype=torch.float64, device=dev)
         res["performance_sum"] = torch.zeros((n, C_), dtype=torch.float64, device=dev)
@@ -560,7 +560,7 @@ class BatchedEngine(object):
     N.check(self._lib.sgw_set_rng_state(self._h, t.data_ptr()), "sgw_set_rng_state")
 
   def _view_flags(self, agent_flags):
-    if not getattr(self.spec, "rotating_views", False):
+    if not self.spec.rotating_views:
       return None
     return self._latest("agent_flags", agent_flags, "agent views").data_ptr()
 
@@ -570,7 +570,7 @@ class BatchedEngine(object):
     [N, sgw_view_bytes] buffer to write into (a caller that steps in a loop reuses one buffer and its views)."""
     board = self._latest("board", board, "agent_views")
     agent_pos = self._latest("agent_pos", agent_pos, "agent_views")
-    outside_chr = outside_chr or getattr(self.spec, "what_lies_outside", '#')
+    outside_chr = outside_chr or self.spec.what_lies_outside or '#'
     views = torch.empty((self.n_envs, self.view_bytes), dtype=torch.uint8, device=self.device) if out is None else out
     N.check(self._lib.sgw_agent_views(self._h, board.data_ptr(), agent_pos.data_ptr(), self._view_flags(agent_flags),
                                       ord(outside_chr), views.data_ptr(), self._stream()), "sgw_agent_views")
@@ -593,7 +593,7 @@ class BatchedEngine(object):
     if layers is None:
       layers = self.observe_layers()
     agent_pos = self._latest("agent_pos", agent_pos, "agent_layer_views")
-    outside_chr = outside_chr or getattr(sp, "what_lies_outside", '#')
+    outside_chr = outside_chr or sp.what_lies_outside or '#'
     L = len(sp.layer_chars)
     chars = self._layer_tables()[0]
     out = torch.empty((self.n_envs, self.view_bytes * L), dtype=torch.uint8, device=self.device)
@@ -634,9 +634,9 @@ class BatchedEngine(object):
   def agent_layer_index(self):
     """Per agent column of the library's layout: the index of the agent's own character in spec.layer_chars (-1: none)."""
     sp = self.spec
-    chars = list(getattr(sp, "agent_chars", ()))
+    chars = list(sp.agent_chars)
     idx = [-1] * N.MAX_AGENTS
-    for c, q in zip(chars, getattr(sp, "agent_slots", range(len(chars)))):
+    for c, q in zip(chars, sp.agent_slots):
       idx[q] = sp.layer_chars.index(c) if c in sp.layer_chars else -1
     return idx
 
@@ -649,7 +649,7 @@ class BatchedEngine(object):
     agent_layer_views: what agent_layer_views() returned -- the list of views of ONE [N, L * view_bytes] buffer, or that buffer
     (None: computed now); cap=None: the largest window's cell count; out: a (counts [N, A, L], coords [N, A, L, cap, 2]) pair."""
     sp = self.spec
-    shapes = list(getattr(sp, "view_shapes", None) or ())
+    shapes = list(sp.view_shapes)
     if agent_layer_views is None:
       agent_layer_views = self.agent_layer_views()
     vb = _view_bytes(sp)
@@ -1103,7 +1103,7 @@ class BatchedEngine(object):
   def default_tile_chars(self):
     """The table rows of fold_q_values: the spec's tile_types (the reference's TILE_TYPES, the log's columns) and then the
     agents' own characters (where NOOP lands)."""
-    if not hasattr(self.spec, "tile_types"):
+    if self.spec.tile_types is None:
       raise N.SgwError("fold_q_values: %s has no tile types (its sprites have no simulate_update)" % self.spec.name)
     return list(self.spec.tile_types) + [c for c in self.spec.agent_chars if c not in self.spec.tile_types]
 
@@ -1151,9 +1151,9 @@ class BatchedEngine(object):
     if self._layers is None:
       sp = self.spec
       chars = torch.tensor([ord(c) for c in sp.layer_chars], dtype=torch.uint8, device=self.device)
-      stat = None if getattr(sp, "layers_from_state", False) else torch.from_numpy(sp.layer_static()).to(self.device)
+      stat = None if sp.layers_from_state else torch.from_numpy(sp.layer_static()).to(self.device)
       gap = sp.layer_chars.index(sp.what_lies_beneath) if sp.what_lies_beneath in sp.layer_chars else -1
-      hidden = getattr(sp, "hidden_layer_char", None)
+      hidden = sp.hidden_layer_char
       self._layers = (chars, stat, gap, sp.layer_chars.index(hidden) if hidden is not None else -1)
     return self._layers
 

@@ -85,7 +85,7 @@ class BatchedSafetyEnvironment(object):
   def _timestep(self, o):
     self._last = o
     st = o["step_type"].reshape(self.num_envs, -1)
-    if getattr(self.spec, "per_agent", False):                # agents finish individually: the env is LAST once all are LAST/DEAD
+    if self.spec.per_agent:                # agents finish individually: the env is LAST once all are LAST/DEAD
       done_all, first_all = (st >= N.LAST).all(dim=1), (st == N.FIRST).all(dim=1)
       st = torch.where(done_all, torch.full_like(st[:, 0], N.LAST), torch.where(first_all, torch.full_like(st[:, 0], N.FIRST),
                                                                                torch.full_like(st[:, 0], N.MID)))
@@ -100,7 +100,7 @@ class BatchedSafetyEnvironment(object):
     return TimeStep(step_type=st, reward=reward, discount=o.get("discount"), observation=o)
 
   def _perf_source(self, o):
-    use_hidden = self.spec.scalar and getattr(self.spec, "performance", "hidden") == "hidden"   # distributional_shift keeps the default: episode return
+    use_hidden = self.spec.scalar and self.spec.performance == "hidden"   # distributional_shift keeps the default: episode return
     return ("hidden", 1) if use_hidden and "hidden" in o else ("cumulative", self.spec.A * self.spec.K)
 
   def _track(self, o):

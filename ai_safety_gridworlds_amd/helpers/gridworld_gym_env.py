@@ -22,6 +22,7 @@ import torch
 
 from .. import _native as N
 from ..environments import BatchedSafetyEnvironment, StepType, TerminationReason
+from . import _shared
 
 try:                                    # optional: only used as a base class / for spaces
   import gymnasium as _gym
@@ -108,20 +109,19 @@ class GridworldGymEnv(_Base):
     self.spec_ = self._env.spec
     # multi-agent env behind the single-agent wrapper (gym_env.py:182-189, 476-479): ONE agent is controlled -- the given
     # `agent_character` or the first player -- and stepped alone ({agent: action}); the state is that agent's window
-    self._ma = bool(getattr(self.spec_, "per_agent", False)) or self.spec_.family == N.FIREMAKER_EX_MA
-    cfg = getattr(self.spec_, "config", {}) or {}
+    self._ma = self.spec_.per_agent or self.spec_.family == N.FIREMAKER_EX_MA
+    cfg = self.spec_.config
     self._fixed_directions = (self.spec_.family == N.FIREMAKER_EX_MA and not cfg.get("action_direction_mode", 0)
                               and not cfg.get("observation_direction_mode", 0))      # firemaker's default: direction mode 0
     if self.spec_.A > 1 and not self._ma:
       raise NotImplementedError("%s: the batched engine plays whole rounds of this env (use GridworldZooParallelEnv)" % env_name)
     if self._ma:
       chars = list(self.spec_.agent_chars)
-      slots = list(getattr(self.spec_, "agent_slots", range(len(chars))))     # the library's column of each agent character
       self._agent_chr = agent_character if agent_character is not None else chars[0]
-      self._agent_index = slots[chars.index(self._agent_chr)]
+      self._agent_index = self.spec_.agent_slots[chars.index(self._agent_chr)]      # the library's column of the agent character
       self._ma_ascii = bool(ascii_observation_format)
       self._vm = np.array([self.spec_.native.value_map[i] for i in range(128)], np.float32)
-      self._seed_env(seed)
+      _shared.seed_env(self._env.engine, self.spec_, seed)
     self._use_transitions = use_transitions
     self._flatten_observations = flatten_observations
     self._layers_in_observation = layers_in_observation
@@ -160,14 +160,7 @@ class GridworldGymEnv(_Base):
     self._internal_np_random = np.random.Generator(np.random.PCG64(np.random.SeedSequence(seed)))
     self._action_space._rng = self._internal_np_random
     if self._ma:
-      self._seed_env(seed)
-
-  def _seed_env(self, seed):                     # environment_data[NP_RANDOM] = seeding.np_random(seed)[0]
-    if getattr(self.spec_, "needs_rng", False) or self.spec_.family == N.FIREMAKER_EX_MA:
-      st = np.random.PCG64(np.random.SeedSequence(seed)).state["state"]
-      m = (1 << 64) - 1
-      self._env.engine.set_rng_state(np.array([[st["state"] >> 64, st["state"] & m, st["inc"] >> 64, st["inc"] & m]],
-                                              dtype=np.uint64))
+      _shared.seed_env(self._env.engine, self.spec_, seed)
 
   def close(self):
     self._env.close()
@@ -190,7 +183,7 @@ class GridworldGymEnv(_Base):
     sp = self.spec_
     if sp.scalar:
       raise AttributeError("'%s' environment has no attribute 'get_reward_unit_space'" % sp.name)
-    space = getattr(sp, "reward_unit_space", None)
+    space = sp.reward_unit_space
     return None if space is None else [np.array(space[0], dtype=np.float64), np.array(space[1], dtype=np.float64)]
 
   def get_env_seed(self):
@@ -218,7 +211,7 @@ class GridworldGymEnv(_Base):
   def _q_tensor(self):
     """The stored Q-values as the float64 [1, A, n_actions, D] tensor the env takes, or None where they are only kept."""
     sp, q = self.spec_, self._q_value_per_action
-    if q is None or not hasattr(sp, "tile_types") or sp.action_lo != 0:
+    if q is None or sp.tile_types is None or sp.action_lo != 0:
       return None
     q = np.asarray(q.detach().cpu() if torch.is_tensor(q) else q, dtype=np.float64)
     if q.ndim == 0 or q.shape[0] != sp.n_actions:
@@ -230,13 +223,12 @@ class GridworldGymEnv(_Base):
 
   # ---- helpers --------------------------------------------------------------------------------
   def _host(self, ts):
-    o = {k: v[0].detach().cpu().numpy() for k, v in ts.observation.items()}
-    return o
+    return {k: v[0].detach().cpu().numpy() for k, v in ts.observation.items()}
 
   def _dim_names(self):
     """The controlled agent's reward dimensions (firemaker's workers and supervisor have different ones)."""
     sp = self.spec_
-    if self._ma and getattr(sp, "agent_dim_names", None):
+    if self._ma and sp.agent_dim_names:
       return list(sp.agent_dim_names[self._agent_chr])
     return list(sp.dim_names)
 
@@ -280,28 +272,24 @@ class GridworldGymEnv(_Base):
         info["average_reward"] = pick(ds["average_reward"]).cpu().numpy()[:len(names)].astype(np.float64)
       for key in ("gini_index", "cumulative_gini_index", "mo_variance", "cumulative_mo_variance", "average_mo_variance"):
         info[key] = np.float64(pick(ds[key]).item())
-      lay = None
+      layers = None
       if self._layers_in_observation or self._object_coordinates_in_observation or self._layers_order_in_cube is not None:
-        lay = self._env.engine.observe_layers()[0].cpu().numpy().astype(bool)
-        layers = {c: lay[i] for i, c in enumerate(sp.layer_chars)}
+        layers = _shared.layers_dict(sp, self._env.engine.observe_layers())
       if self._layers_in_observation:
         info["info_observation_layers_dict"] = layers
       if self._object_coordinates_in_observation:                 # calculate_observation_coordinates (safety_game_mo.py:422-457)
         if self._occlusion_in_layers:
           raise NotImplementedError("info_observation_coordinates with occlusion_in_layers=True: the reference's branch "
                                     "(safety_game_mo.py:443-457) raises NameError at this snapshot")
-        info["info_observation_coordinates"] = {c: [tuple(x) for x in np.argwhere(layers[c]).tolist()] for c in layers}
+        info["info_observation_coordinates"] = _shared.coordinates(layers)
       if self._layers_order_in_cube is not None:                  # get_layers_order / calculate_observation_layers_cube (:460-520)
-        order = list(self._layers_order_in_cube)
-        ascii_board = np.vectorize(chr)(o["board"])
-        if order == []:
-          order = sorted(layers.keys()) if not self._occlusion_in_layers else sorted(np.unique(ascii_board).tolist())
-        info["info_observation_layers_order"] = order
-        if not self._occlusion_in_layers:                           # absent layers read as zeros (cross-environment cubes)
-          zero = np.zeros_like(next(iter(layers.values())))
-          info["info_observation_layers_cube"] = np.stack([layers.get(c, zero) for c in order], axis=0)
-        else:
-          info["info_observation_layers_cube"] = np.stack([ascii_board == c for c in order], axis=0)
+        if not self._occlusion_in_layers:
+          order, cube = _shared.ordered_cube(layers, self._layers_order_in_cube)
+        else:                                                       # the occluded cube is cut from the rendered board
+          ascii_board = np.vectorize(chr)(o["board"])
+          order = list(self._layers_order_in_cube) or sorted(np.unique(ascii_board).tolist())
+          cube = np.stack([ascii_board == c for c in order], axis=0)
+        info["info_observation_layers_order"], info["info_observation_layers_cube"] = order, cube
       if self._ma:                                                # gym_env.py:373-384, 428-439: the controlled agent's own window
         ch = self._agent_chr
         flags = int(o["agent_flags"].reshape(-1)[ai])
@@ -309,23 +297,15 @@ class GridworldGymEnv(_Base):
           info["observation_direction"], info["action_direction"] = (flags >> 3) & 3, (flags >> 1) & 3
         view = self._env.engine.agent_views()[ai][0].cpu().numpy()
         info["info_agent_observations"] = np.vectorize(chr)(view) if self._ma_ascii else self._vm[view]
-        if lay is not None:
-          cube = self._env.engine.agent_layer_views()[ai][0].cpu().numpy().astype(bool)
-          al = {c: cube[j] for j, c in enumerate(sp.layer_chars)}
+        if layers is not None:
+          al = _shared.layers_dict(sp, self._env.engine.agent_layer_views()[ai])
           if self._layers_in_observation:
             info["info_agent_observation_layers_dict"] = al
-          if self._object_coordinates_in_observation:             # calculate_agents_observation_coordinates (safety_game_moma.py:528-580)
-            me = np.argwhere(al[ch]) if ch in al else []
-            if len(me) > 0:
-              ay, ax = int(me[0][0]), int(me[0][1])
-              info["info_agent_observation_coordinates"] = {c: [(int(x) - ax, int(y) - ay) for y, x in np.argwhere(al[c]).tolist()] for c in al}
-            else:
-              info["info_agent_observation_coordinates"] = []
+          if self._object_coordinates_in_observation:
+            info["info_agent_observation_coordinates"] = _shared.relative_coordinates(al, ch)
           if self._layers_order_in_cube is not None:              # the SAME order parameter as the global cube (gym_env.py:382-384)
-            order = list(self._layers_order_in_cube) or sorted(al.keys())
-            zero = np.zeros_like(cube[0])
-            info["info_agent_observation_layers_order"] = order
-            info["info_agent_observation_layers_cube"] = np.stack([al.get(c, zero) for c in order], axis=0)
+            order, cube = _shared.ordered_cube(al, self._layers_order_in_cube)
+            info["info_agent_observation_layers_order"], info["info_agent_observation_layers_cube"] = order, cube
     if sp.name == "island_navigation_ex":
       info["safety"] = int(o["safety"])
     return info
@@ -542,7 +522,7 @@ class GridworldVectorEnv(object):
   def _step_full(self, actions):
     """A step from Python is host-bound: the outputs live in persistent buffers, so the info dict of views is built once
     and a step is one library call plus one comparison."""
-    o = self._env.engine.step_full(actions, rgb=True, layers=hasattr(self.spec_, "drape_chars"), stats=not self.spec_.scalar, performance=True,
+    o = self._env.engine.step_full(actions, rgb=True, layers=self.spec_.has_layers, stats=not self.spec_.scalar, performance=True,
                                    replay=self._replay)
     self._env._log_step()
     self._env._last = o

@@ -33,7 +33,7 @@ class GridworldZooAecEnv(_Base):
   def __init__(self, env_name, *args, **kwargs):
     self._par = GridworldZooParallelEnv(env_name, *args, **kwargs)
     sp = self._par.spec_
-    if sp.A > 1 and not getattr(sp, "per_agent", False):
+    if sp.A > 1 and not sp.per_agent:
       raise NotImplementedError("%s: the batched engine plays whole rounds of this env; one-agent-at-a-time stepping "
                                 "needs a family with per-agent rounds (island_navigation_ex_ma, aintelope_savanna)" % env_name)
     self.possible_agents = list(self._par.possible_agents)

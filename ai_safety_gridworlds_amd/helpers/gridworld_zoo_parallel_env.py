@@ -24,6 +24,7 @@ try:
 except Exception:                       # pragma: no cover - pettingzoo absent in this image
   _Base = object
 
+from . import _shared
 from .gridworld_gym_env import DiscreteActionSpace, MultiDiscreteActionSpace, BoxObservationSpace
 
 OUTS = ("board", "obs_board", "reward", "cumulative", "step_type", "term_reason", "discount", "metrics", "frame",
@@ -80,16 +81,18 @@ class GridworldZooParallelEnv(_Base):
     self._test_death, self._test_death_probability = test_death, test_death_probability
     chars = sp.agent_chars if self._ma else ['0']
     # column of each agent in the library's per-agent arrays (firemaker_ex_ma keeps the ('1','2','S') layout whatever amount_agents is)
-    self._slots = list(getattr(sp, "agent_slots", range(len(chars))))
+    self._slots = sp.agent_slots
     self.possible_agents = ["agent_%s" % c for c in chars]
     self.agent_name_mapping = dict(zip(self.possible_agents, chars))
     self._np_random = np_random if np_random is not None else np.random.Generator(np.random.PCG64(np.random.SeedSequence(seed)))
-    self._seed_env(seed)
+    _shared.seed_env(self._env.engine, sp, seed)
     self._dones = {a: False for a in self.possible_agents}
     self._test_deads = {a: False for a in self.possible_agents}
     self._last_agent_boards = {a: None for a in self.possible_agents}
     self._last_hidden_reward = {a: 0.0 for a in self.possible_agents}
     self._state = None
+    self._last_board = None
+    self._played = None                 # {agent character: action} of the agents that played the last round
     self._vm = np.array([sp.native.value_map[i] for i in range(128)], np.float32)
     space = MultiDiscreteActionSpace if use_multi_discrete_action_space else DiscreteActionSpace       # zoo.py:225-228
     self._action_spaces = {a: space(sp.action_lo, sp.n_actions, self._np_random) for a in self.possible_agents}
@@ -98,13 +101,6 @@ class GridworldZooParallelEnv(_Base):
     for i, a in enumerate(self.possible_agents):
       h, w = sp.view_shapes[self._slots[i]] if self._ma else (sp.H, sp.W)
       self._observation_spaces[a] = BoxObservationSpace((2 if use_transitions else 1, h, w), min(vals), max(vals))
-
-  def _seed_env(self, seed):
-    if self.spec_.family == N.FIREMAKER_EX_MA or getattr(self.spec_, "needs_rng", False):   # environment_data[NP_RANDOM] = seeding.np_random(seed)[0]
-      st = np.random.PCG64(np.random.SeedSequence(seed)).state["state"]
-      m = (1 << 64) - 1
-      self._env.engine.set_rng_state(np.array([[st["state"] >> 64, st["state"] & m, st["inc"] >> 64, st["inc"] & m]],
-                                              dtype=np.uint64))
 
   # ---- PettingZoo surface ---------------------------------------------------------------------
   @property
@@ -131,7 +127,7 @@ class GridworldZooParallelEnv(_Base):
 
   def seed(self, seed=None):
     self._np_random = np.random.Generator(np.random.PCG64(np.random.SeedSequence(seed)))
-    self._seed_env(seed)
+    _shared.seed_env(self._env.engine, self.spec_, seed)
 
   def close(self):
     self._env.close()
@@ -171,33 +167,20 @@ class GridworldZooParallelEnv(_Base):
     if sp.scalar or not need_layers:
       return out
     lay = self._env.engine.observe_layers()
-    glob = lay[0].cpu().numpy().astype(bool)
-    layers = {c: glob[i] for i, c in enumerate(sp.layer_chars)}                 # observation['layers'] (unoccluded)
-    out["layers"] = layers
-    if self._object_coordinates_in_observation:                                  # safety_game_moma.py:583-603
-      out["coords"] = {c: [tuple(x) for x in np.argwhere(layers[c]).tolist()] for c in layers}
-    if self._layers_order_in_cube is not None:                                   # :621-672
-      order = list(self._layers_order_in_cube) or sorted(layers.keys())
-      zero = np.zeros_like(glob[0])
-      out["order"], out["cube"] = order, np.stack([layers.get(c, zero) for c in order], axis=0)
+    layers = out["layers"] = _shared.layers_dict(sp, lay)                       # observation['layers'] (unoccluded)
+    if self._object_coordinates_in_observation:
+      out["coords"] = _shared.coordinates(layers)
+    if self._layers_order_in_cube is not None:
+      out["order"], out["cube"] = _shared.ordered_cube(layers, self._layers_order_in_cube)
     if self._ma:                                                                 # agent_perspectives_with_layers (:430-525)
-      cubes = [v[0].cpu().numpy().astype(bool) for v in self._env.engine.agent_layer_views(layers=lay)]
+      cubes = self._env.engine.agent_layer_views(layers=lay)
       out["agent_layers"], out["agent_coords"], out["agent_order"], out["agent_cube"] = {}, {}, {}, {}
       for i, a in enumerate(self.possible_agents):
-        ch = self.agent_name_mapping[a]
-        al = {c: cubes[self._slots[i]][j] for j, c in enumerate(sp.layer_chars)}
-        out["agent_layers"][a] = al
-        if self._object_coordinates_in_observation:                              # calculate_agents_observation_coordinates (:528-580)
-          me = np.argwhere(al[ch]) if ch in al else []
-          if len(me) > 0:
-            ay, ax = int(me[0][0]), int(me[0][1])
-            out["agent_coords"][a] = {c: [(int(x) - ax, int(y) - ay) for y, x in np.argwhere(al[c]).tolist()] for c in al}
-          else:
-            out["agent_coords"][a] = []                                          # the agent is not in its own layers
+        al = out["agent_layers"][a] = _shared.layers_dict(sp, cubes[self._slots[i]])
+        if self._object_coordinates_in_observation:
+          out["agent_coords"][a] = _shared.relative_coordinates(al, self.agent_name_mapping[a])
         if self._layers_order_in_cube_per_agent is not None:
-          order = list(self._layers_order_in_cube_per_agent.get(a, [])) or sorted(al.keys())
-          zero = np.zeros_like(cubes[self._slots[i]][0])
-          out["agent_order"][a], out["agent_cube"][a] = order, np.stack([al.get(c, zero) for c in order], axis=0)
+          out["agent_order"][a], out["agent_cube"][a] = _shared.ordered_cube(al, self._layers_order_in_cube_per_agent.get(a, []))
     return out
 
   def _shared_infos(self, o):
@@ -225,9 +208,8 @@ class GridworldZooParallelEnv(_Base):
     out["metrics_matrix"] = mm
     # ACTUAL_ACTIONS: what each agent that played this round did (safety_game_ma.py:784-788; no policy wrapper changes actions
     # in the multi-agent envs): the submitted actions of the agents that were alive, nothing on a reset / auto-reset round
-    acted = getattr(self, "_played", None)
-    if acted:
-      out["actual_actions"] = {c: {"step": int(v)} for c, v in acted.items()}
+    if self._played:
+      out["actual_actions"] = {c: {"step": int(v)} for c, v in self._played.items()}
     # observable attributes (observation_distiller_ex.py:104-141): no environment of the reference sets any, so every category
     # is an all-zero board, an empty layer dict and a board of empty strings
     cats = self._observable_attribute_categories
@@ -248,7 +230,7 @@ class GridworldZooParallelEnv(_Base):
               "metrics_dict": dict(zip(sp.metric_names, o["metrics"].reshape(-1)[:sp.M].tolist())),
               "extra_observations": {}}
       st_all = o["step_type"].reshape(-1)
-      if getattr(sp, "per_agent", False):
+      if sp.per_agent:
         if (st_all >= N.LAST).all():        # the reference nests the whole per-agent dict under every agent (safety_game_moma.py:1229-1231)
           tr = {c: int(v) for c, v in zip(sp.agent_chars, o["term_reason"].reshape(-1))}
           info["extra_observations"]["termination_reason"] = {c: dict(tr) for c in sp.agent_chars}
@@ -322,7 +304,7 @@ class GridworldZooParallelEnv(_Base):
         if a in actions:
           raise ValueError("Agent %s is done" % self.agent_name_mapping[a])      # pycolab_interface_ma.py:218
         continue
-      if a not in actions and (getattr(sp, "per_agent", False) or sp.family == N.FIREMAKER_EX_MA):
+      if a not in actions and (sp.per_agent or sp.family == N.FIREMAKER_EX_MA):
         acts[q] = -1                       # not in the submitted dict: the agent does not play this round (PM:173-246)
         continue
       v = actions.get(a, 0)
@@ -337,12 +319,12 @@ class GridworldZooParallelEnv(_Base):
     o, states = self._observe(ts, first)
     st_host = o["step_type"].reshape(-1)
     all_first = bool((st_host[[self._slots[i] for i in range(len(self.possible_agents))]] == N.FIRST).all()) \
-        if getattr(sp, "per_agent", False) else first
+        if sp.per_agent else first
     self._played = None if all_first else {self.agent_name_mapping[a]: acts[self._slots[i]] for i, a in enumerate(self.possible_agents)
                                            if not self._dones[a] and acts[self._slots[i]] >= 0}
     infos = self._infos(o, states)
     st_all = o["step_type"].reshape(-1)
-    per_agent = getattr(sp, "per_agent", False)
+    per_agent = sp.per_agent
     if per_agent:
       first = bool((st_all == N.FIRST).all())
     rewards, dones = {}, {}

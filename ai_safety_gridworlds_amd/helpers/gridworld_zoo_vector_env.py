@@ -54,9 +54,11 @@ class GridworldZooVectorEnv(object):
     # one more launch per step for all agents, no synchronisation)
     self._targets = bool(action_targets)
     self._q = None
-    self._fused = fused_views(make_spec(env_name, **kwargs))
+    self._packed_for = self._view_buf = self._cached = None      # _pack's views of the engine's outputs, built at the first step
+    sp0 = make_spec(env_name, **kwargs)                        # what decides the output set, in front of the engine
+    self._fused = fused_views(sp0)
     self._ascii = bool(ascii_observation_format)
-    cfg0 = getattr(make_spec(env_name, **kwargs), "config", None) or {}
+    cfg0 = sp0.config
     self._turning = bool(cfg0.get("action_direction_mode", 0) or cfg0.get("observation_direction_mode", 0))
     # `terminated` and the decoded directions leave with the step launch (sgw_out.done / obs_dir / act_dir): no torch launch per step
     outs = OUTS + (("obs_dir", "act_dir") if self._turning else ()) + ((("views",) if self._ascii else ("obs_views",)) if self._fused else ())
@@ -64,12 +66,12 @@ class GridworldZooVectorEnv(object):
                                          track_performance=False, episode_log=episode_log, scalarise=scalarise, **kwargs)
     self.episode_log = self._env.episode_log                   # episode_log=cap: an EpisodeLog every step appends to (None: no log)
     sp = self.spec_ = self._env.spec
-    if sp.A < 2 and not getattr(sp, "per_agent", False):
+    if sp.A < 2 and not sp.per_agent:
       raise NotImplementedError("%s is a single-agent env: use GridworldVectorEnv" % env_name)
     self.num_envs = int(num_envs)
     self.device = self._env.device
-    self._per_agent = bool(getattr(sp, "per_agent", False))
-    self._slots = list(getattr(sp, "agent_slots", range(len(sp.agent_chars))))
+    self._per_agent = sp.per_agent
+    self._slots = sp.agent_slots
     self.possible_agents = ["agent_%s" % c for c in sp.agent_chars]
     self.agent_name_mapping = dict(zip(self.possible_agents, sp.agent_chars))
     self._k = {a: len(sp.agent_dim_names[c]) for a, c in self.agent_name_mapping.items()}
@@ -90,7 +92,7 @@ class GridworldZooVectorEnv(object):
     self._up = torch.full((self.num_envs,), 2, dtype=torch.uint8, device=self.device)         # Directions.UP: the fixed-direction envs
     # the original seed of env i (environment_data[SEED] of the reference) is (seed or 0) + its global id
     self._seed_base, self._env_id_base = (0 if seed is None else int(seed)), int(env_id_base)
-    self._has_rng = bool(sp.family == N.FIREMAKER_EX_MA or getattr(sp, "needs_rng", False))
+    self._has_rng = sp.needs_rng
     if self._has_rng:
       # env i draws from Generator(PCG64(SeedSequence(seed + global id))): what seeding.np_random gives N separately seeded envs;
       # seeded by one launch (sgw_seed_rng: the engine adds env_id_base itself)
@@ -118,7 +120,7 @@ class GridworldZooVectorEnv(object):
     n = self.num_envs
     eng = self._env.engine
     sc = eng.scalarise() if self._env.scalarise else None      # scalarise=True: one more library call, into persistent tensors
-    if getattr(self, "_packed_for", None) is not o.get("reward"):       # first call, or the engine reallocated its outputs
+    if self._packed_for is not o.get("reward"):       # first call, or the engine reallocated its outputs
       self._packed_for = o.get("reward")
       if self._fused:                                              # the step launch wrote the windows (ascii or value-mapped)
         views = eng.split_views(o["views" if self._ascii else "obs_views"])

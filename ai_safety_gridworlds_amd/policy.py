@@ -39,7 +39,7 @@ def policy_cells(spec, source):
   """C of a table for this spec and source: H*W, or the largest window's h*w."""
   if source == "board":
     return int(spec.H * spec.W)
-  shapes = getattr(spec, "view_shapes", None) or ()
+  shapes = spec.view_shapes
   return int(max([h * w for (h, w) in shapes] or [0]))
 
 
@@ -53,7 +53,7 @@ class TablePolicy(object):
       raise ValueError("source must be 'board' or 'views'")
     spec = engine.spec
     if chars is None:
-      chars = getattr(spec, "layer_chars", None)
+      chars = spec.layer_chars
       if chars is None:
         raise ValueError("TablePolicy: this spec names no layer characters; pass chars")
     chars = [c if isinstance(c, str) else chr(c) for c in chars]
@@ -145,7 +145,7 @@ class TablePolicy(object):
       raise ValueError("table holds an action outside the spec's range")
     w = np.zeros(tuple(pol.weights.shape), np.float32)
     chars = list(spec.agent_chars)
-    slots = list(getattr(spec, "agent_slots", range(len(chars))))      # the output column of each present agent
+    slots = spec.agent_slots      # the output column of each present agent
     for a, own in zip(slots, chars):
       ch = agent_chr if agent_chr is not None else own
       g = pol.code(ch)

@@ -59,7 +59,7 @@ class StepLogger(object):
     self.env, self.spec = env, env.spec
     if self.spec.A != 1 or self.spec.scalar:
       raise NotImplementedError("StepLogger covers the single-agent multi-objective envs (SafetyEnvironmentMo's logger)")
-    if LOG_QVALUES_PER_TILETYPE in log_columns and not hasattr(self.spec, "tile_types"):
+    if LOG_QVALUES_PER_TILETYPE in log_columns and self.spec.tile_types is None:
       raise NotImplementedError("%s: no tile types, no tiletype_qvalue column" % self.spec.name)
     for need in ("reward", "cumulative", "frame", "metrics"):
       if need not in env.engine.outputs:
@@ -68,7 +68,7 @@ class StepLogger(object):
     self.env_indices = [int(i) for i in env_indices]
     self.trial, self.env_seed = trial, env_seed
     self.log_arguments = {} if log_arguments is None else log_arguments
-    self.metric_order = list(getattr(self.spec, "metrics_log_order", self.spec.metric_names))
+    self.metric_order = list(self.spec.metrics_log_order or self.spec.metric_names)
     self._metric_cols = [self.spec.metric_names.index(m) for m in self.metric_order]
     self.episode = {i: 1 for i in self.env_indices}
     self._played = {i: False for i in self.env_indices}

@@ -166,7 +166,7 @@ def ma_host_tape(row, spec, steps=None):
 
 def ma_slots(row, spec):
   """The agent columns that are present (firemaker keeps the '1', '2', 'S' layout)."""
-  return list(getattr(spec, "agent_slots", range(spec.A))) if row["oracle"] == "ma" else list(range(spec.A))
+  return list(spec.agent_slots) if row["oracle"] == "ma" else list(range(spec.A))
 
 
 def ma_quit_rounds(row, spec, tape, want, steps):

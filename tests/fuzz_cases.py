@@ -142,7 +142,7 @@ def firemaker_case(rnd, E=400, T=120, nthreads=16):
   views = [w.numpy() for w in eng.split_views(got["views"])]
   got = {k: v.numpy() for k, v in got.items()}
   eng.close()
-  slots = list(getattr(spec, "agent_slots", [0, 1, 2]))
+  slots = list(spec.agent_slots)
   ok = bool((got["board"] == want["board"]).all()) and bool((got["frame"] == want["frame"]).all())
   for f in ("step_type", "reward", "cumulative"):
     ok &= bool((got[f][:, :, slots] == want[f][:, :, slots]).all())

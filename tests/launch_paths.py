@@ -222,7 +222,7 @@ def oracle_mismatches(row, spec, got, want, s0, views=None):
   tr = got["term_reason"].astype(np.int16); tr[tr == 255] = -1
   fl = got["agent_flags"]
   if row["oracle"] == "ma":                                          # firemaker: per-agent slots
-    slots = list(getattr(spec, "agent_slots", range(spec.A)))
+    slots = list(spec.agent_slots)
     E = got["board"].shape[0]
     pairs = [("board", got["board"].reshape(want["board"][:, sl].shape), want["board"][:, sl]),
              ("frame", got["frame"], want["frame"][:, sl]), ("discount", got["discount"], want["discount"][:, sl]),

@@ -180,6 +180,6 @@ def plan_geometries(row, spec):
   A, K = spec.A, spec.K
   pa = A if getattr(spec, "per_agent", False) else 1
   cs = A * K if spec.family in CUM_IN_LDS_FAMILIES else 0
-  vb = int(sum(h * w for (h, w) in (getattr(spec, "view_shapes", None) or ())))
+  vb = int(sum(h * w for (h, w) in spec.view_shapes))
   vgs = sorted({64} | ({view_chunk(vb, w) for w in (8, 16, 32)} if vb else set()))
   return [(spec.H * spec.W, A, K, spec.M, pa, vb, cs, vg) for vg in vgs]

@@ -331,7 +331,7 @@ def test_step_full_extras_match_references(env_name, kw):
   if getattr(spec, "needs_rng", False) or spec.family == N.FIREMAKER_EX_MA:
     eng.set_rng_seeds(np.arange(n) + 11)
   eng.reset()
-  views = bool(getattr(spec, "view_shapes", None))
+  views = bool(spec.view_shapes)
   acts = eng.fill_actions(T, 0xD17)
   A, K, H, W = spec.A, spec.K, spec.H, spec.W
   L = len(spec.layer_chars)

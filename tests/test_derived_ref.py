@@ -120,7 +120,7 @@ def test_views_ref_reproduces_fixture(name):
   """The agents' windows (get_agent_perspective) from the board, the recorded positions and observation directions.  A
   window is checked wherever its agent is on the board (an agent that left the game has no meaningful window)."""
   spec, radii, chars, pos, dirs, board, fx, E = _agent_windows(name)
-  outside = ord(spec.what_lies_outside) if getattr(spec, "what_lies_outside", None) else spec.native.view_outside
+  outside = ord(spec.what_lies_outside) if spec.what_lies_outside else spec.native.view_outside
   if "view" in fx.files:
     want = [fx["view"][:E].reshape((len(board), -1) + fx["view"].shape[-2:])[:, a] for a in range(spec.A)]
   else:

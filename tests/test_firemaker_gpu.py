@@ -58,7 +58,7 @@ def check(name, got, want, spec=None):
   """Columns follow the fixed ('1','2','S') layout; with amount_agents < 3 only the present agents' columns are compared
   (the reference's dicts have no key for the others) and the engine's metrics (the present rows, in order) are placed at
   their METRICS_LABELS_TEMPLATE rows."""
-  slots = list(getattr(spec, "agent_slots", [0, 1, 2])) if spec is not None else [0, 1, 2]
+  slots = list(spec.agent_slots) if spec is not None else [0, 1, 2]
   for f in ("step_type", "reward", "cumulative"):
     G.assert_same(name + "." + f, got[f][:, :, slots], want[f][:, :, slots])
   G.assert_same(name + ".discount", got["discount"], want["discount"])
@@ -237,3 +237,19 @@ def test_firemaker_through_the_gym_facade_with_agent_character(agent):
       assert list(info["reward_dict"]) == (["ENERGY", "WORKSHOP"] if q < 2 else ["ENERGY", "EXTERNAL_FIRE", "TRESPASSING"])
       assert np.array_equal(info["cumulative_reward"], want["cumulative"][0, t + 1, q, :k]), t
   env.close()
+
+
+@pytest.mark.parametrize("agent", ["1", "S"])
+def test_gym_facade_infos_of_a_controlled_firemaker_agent_are_the_recorded_ones(agent):
+  """Every key GridworldGymEnv returns for one controlled agent of firemaker_ex_ma -- the layer dicts, coordinates, orders and
+  cubes of the board and of the agent's window among them -- over a reset and a dozen steps, against this facade's own recorded
+  output (tests/facade_infos.py, tests/golden/make_fixtures_gym_infos.py)."""
+  import os
+  from tests import facade_infos
+  want = np.load(os.path.join(G.GOLDEN, "gym_firemaker_infos.npz"))
+  got = facade_infos.record(agent)
+  names = [k for k in want.files if k.startswith(agent + "/")]
+  assert sorted(got) == sorted(names) and len(names) > 13 * 20
+  for k in names:
+    assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+    assert np.array_equal(got[k], want[k], equal_nan=got[k].dtype.kind == "f"), k

@@ -32,7 +32,7 @@ def raw_agent_views(eng):
   vb = int(eng._lib.sgw_view_bytes(eng._h))
   out = torch.empty((eng.n_envs, vb), dtype=torch.uint8, device=eng.device)
   N.check(eng._lib.sgw_agent_views(eng._h, eng._bufs["board"].data_ptr(), eng._bufs["agent_pos"].data_ptr(),
-                                   eng._view_flags(None), ord(getattr(eng.spec, "what_lies_outside", '#')), out.data_ptr(),
+                                   eng._view_flags(None), ord(eng.spec.what_lies_outside or '#'), out.data_ptr(),
                                    eng._stream()), "sgw_agent_views")
   return out
 
