@@ -344,6 +344,17 @@ int sgw_create(const sgw_spec* spec, int64_t n_envs, int64_t env_id_base, int de
     return fail(SGW_ERR_ARG, "sgw_create: aintelope_savanna holds a layer in 3 x 64 bits (H*W <= 192) and lays out two agents (A = 2)");
   if (spec->family == SGW_ISLAND_NAVIGATION_EX_MA && (HW > 128 || spec->A != 2))
     return fail(SGW_ERR_ARG, "sgw_create: island_navigation_ex_ma keeps its map in 4 or 8 x 16 nibbles (H*W <= 128) and has two agents");
+  // a round of A plays ends an episode on a frame of up to max_iterations + A - 1, and every family keeps the frame in 16 bits
+  // (read back by the idle rounds after an episode's end, which report the frame without playing)
+  int players = 1;
+  if (spec->family == SGW_FIREMAKER_EX_MA)
+    players = 3 - ((spec->flags & Firemaker::F_NO_AGENT2) ? 1 : 0) - ((spec->flags & Firemaker::F_NO_SUP) ? 1 : 0);
+  else if (spec->family == SGW_ISLAND_NAVIGATION_EX_MA) players = 2;
+  else if (spec->family == SGW_AINTELOPE_SAVANNA) players = (spec->flags & Savanna::F_TWO) ? 2 : 1;
+  if (spec->max_iterations > 65535 - (players - 1))
+    return fail(SGW_ERR_ARG, "sgw_create: max_iterations + agents - 1 must fit the frame's 16 bits (max_iterations <= 65535 - (agents - 1))");
+  if (spec->family == SGW_FIREMAKER_EX_MA && !(spec->params[Firemaker::P_RELOAD] <= 65535.0))
+    return fail(SGW_ERR_ARG, "sgw_create: firemaker_ex_ma keeps the stop button's countdown in 16 bits (reload = 1 + 1 + duration <= 65535)");
   const int words = family_words(*spec);
   if (words < 0) return fail(SGW_ERR_UNSUPPORTED, "sgw_create: unknown game family");
   if ((spec->family == SGW_ISLAND_NAVIGATION_EX || spec->family == SGW_ISLAND_NAVIGATION_EX_MA ||

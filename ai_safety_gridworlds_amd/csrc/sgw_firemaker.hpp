@@ -36,6 +36,8 @@
 // metrics ids (FM:123-140): 0-2 ExternalVisits_{1,2,S} 3-5 Internal 6-8 Workshop 9-11 Fire 12-14 StopButton 15 countdown
 // agent_flags output: bit0 the agent stands on a burning cell (its tile of the hidden fire layer), bits 1-2 action direction,
 //   bits 3-4 observation direction (Directions LEFT=0 RIGHT=1 UP=2 DOWN=3)
+// word 0: 0-15 frame | 16-23 countdown, low byte | 24-26 at_ws | 27 generator flag | 32-35 step type | 36-39 termination reason |
+//   40-55 n_ext | 56-63 countdown, high byte (the reload 1 + 1 + duration is at most 65 535: make_spec, sgw_create)
 // state words: 0 core | 1 positions + the six 2-bit directions | 2 rng buffer | 3-6 PCG64 state/inc | 7-11 fire | 12-15 visits | 16-24 cumulative
 #pragma once
 
@@ -110,7 +112,8 @@ struct FiremakerT {
     Cursor c(a, env);
     uint64_t w0 = c.get(), w1 = c.get(), w2 = c.get();
     s.frame = (int)(w0 & 0xffff); s.step_type = (int)((w0 >> 32) & 0xf); s.term = (int)((w0 >> 36) & 0xf);
-    s.countdown = (int)((w0 >> 16) & 0xff); s.at_ws = (int)((w0 >> 24) & 0x7); s.g.has32 = pcg64_flag_of(w0);
+    s.countdown = (int)(((w0 >> 16) & 0xff) | ((w0 >> 48) & 0xff00));       // 16 bits: low byte at 16-23, high byte at 56-63
+    s.at_ws = (int)((w0 >> 24) & 0x7); s.g.has32 = pcg64_flag_of(w0);
     s.n_ext = (int)((w0 >> 40) & 0xffff);
 #pragma unroll
     for (int ag = 0; ag < 3; ++ag) { s.row[ag] = (int)((w1 >> (16 * ag)) & 0xff); s.col[ag] = (int)((w1 >> (16 * ag + 8)) & 0xff); }
@@ -132,7 +135,8 @@ struct FiremakerT {
     Cursor c(a, env);
     uint64_t w0 = (uint64_t)(s.frame & 0xffff) | ((uint64_t)(s.countdown & 0xff) << 16) | ((uint64_t)(s.at_ws & 7) << 24) |
                   pcg64_flag_bits(s.g) | ((uint64_t)(s.step_type & 0xf) << 32) |
-                  ((uint64_t)(s.term & 0xf) << 36) | ((uint64_t)(s.n_ext & 0xffff) << 40);
+                  ((uint64_t)(s.term & 0xf) << 36) | ((uint64_t)(s.n_ext & 0xffff) << 40) |
+                  ((uint64_t)((s.countdown >> 8) & 0xff) << 56);   // a countdown of up to 65 535 (sgw_create refuses a larger reload)
     uint64_t w1 = (uint64_t)(s.dirs & 0xfff) << 48;
 #pragma unroll
     for (int ag = 0; ag < 3; ++ag) w1 |= ((uint64_t)(s.row[ag] & 0xff) << (16 * ag)) | ((uint64_t)(s.col[ag] & 0xff) << (16 * ag + 8));

@@ -389,6 +389,12 @@ def _finish(name, family, art, static_board, aux, value_mapping, dim_names, metr
     raise ValueError("board of %dx%d cells exceeds SGW_MAX_CELLS" % (H, W))
   if not (1 <= max_iterations <= 65535):
     raise ValueError("max_iterations must be in [1, 65535]")
+  players = len(fields.get("agent_chars", ())) or 1
+  if max_iterations > 65535 - (players - 1):
+    # frame counts plays and the episode ends after the round in which it reaches max_iterations: up to max_iterations + A - 1,
+    # which the device state keeps in 16 bits
+    raise ValueError("max_iterations must be in [1, %d] with %d agents: a round of %d plays ends on a frame of up to "
+                     "max_iterations + %d, kept in 16 bits" % (65535 - (players - 1), players, players, players - 1))
   sp = N.Spec()
   K, M, A = len(dim_names), len(metric_names), len(start_cells)
   sp.family, sp.H, sp.W, sp.K, sp.M, sp.A = family, H, W, K, M, A
@@ -674,12 +680,16 @@ def _firemaker_spec(kwargs):
       rel = (dist - 1) / (maxd - 1 + eps)
       spread.append((1 - rel) * p1)
       if inside: valid |= 1 << (adr * 3 + adc)
+  reload = 1 + 1 + int(cfg["STOP_BUTTON_PRESS_EFFECT_DURATION"])       # firemaker_ex_ma.py:664
+  if reload > 65535:
+    raise ValueError("firemaker_ex_ma: STOP_BUTTON_PRESS_EFFECT_DURATION = %r: the device state keeps the countdown in 16 bits "
+                     "(1 + 1 + duration <= 65535)" % (cfg["STOP_BUTTON_PRESS_EFFECT_DURATION"],))
   rv = lambda flag: list(cfg[flag].values())[0]
   params = [rv("AGENT_MOVEMENT_REWARD"), rv("AGENT_WORKSHOP_WORK_REWARD"), rv("AGENT_WORKSHOP_ENERGY_REWARD"),
             rv("SUPERVISOR_MOVEMENT_REWARD"), rv("SUPERVISOR_EXTERNAL_FIRE_REWARD"), rv("SUPERVISOR_TRESPASSING_REWARD"),
             rv("SUPERVISOR_STOP_BUTTON_REWARD"), rv("SUPERVISOR_WORKSHOP_REWARD"),
             float(cfg["FIRE_CONTINUATION_PROBABILITY"])] + spread + [float(valid),
-            float(1 + 1 + int(cfg["STOP_BUTTON_PRESS_EFFECT_DURATION"]))]
+            float(reload)]
   params += _mask_words([(a & (1 | 4 | 8)) == 0 for a in aux]) + _mask_words(territory)
   if radius > 2:                          # the WIDE kernels: radius, then p[|dr|][|dc|] for 0..4 x 0..4 (0.0 = out of range or the cell itself)
     wide = []

@@ -73,7 +73,7 @@ typedef struct sgw_spec {
   int32_t K;                 /* enabled reward dimensions (per agent; max over agents) */
   int32_t M;                 /* metrics per env */
   int32_t A;                 /* agents per env (1 unless multi-agent) */
-  int32_t max_iterations;
+  int32_t max_iterations;    /* 1 .. 65535 - (playing agents - 1): the state keeps the frame in 16 bits */
   int32_t start_cell[SGW_MAX_AGENTS];   /* row*W+col of each agent sprite in the art */
   int32_t action_lo, n_actions;         /* action range, used by the synthetic rollout */
   int32_t flags;
