@@ -121,6 +121,8 @@ def lib():
   L.sgw_step_shape.argtypes = [C.c_void_p]
   if hasattr(L, "sgw_step_rules"):                          # (an SGW_LIBRARY build from before the symbol)
     L.sgw_step_rules.argtypes = [C.c_void_p]
+  if hasattr(L, "sgw_step_fork"):                           # (as above)
+    L.sgw_step_fork.argtypes = [C.c_void_p]
   if hasattr(L, "sgw_step_lds_bytes"):                      # (an SGW_LIBRARY build from before the symbol: A/B runs against older builds)
     L.sgw_step_lds_bytes.argtypes = [C.c_void_p, C.c_void_p]
     L.sgw_step_lds_bytes.restype = C.c_int64
@@ -214,7 +216,7 @@ EXPORTS = [
     "sgw_destroy", "sgw_n_envs", "sgw_n_pad", "sgw_state_bytes", "sgw_set_episode_bits",
     "sgw_set_rng_state", "sgw_set_random_stream", "sgw_set_family_table", "sgw_pow_f64", "sgw_pow_selfcheck", "sgw_reset", "sgw_step", "sgw_step_n", "sgw_rollout", "sgw_replay", "sgw_group_create", "sgw_group_destroy", "sgw_group_step_n", "sgw_group_rollout", "sgw_read_returns", "sgw_fill_actions",
     "sgw_accumulate_returns", "sgw_observe", "sgw_derived_stats", "sgw_observe_layers", "sgw_state_layers", "sgw_view_bytes", "sgw_agent_views", "sgw_agent_layer_views", "sgw_state_words", "sgw_get_state", "sgw_set_state",
-    "sgw_step_shape", "sgw_step_rules", "sgw_layer_coords", "sgw_agent_layer_coords", "sgw_step_lds_bytes",
+    "sgw_step_shape", "sgw_step_rules", "sgw_step_fork", "sgw_layer_coords", "sgw_agent_layer_coords", "sgw_step_lds_bytes",
     "sgw_sizeof_episodes", "sgw_episode_scratch_bytes", "sgw_log_episodes",
     "sgw_seed_rng", "sgw_pcg64_from_seeds",
     "sgw_copy_envs", "sgw_out_row_bytes",

@@ -176,9 +176,10 @@ struct sgw_engine {
   GraphCache<1> graphs{256, 65536, " of the step launches"}, full_graphs{16, 0, ""};
   // sgw_policy_step_n: the 2T + 1 launches of one closed-loop call, in a cache of their own (they never evict sgw_step_n's): at most 64
   GraphCache<1> policy_graphs{64, 0, " of the policy and step launches"};
-  unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel, + 4 for the BigViews variant; bit 20 for a shaped kernel with compiled rules): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
+  unsigned lds_cap_raised; // bit KIND (+ 3 for the shaped step kernel, + 4 for the BigViews variant; bit 20 for a shaped kernel with compiled rules, bit 21 for k_step_fork): this engine's k_engine<F, KIND> may use more than 64 KiB of dynamic LDS (set once)
   int step_shape;          // 1 + the ShapedSteps entry whose kernel runs this engine's one-step launches, 0 = the generic kernel
   int step_rules;          // 1: that entry's kernel with the spec's rule set compiled in runs them (ShapedStep::Rules), 0: the entry's own family
+  int step_fork;           // 1: the one-step launches run k_step_fork (a state wave and an output wave per env-wave), see engine_step_fork
   // bumped by drop_graphs: a cache entry records its engines' epochs when it is seen and is stale once one moved
   unsigned long long arg_epoch;
 };
@@ -300,6 +301,7 @@ static long pow_selfcheck_run() {
 }
 static int engine_step_shape(const sgw_engine* e);      // (below the launch dispatch)
 static int engine_step_rules(const sgw_engine* e);
+static int engine_step_fork(const sgw_engine* e);
 
 static long pow_selfcheck() {
   static const long cached = pow_selfcheck_run();           // C++11: initialised once, thread-safe
@@ -394,6 +396,9 @@ int sgw_create(const sgw_spec* spec, int64_t n_envs, int64_t env_id_base, int de
   // ... and that kernel with the spec's whole rule set compiled in, when the shape's entry has one and the spec is exactly it;
   // SGW_GENERIC_RULES keeps the entry's own family
   e->step_rules = (e->step_shape > 0 && !getenv("SGW_GENERIC_RULES")) ? engine_step_rules(e) : 0;
+  // ... as a pair of waves per env-wave when the launch is small enough for the second wave to find an idle issue slot;
+  // SGW_NO_FORK keeps the one-wave kernel
+  e->step_fork = (e->step_rules > 0 && !getenv("SGW_NO_FORK")) ? engine_step_fork(e) : 0;
 
   const size_t tbytes = TABLE_BYTES;
   uint8_t host_tables[TABLE_BYTES];
@@ -459,6 +464,7 @@ int64_t sgw_n_pad(const sgw_engine* e) { return e ? e->n_pad : 0; }
 int sgw_state_words(const sgw_engine* e) { return e ? e->ks.words : 0; }
 int sgw_step_shape(const sgw_engine* e) { return e ? e->step_shape : 0; }
 int sgw_step_rules(const sgw_engine* e) { return e ? e->step_rules : 0; }
+int sgw_step_fork(const sgw_engine* e) { return e ? e->step_fork : 0; }
 int64_t sgw_state_bytes(const sgw_engine* e) { return e ? (int64_t)e->ks.words * e->n_pad * 8 : 0; }
 
 int sgw_set_episode_bits(sgw_engine* e, const uint8_t* bits_dev, int n_per_env, uint64_t seed) {
@@ -640,6 +646,18 @@ template <size_t I = 0> static int find_step_rules(const sgw_engine* e) {
 }
 static int engine_step_rules(const sgw_engine* e) { return find_step_rules(e); }
 
+// The forked step kernel (sgw_kernels.hpp k_step_fork) doubles the launch's wavefronts and reads the state twice: that pays
+// while a SIMD holds at most one env-wave, so that the second wave takes issue slots nobody uses.  A larger launch is bound by
+// HBM with many waves per SIMD already and keeps the one-wave kernel.  (DESIGN.md §4.1 has the sizes measured.)
+static int engine_step_fork(const sgw_engine* e) {
+#ifdef SGW_FORK_ANY_SIZE       // diagnostic build: the size sweep behind the rule below
+  return 1;
+#endif
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus <= 0) return 0;
+  return e->n_pad / WAVE <= 4ll * cus ? 1 : 0;
+}
+
 static int launch_kind(const KArgs& a) {                      // K_STEP reads the caller's actions only
   return a.mode == MODE_RESET ? K_RESET : ((a.T == 1 && a.actions) ? K_STEP : K_ROLLOUT);
 }
@@ -696,8 +714,8 @@ static int views_chunk_envs() {
 }
 struct LaunchPlan { size_t lds_bytes; unsigned blocks, threads; };
 // LDS plan + grid of k_engine<F, KIND> for these arguments (fills a.lp / a.need)
-template <class F, int KIND> static int plan_launch(const sgw_engine* e, KArgs& a, LaunchPlan& p) {
-  constexpr int EW = env_waves<F, KIND>(), NB = lds_buffers<F, KIND>();
+// (EW env-waves per workgroup with NB staging buffers each, `threads` threads: k_engine<F, KIND>'s, or k_step_fork's)
+template <class F> static int plan_launch_as(const sgw_engine* e, KArgs& a, LaunchPlan& p, const int EW, const int NB, const unsigned threads) {
   const long long n_waves = e->n_pad / WAVE;
   const int need = lds_need(a, F::LDS_SCRATCH_M), pa = F::PER_AGENT ? F::NA : 1;
   if ((need & (LN_VIEWS | LN_OBSVIEWS)) && (!has_views<F>::value || a.sp.view_total <= 0))
@@ -717,13 +735,17 @@ template <class F, int KIND> static int plan_launch(const sgw_engine* e, KArgs& 
   a.lp = lds_plan(a.sp.HW, a.sp.A, a.sp.K, a.sp.M, pa, need, vb, CS, VG); a.need = need;
   p.lds_bytes = lds_total_bytes(a.sp.HW, a.sp.A, a.sp.K, a.sp.M, pa, need, vb, F::LDS_EXTRA, EW, NB, CS, VG);
   p.blocks = (unsigned)((n_waves + EW - 1) / EW);
-  p.threads = (unsigned)wg_threads<F, KIND>();
+  p.threads = threads;
   // the bytes requested == the bytes the plan hands out (checked on every launch)
   if ((size_t)TABLE_BYTES + F::LDS_EXTRA + (size_t)EW * NB * a.lp.wave_bytes != p.lds_bytes || (F::LDS_EXTRA & 15) != 0 ||
       (a.lp.wave_bytes & 15) != 0 || (a.lp.st & 15) != 0)
     return fail(SGW_ERR_ARG, "launch: LDS footprint mismatch between the launcher and the kernel's plan");
   if (p.lds_bytes > 160 * 1024) return fail(SGW_ERR_UNSUPPORTED, "launch: the requested outputs need more than 160 KiB of LDS per workgroup");
   return SGW_OK;
+}
+
+template <class F, int KIND> static int plan_launch(const sgw_engine* e, KArgs& a, LaunchPlan& p) {
+  return plan_launch_as<F>(e, a, p, env_waves<F, KIND>(), lds_buffers<F, KIND>(), (unsigned)wg_threads<F, KIND>());
 }
 
 template <class F, int KIND, class SH = NoShape, bool RULES = false> static int launch_as(sgw_engine* e, KArgs& a, hipStream_t st) {
@@ -743,6 +765,20 @@ template <class F, int KIND, class SH = NoShape, bool RULES = false> static int 
   return SGW_OK;
 }
 
+// one step by k_step_fork<RF, SH>: FORK_EW env-waves per workgroup, two wavefronts each
+template <class RF, class SH> static int launch_fork(sgw_engine* e, KArgs& a, hipStream_t st) {
+  LaunchPlan p;
+  int rc = plan_launch_as<RF>(e, a, p, FORK_EW, 1, (unsigned)FORK_THREADS);
+  if (rc) return rc;
+  constexpr unsigned bit = 1u << 21;
+  if (p.lds_bytes > 65536 && !(e->lds_cap_raised & bit)) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_fork<RF, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    e->lds_cap_raised |= bit;
+  }
+  hipLaunchKernelGGL((k_step_fork<RF, SH>), dim3(p.blocks), dim3(p.threads), p.lds_bytes, st, SGW_HOT_ARGS(a), a);
+  return SGW_OK;
+}
+
 // one step: the engine's shaped kernel when it has one (e->step_shape), the generic one otherwise
 template <class F, size_t I = 0> static int launch_step(sgw_engine* e, KArgs& a, hipStream_t st) {
   if constexpr (I < std::tuple_size<ShapedSteps>::value) {
@@ -750,6 +786,7 @@ template <class F, size_t I = 0> static int launch_step(sgw_engine* e, KArgs& a,
     if constexpr (std::is_same<typename E::Family, F>::value) {
       if (e->step_shape == (int)I + 1) {
         if constexpr (!std::is_void<typename E::Rules>::value) {
+          if (e->step_fork) return launch_fork<typename E::Rules, typename E::Shape>(e, a, st);
           if (e->step_rules) return launch_as<typename E::Rules, K_STEP, typename E::Shape, true>(e, a, st);
         }
         return launch_as<F, K_STEP, typename E::Shape>(e, a, st);

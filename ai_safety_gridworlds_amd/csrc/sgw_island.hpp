@@ -241,7 +241,10 @@ struct IslandT : IslandDefs {
   // One Engine.play(action).  Returns the plot's discount (0.0 when an entity terminated the episode).
   // Written select-style (`r[X] += cond ? v : 0.0`): every add_reward of the reference is one add in
   // the reference's order (IN:455-571); adding +0.0 where the reference adds nothing is exact.
-  template <class R> static __device__ __forceinline__ double play_rules(const R& rules, State& s, const int action, const Lds& l, double (&r)[NU]) {
+  // REGROW = false leaves the drapes' regrowth pass out: for a caller that keeps only outputs of the step other than `metrics`
+  // (nothing else of a step reads what the pass writes, d_avail / f_avail / d_frac / f_frac: k_step_fork's output wave).
+  template <class R, bool REGROW = true>
+  static __device__ __forceinline__ double play_rules(const R& rules, State& s, const int action, const Lds& l, double (&r)[NU]) {
     const int W = rules.W();
     const bool oversat = rules.oversat(), prop = rules.prop();
     const bool death = rules.death(), sustain = rules.sustain();
@@ -332,6 +335,7 @@ struct IslandT : IslandDefs {
         }
       }
     }
+    if constexpr (REGROW) {
     // DrinkDrape / FoodDrape regrowth (IN:638-657, 682-701).  Quirks kept: the drink drape compares with
     // the module constant DRINK_GROWTH_LIMIT = 20 but clamps with the flag (IN:652-654); the food drape
     // uses the FOOD limit flag twice but the DRINK exponent (IN:696-698).
@@ -360,6 +364,7 @@ struct IslandT : IslandDefs {
       s.f_avail = k ? fl : s.f_avail; s.f_frac = k ? fr : s.f_frac;
       s.d_avail = k ? s.d_avail : fl; s.d_frac = k ? s.d_frac : fr;
       pend &= k ? ~2 : ~1;
+    }
     }
     return terminated ? 0.0 : 1.0;
   }
@@ -524,6 +529,14 @@ struct IslandL9Default : IslandPacked {
   static __device__ double play(State& s, const int (&actions)[1], const KArgs& a, const Lds& l, double (&r)[NU], long long) {
     return play_rules(Rules(a, l), s, actions[0], l, r);
   }
+  // the play without its regrowth pass (k_step_fork's output wave, sgw_kernels.hpp)
+  static __device__ double play_events(State& s, const int (&actions)[1], const KArgs& a, const Lds& l, double (&r)[NU], long long) {
+    return play_rules<Rules, false>(Rules(a, l), s, actions[0], l, r);
+  }
+  // the pow tables staged by a workgroup of NT threads (k_step_fork's is not ENV_WAVES_MAX * WAVE)
+  template <int NT> struct CtxN { SgwPowStageT<NT> pow; };
+  template <int NT> static __device__ void init_issue_n(CtxN<NT>& cx) { sgw_pow_stage_issue<NT>(cx.pow); }
+  template <int NT> static __device__ void init_ctx_n(CtxN<NT>& cx, const Lds& l) { sgw_pow_stage_commit<NT>(cx.pow, l.extra); }
 };
 
 

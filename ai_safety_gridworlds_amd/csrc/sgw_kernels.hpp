@@ -1056,6 +1056,142 @@ __global__ SGW_OCC __launch_bounds__((wg_threads<F, KIND>())) void k_engine(uint
   engine_body<F, KIND, SGW_KARGS_OFFSET + (int)sizeof(KArgs)>(a, (long long)blockIdx.x, SGW_KARGS_OFFSET);
 }
 
+// ---- the forked one-step kernel: a state wave and an output wave per env-wave, no hand-over ---------------------------------
+// A one-step launch of at most one env-wave per SIMD (the headline: 65 536 envs = 1 024 waves on 1 024 SIMDs) is one serial
+// chain per wave, and a lone wave leaves more than half of its SIMD's issue slots idle.  Here every env-wave is TWO wavefronts
+// that load the same old state and the same action and run the same deterministic rules, so both hold the same bits:
+//   the S wave (waves [0, EW) of the workgroup) keeps the state side: returns accumulation and the state store;
+//   the O wave (waves [EW, 2 EW)) keeps the output side: board / reward / ... staging, the drains and the small direct stores.
+// Nothing passes from one to the other (the hand-over form, a second wave that waits for the first one's play behind a barrier,
+// is the pair that was measured and lost, see pipelined() above).  The O wave leaves the rules' regrowth pass out unless
+// `metrics` is asked for: no other output reads what the pass writes.  The LDS plan is k_engine's for EW env-waves: the O wave
+// owns board / vec_r / vec_c / vec_m and the small-output regions of its env-wave, the S wave vec_a.
+// F provides play_events (the play without the regrowth pass) and the pow stage for a workgroup of any size (CtxN / init_issue_n / init_ctx_n).
+#ifndef SGW_FORK_EW
+#define SGW_FORK_EW 2        // env-waves per workgroup: 2 (256 threads, one wave per SIMD) or 4 (512 threads); measured at the headline:
+                             // 4.87-4.91 us per launch with 2, 5.29-5.34 with 4, the one-wave kernel 5.17-5.19
+#endif
+constexpr int FORK_EW = SGW_FORK_EW, FORK_THREADS = 2 * FORK_EW * WAVE;
+static_assert(FORK_EW == 2 || FORK_EW == 4, "");
+enum { ROLE_STATE = 0, ROLE_OUTPUT = 1 };
+
+// one role's part of the step, after the staging barrier: straight-line but for the auto-reset / play branch
+template <class F, int ROLE>
+__device__ __forceinline__ void fork_role(typename F::State& s, const int (&action)[F::NA], const KArgs& a, const Lds& l, const long long wave_id,
+                                          const long long env0, const int lane, const bool real, const unsigned kargs_off) {
+  const long long env = env0 + lane;
+  double r[F::NU];
+#pragma unroll
+  for (int u = 0; u < F::NU; ++u) r[u] = 0.0;
+  double discount = __longlong_as_double(0x7ff8000000000000LL);   // None at FIRST
+  bool over_now = false;
+  if (s.step_type >= ST_LAST) {
+    F::pre_autoreset(s, a, action);
+    F::begin_episode(s, a, l, env, a.env_id_base + env);
+  } else {
+    if constexpr (ROLE == ROLE_STATE) {
+      discount = F::play(s, action, a, l, r, env);
+    } else {
+      // wave-uniform: `metrics` shows d_avail / f_avail, so a launch that asks for it plays the whole rules here too
+      if (a.need & LN_METRICS) discount = F::play(s, action, a, l, r, env);
+      else discount = F::play_events(s, action, a, l, r, env);
+    }
+    const bool over = (discount == 0.0) || (s.frame >= a.sp.max_iterations);
+    s.step_type = over ? ST_LAST : ST_MID;
+    if (over && s.term == TERM_NONE4) s.term = SGW_MAX_STEPS;
+#pragma unroll
+    for (int u = 0; u < F::NU; ++u) s.cum[u] += r[u];
+    over_now = over;
+  }
+  SGW_STAMP(a, 2);
+  if constexpr (ROLE == ROLE_STATE) {
+    F::store(s, a, env);
+    SGW_STAMP(a, 4);
+    if (a.need & LN_RETURNS) {
+      if (__ballot(over_now && real) != 0ull) {                    // wave-uniform
+        const int C = a.sp.A * a.sp.K + 1;
+        const StageRow row_a(l.vec_a, l.trash, lane, C);
+#pragma unroll
+        for (int u = 0; u < F::NU; ++u) *row_a.cell(F::slot(a.sp, u)) = (over_now && real) ? s.cum[u] : 0.0;
+        l.vec_a[lane * C + C - 1] = (over_now && real) ? 1.0 : 0.0;
+        lds_wave_sync();
+        accumulate_returns(a, l, wave_id, lane);
+      }
+    }
+    SGW_STAMP(a, 5);
+  } else {
+    emit_stage<F, false, true>(s, r, discount, a, l, lane);
+    emit_decodes_direct<F>(s, a, env0, lane, 0, true, kargs_off);
+    lds_wave_sync();
+    emit_drain<F, false, true>(a, l, env0, lane, 0, true, true);
+    SGW_STAMP(a, 11);
+    emit_small_direct<F>(s, discount, a, l, env0, lane, 0, true);
+    SGW_STAMP(a, 3);
+  }
+  SGW_STAMP_RT(a, 7);
+}
+
+template <class F, int TOUCH_END>
+__device__ __forceinline__ void fork_body(const KArgs& a, const long long block, const unsigned kargs_off) {
+  static_assert(!F::COOPERATIVE && F::WAVES == 1 && !F::PER_AGENT && F::NA == 1 && !has_views<F>::value && !cum_in_lds<F>::value &&
+                !step_rereads<F>::value && !has_idle_round<F>::value && !has_board_part<F>::value && F::LDS_EXTRA == SGW_POW_LDS_BYTES /* the pow tables and nothing init_args would fill */, "");
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  constexpr int EW = FORK_EW, NT = FORK_THREADS;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const bool out_role = wave_in_wg >= EW;
+  const int wv = out_role ? wave_in_wg - EW : wave_in_wg;          // env-wave within the workgroup
+  const long long wave_id = block * EW + wv;
+  const long long env0 = wave_id * WAVE;
+  const long long env = env0 + lane;
+  const bool real = env < a.n_envs;
+  const bool wave_live = env0 < a.n_pad;                 // the last workgroup may hold fewer than EW env-waves
+
+  SGW_STAMP_RT(a, 6);
+  SGW_STAMP(a, 0);
+  // k_engine's prologue in k_engine's order, the same in both roles and with no branch up to the barrier: level tables, state,
+  // action, pow pieces, kernarg touch, then the LDS commits (a dead env-wave loads env-wave 0's data)
+  TableStage ts;
+  lds_tables_issue<NT>(ts, a.tables);
+  const Lds l = lds_carve(smem, a.lp, F::LDS_EXTRA, wv);
+  typename F::template CtxN<NT> cx;
+  typename F::State s;
+  F::load(s, a, wave_live ? env : (long long)lane);
+  int action[1];
+  {
+    const bool have = a.actions != nullptr && real;
+    const int8_t* ap = have ? a.actions + env : reinterpret_cast<const int8_t*>(a.tables);
+    const int v = (int)*ap;
+    action[0] = have ? v : 0;
+  }
+  F::template init_issue_n<NT>(cx);
+  const uint32_t touch = kernarg_touch_issue<TOUCH_END>();
+  lds_tables_commit<NT>(ts, smem);
+  F::template init_ctx_n<NT>(cx, l);
+  kernarg_touch_settle(touch);
+  // THE ordering the fork rests on: every wave's loads of the OLD state have returned before any S wave stores the new one.  An
+  // env-wave's two waves are in one workgroup, and __syncthreads() is `s_waitcnt vmcnt(0)` + s_barrier: each wave drains its own
+  // loads before it arrives, so when the barrier opens all of the workgroup's state loads are back.  No store stands ahead of it.
+  // (tests/test_step_fork_asm.py reads both off the assembly.)
+  __syncthreads();
+  if (!wave_live) return;
+  SGW_STAMP(a, 1);
+  if (out_role) fork_role<F, ROLE_OUTPUT>(s, action, a, l, wave_id, env0, lane, real, kargs_off);
+  else fork_role<F, ROLE_STATE>(s, action, a, l, wave_id, env0, lane, real, kargs_off);
+}
+
+// the same parameter list as k_engine (SGW_HOT_ARGS, then KArgs: SGW_KARGS_OFFSET and the preload count hold); a kernel of its
+// own name, not a k_engine instantiation
+template <class F, class SH>
+__global__ SGW_OCC __launch_bounds__(FORK_THREADS) void k_step_fork(uint64_t* hot_state, const uint8_t* hot_tables, const int8_t* hot_actions,
+                                                                    long long hot_n_pad, long long hot_n_envs, int hot_words, const KArgs a_in) {
+  KArgs a = a_in;
+  a.state = hot_state; a.tables = hot_tables; a.actions = hot_actions; a.n_pad = hot_n_pad; a.n_envs = hot_n_envs; a.sp.words = hot_words;
+  static_assert(SH::ON && SH::NSLOT == F::NU, "");
+  SH::apply(a.sp);
+  fork_body<F, SGW_KARGS_OFFSET + (int)sizeof(KArgs)>(a, (long long)blockIdx.x, SGW_KARGS_OFFSET);
+}
+
 // ---- heterogeneous launch: several engines (env families) in ONE grid --------------------------------------------------
 // A mixed suite sharded over one GPU (BASELINE config 5: island_navigation_ex + boat_race_ex + safe_interruptibility) is three
 // small launches otherwise -- 171 workgroups each on a 256-CU chip, three kernel boundaries per step.  Here workgroup b belongs

@@ -702,9 +702,16 @@ int sgw_step_shape(const sgw_engine* e);
  * SGW_GENERIC_RULES set in the environment at sgw_create keeps the shape-only kernel), 0 otherwise.  Same bytes either way. */
 int sgw_step_rules(const sgw_engine* e);
 
+/* 1 when those launches run the forked kernel: every env-wave as a state wave and an output wave that both run the rules and
+ * each keep one side of the result (chosen by sgw_create for an engine with sgw_step_rules' kernel whose launch has at most one
+ * env-wave per SIMD of its device; SGW_NO_FORK set in the environment at sgw_create keeps the one-wave kernel), 0 otherwise.
+ * Same bytes either way. */
+int sgw_step_fork(const sgw_engine* e);
+
 /* Dynamic LDS, in bytes per workgroup, that a one-step launch (sgw_step, sgw_step_n) of this engine asks for when `out` names
  * these outputs (NULL: none): what decides, with the kernel's registers, how many workgroups a CU keeps resident.  Nothing is
- * launched.  Negative = the error code such a launch would return. */
+ * launched.  Negative = the error code such a launch would return.  For an engine whose launches fork (sgw_step_fork) this is
+ * the one-wave kernel's figure; the forked kernel's workgroups hold half as many env-waves and ask for less. */
 int64_t sgw_step_lds_bytes(sgw_engine* e, const sgw_out* out);
 
 #ifdef __cplusplus

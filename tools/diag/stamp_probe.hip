@@ -3,7 +3,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DSGW_STAMPS -I. tools/diag/stamp_probe.hip -o /tmp/stamp_probe && /tmp/stamp_probe
 // It drives k_engine<IslandPacked, K_STEP> directly (same code as libsgw.so, compiled with stamps) on 65 536 envs, with the
 // bench's outputs and the episodic-return accumulators.  -DSGW_ISLAND_EW=n sets the env-waves per workgroup.
-//   stamp_probe [n_envs] [extra LDS bytes] [output mask] [kernel: 0 generic, 1 shaped (the level-9 shape of sgw_api.hip), 2 shaped with level 9's default rules compiled in]
+//   stamp_probe [n_envs] [extra LDS bytes] [output mask] [kernel: 0 generic, 1 shaped (the level-9 shape of sgw_api.hip), 2 shaped with level 9's default rules compiled in,
+//                                                          3 the forked kernel k_step_fork (phases and wave START / END per role; -DSGW_FORK_EW=n: env-waves per workgroup)]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -52,12 +53,13 @@ int main(int argc, char** argv) {
   std::vector<signed char> acts(T * n);
   unsigned x = 12345; for (auto& v : acts) { x = x * 1664525u + 1013904223u; v = (signed char)((x >> 24) % 5); }
   CK(hipMemcpy(d_act, acts.data(), T * n, hipMemcpyHostToDevice));
-  CK(hipMalloc(&d_stamps, (size_t)NWL * SGW_STAMP_SLOTS * 8)); CK(hipMalloc(&d_board, n * HW)); CK(hipMalloc(&d_reward, n * K * 8));
+  const int NBF = (NW + FORK_EW - 1) / FORK_EW, NWF = NBF * 2 * FORK_EW;      // the forked kernel: workgroups, wavefronts launched
+  CK(hipMalloc(&d_stamps, (size_t)std::max(NWL, NWF) * SGW_STAMP_SLOTS * 8)); CK(hipMalloc(&d_board, n * HW)); CK(hipMalloc(&d_reward, n * K * 8));
   CK(hipMalloc(&d_st, n)); CK(hipMalloc(&d_term, n)); CK(hipMalloc(&d_safety, n * 4)); CK(hipMalloc(&d_frame, n * 4));
   a.tables = d_tables; a.state = reinterpret_cast<uint64_t*>(d_state); a.n_pad = n; a.n_envs = n; a.mode = MODE_STEP; a.T = 1;
   const int omask = argc > 3 ? atoi(argv[3]) : 127;     // bit0 board, 1 reward, 2 step_type, 3 term_reason, 4 safety, 5 frame, 6 returns
   const int kernel = argc > 4 ? atoi(argv[4]) : 0;
-  const bool shaped = kernel != 0, rules = kernel == 2;
+  const bool shaped = kernel != 0, rules = kernel == 2, forked = kernel == 3;
   using Shape = StepShape<6, 8, 10, 0, 1, 2, 3, -1, 4, 5, 6, 7, 8, 9, -1>;
   if (shaped && !Shape::matches(sp)) { printf("the probe's spec does not match the shape\n"); return 1; }
   if (omask & 1) a.out.board = d_board;
@@ -74,8 +76,60 @@ int main(int argc, char** argv) {
   a.sgw_stamps = d_stamps;
   a.lp = lds_plan(HW, 1, K, 9, 1, lds_need(a, false), 0); a.need = lds_need(a, false);
   const size_t lds = lds_total_bytes(HW, 1, K, 9, 1, lds_need(a, false), 0, Fam::LDS_EXTRA, EW, 1) + (argc > 2 ? atoll(argv[2]) : 0);
-  printf("n %lld, %d env-waves per workgroup, dynamic LDS %zu bytes per workgroup, output mask %d, %s kernel\n", n, EW, lds, omask,
-         rules ? "shaped, compiled-rules" : shaped ? "shaped" : "generic");
+  const size_t lds_fork = lds_total_bytes(HW, 1, K, 9, 1, lds_need(a, false), 0, Fam::LDS_EXTRA, FORK_EW, 1) + (argc > 2 ? atoll(argv[2]) : 0);
+  printf("n %lld, %d env-waves per workgroup, dynamic LDS %zu bytes per workgroup, output mask %d, %s kernel\n", n, forked ? FORK_EW : EW,
+         forked ? lds_fork : lds, omask, forked ? "forked (state wave + output wave), compiled-rules" : rules ? "shaped, compiled-rules" : shaped ? "shaped" : "generic");
+  if (forked) {
+    // wavefront g = workgroup * 2 FORK_EW + w: w < FORK_EW the state wave of env-wave w, the others the output waves
+    const int S = SGW_STAMP_SLOTS;
+    std::vector<unsigned long long> h((size_t)NWF * S);
+    struct Phase { int role, from, to; const char* name; };
+    const Phase ph[] = {{0, 0, 1, "S: issue loads -> state+tables arrived"}, {0, 1, 2, "S: play (rules, regrowth included)"},
+                        {0, 2, 4, "S: state stores issued"}, {0, 4, 5, "S: returns staging + accumulation"},
+                        {1, 0, 1, "O: issue loads -> state+tables arrived"}, {1, 1, 2, "O: play (rules without the regrowth pass)"},
+                        {1, 2, 9, "O: board stage (LDS)"}, {1, 9, 10, "O: reward stage (LDS)"},
+                        {1, 10, 11, "O: wave sync + board/reward drains"}, {1, 11, 3, "O: small direct stores"}};
+    constexpr int NPF = (int)(sizeof(ph) / sizeof(ph[0]));
+    double accf[NPF] = {0}; int cntf = 0;
+    std::vector<double> st[2], en[2];
+    for (int t = 0; t < T; ++t) {
+      a.actions = d_act + t * n;
+      hipLaunchKernelGGL((k_step_fork<IslandL9Default, Shape>), dim3(NBF), dim3(FORK_THREADS), lds_fork, 0, SGW_HOT_ARGS(a), a);
+      if (t >= 100 && t % 10 == 0) {
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(h.data(), d_stamps, h.size() * 8, hipMemcpyDeviceToHost));
+        auto live = [&](int g) { return (long long)(g / (2 * FORK_EW)) * FORK_EW + (g % FORK_EW) < NW; };
+        for (int k = 0; k < NPF; ++k) {
+          double sum = 0; int m = 0;
+          for (int g = 0; g < NWF; ++g)
+            if (live(g) && (g % (2 * FORK_EW) >= FORK_EW) == (ph[k].role == 1)) { sum += (double)(h[(size_t)g * S + ph[k].to] - h[(size_t)g * S + ph[k].from]); ++m; }
+          accf[k] += sum / m;
+        }
+        ++cntf;
+        unsigned long long r0 = ~0ull;
+        for (int g = 0; g < NWF; ++g) if (live(g)) r0 = std::min(r0, h[(size_t)g * S + 6]);
+        for (int g = 0; g < NWF; ++g) {
+          if (!live(g)) continue;
+          const int role = g % (2 * FORK_EW) >= FORK_EW;
+          st[role].push_back((double)(h[(size_t)g * S + 6] - r0) * 0.01); en[role].push_back((double)(h[(size_t)g * S + 7] - r0) * 0.01);
+        }
+      }
+    }
+    CK(hipDeviceSynchronize());
+    printf("mean shader cycles per wave and role (s_memtime ticks; 2.4 GHz nominal)\n");
+    double tot[2] = {0, 0};
+    for (int k = 0; k < NPF; ++k) { printf("  %-48s %9.0f cycles  %6.2f us\n", ph[k].name, accf[k] / cntf, accf[k] / cntf / 2400.0); tot[ph[k].role] += accf[k] / cntf; }
+    printf("  %-48s %9.0f cycles\n  %-48s %9.0f cycles\n", "S wave, total", tot[0], "O wave, total", tot[1]);
+    auto pctf = [](std::vector<double>& v, double q) { return v[(size_t)(q * (v.size() - 1))]; };
+    for (int role = 0; role < 2; ++role) {
+      std::sort(st[role].begin(), st[role].end()); std::sort(en[role].begin(), en[role].end());
+      printf("%c wave START after the launch's first wave (us, s_memrealtime): p10 %.2f p50 %.2f p90 %.2f p99 %.2f max %.2f\n", "SO"[role],
+             pctf(st[role], .1), pctf(st[role], .5), pctf(st[role], .9), pctf(st[role], .99), st[role].back());
+      printf("%c wave END   after the launch's first wave (us):                p10 %.2f p50 %.2f p90 %.2f p99 %.2f max %.2f\n", "SO"[role],
+             pctf(en[role], .1), pctf(en[role], .5), pctf(en[role], .9), pctf(en[role], .99), en[role].back());
+    }
+    return 0;
+  }
   const int S = SGW_STAMP_SLOTS;
   std::vector<unsigned long long> h((size_t)NWL * S);
   std::vector<double> starts, ends;
