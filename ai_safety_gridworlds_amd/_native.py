@@ -193,6 +193,14 @@ def lib():
     L.sgw_policy_accumulate.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sgw_policy_apply.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+  if hasattr(L, "sgw_policy_sample"):                       # (as above: an older SGW_LIBRARY build has no softmax policies)
+    L.sgw_policy_sample.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sgw_policy_sample_step_n.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_float, C.c_void_p, C.c_int, C.c_int, C.POINTER(Out), C.c_void_p,
+                                           C.c_int, C.c_void_p]
+    L.sgw_policy_probs.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
+    L.sgw_policy_accumulate_softmax.argtypes = [C.c_void_p, C.POINTER(Policy), C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
   if L.sgw_abi_version() != ABI_VERSION:
     raise SgwError("libsgw.so ABI %d != binding ABI %d" % (L.sgw_abi_version(), ABI_VERSION))
   if L.sgw_sizeof_spec() != C.sizeof(Spec) or L.sgw_sizeof_out() != C.sizeof(Out):
@@ -224,7 +232,8 @@ EXPORTS = [
     "sgw_sizeof_policy", "sgw_policy_act", "sgw_policy_step_n",
     "sgw_simulate_moves", "sgw_fold_q_values",
     "sgw_sizeof_td", "sgw_td_targets",
-    "sgw_policy_scores", "sgw_policy_accumulate", "sgw_policy_apply"]
+    "sgw_policy_scores", "sgw_policy_accumulate", "sgw_policy_apply",
+    "sgw_policy_sample", "sgw_policy_sample_step_n", "sgw_policy_probs", "sgw_policy_accumulate_softmax"]
 
 
 def check(rc, what=""):

@@ -38,6 +38,7 @@
 #include "sgw_whatif.hpp"
 #include "sgw_targets.hpp"
 #include "sgw_learn.hpp"
+#include "sgw_softmax.hpp"
 
 using namespace sgw;
 
@@ -84,9 +85,11 @@ template <int N> struct GraphKey {
   const void* obs0;
   unsigned long long epochs[N];
   int n, T, write_every, accumulate, has_out;
+  int sampled;                                  // sgw_policy_sample_step_n: 1, and its beta2 (a greedy call never shares a sampled call's graph)
+  float beta2;
   bool same(const GraphKey& o) const {
     if (actions[0] != o.actions[0] || n != o.n || T != o.T || write_every != o.write_every || accumulate != o.accumulate ||
-        has_out != o.has_out) return false;
+        has_out != o.has_out || sampled != o.sampled || memcmp(&beta2, &o.beta2, sizeof(beta2)) != 0) return false;
     return memcmp(actions, o.actions, sizeof(actions[0]) * n) == 0 && memcmp(outs, o.outs, sizeof(sgw_out) * n) == 0 &&
            memcmp(&ex, &o.ex, sizeof(ex)) == 0 && memcmp(&pol, &o.pol, sizeof(pol)) == 0 && obs0 == o.obs0;
   }
@@ -1659,47 +1662,48 @@ static int policy_plan(const sgw_engine* e, const sgw_policy* p, const char* who
   return SGW_OK;
 }
 
-static int policy_launch(const sgw_engine* e, PolicyLaunch& L, const uint8_t* obs, long long t, int8_t* actions, hipStream_t st) {
+// sampled: k_policy_sample (sgw_softmax.hpp) with beta2 in place of the greedy k_policy_act; the same grid, threads and LDS
+static int policy_launch(const sgw_engine* e, PolicyLaunch& L, const uint8_t* obs, long long t, int8_t* actions, hipStream_t st,
+                         bool sampled = false, float beta2 = 0.0f) {
   if (((uintptr_t)obs) & 15) return fail(SGW_ERR_ARG, "policy: the observation rows must be 16-byte aligned (they move as 16-byte accesses)");
   if (L.blocks == 0) return SGW_OK;
   L.a.obs = obs; L.a.t = t; L.a.actions = actions;
   HIP_TRY(hipSetDevice(e->device));
-  hipLaunchKernelGGL(k_policy_act, dim3(L.blocks), dim3(L.threads), L.lds, st, L.a);
+  if (sampled) {
+    SampleArgs s; memset(&s, 0, sizeof(s));
+    s.p = L.a; s.beta2 = beta2;
+    hipLaunchKernelGGL(k_policy_sample, dim3(L.blocks), dim3(L.threads), L.lds, st, s);
+  } else {
+    hipLaunchKernelGGL(k_policy_act, dim3(L.blocks), dim3(L.threads), L.lds, st, L.a);
+  }
   HIP_TRY(hipGetLastError());
   return SGW_OK;
 }
 
-extern "C" {
+// beta2 = inverse temperature * log2(e): finite and >= 0
+static bool beta2_ok(float beta2) { return beta2 >= 0.0f && beta2 <= 3.4028234663852886e38f; }
 
-int sgw_sizeof_policy(void) { return (int)sizeof(sgw_policy); }
-
-int sgw_policy_act(sgw_engine* e, const sgw_policy* p, const uint8_t* obs_dev, int64_t t, int8_t* actions_dev, void* stream) {
-  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_act: null engine");
-  if (!obs_dev || !actions_dev) return fail(SGW_ERR_ARG, "sgw_policy_act: null observation or actions");
+// sgw_policy_step_n and sgw_policy_sample_step_n: the 2T + 1 launch chain, the acting launch greedy or sampled
+static int policy_step_chain(sgw_engine* e, const sgw_policy* p, bool sampled, float beta2, const uint8_t* obs0_dev, int T, int write_every,
+                             const sgw_out* out, int8_t* actions_out_dev, int accumulate, void* stream, const char* who) {
+  if (!e) return fail(SGW_ERR_ARG, "%s: null engine", who);
+  if (T < 1) return fail(SGW_ERR_ARG, "%s: T < 1", who);
+  if (!obs0_dev || !actions_out_dev || !out) return fail(SGW_ERR_ARG, "%s: obs0, out and actions_out are required", who);
+  if (sampled && !beta2_ok(beta2)) return fail(SGW_ERR_ARG, "%s: beta2 must be finite and >= 0", who);
   PolicyLaunch L;
-  const int rc = policy_plan(e, p, "sgw_policy_act", L);
-  if (rc) return rc;
-  return policy_launch(e, L, obs_dev, (long long)t, actions_dev, (hipStream_t)stream);
-}
-
-int sgw_policy_step_n(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, int T, int write_every, const sgw_out* out,
-                      int8_t* actions_out_dev, int accumulate, void* stream) {
-  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_step_n: null engine");
-  if (T < 1) return fail(SGW_ERR_ARG, "sgw_policy_step_n: T < 1");
-  if (!obs0_dev || !actions_out_dev || !out) return fail(SGW_ERR_ARG, "sgw_policy_step_n: obs0, out and actions_out are required");
-  PolicyLaunch L;
-  int rc = policy_plan(e, p, "sgw_policy_step_n", L);
+  int rc = policy_plan(e, p, who, L);
   if (rc) return rc;
   const bool from_views = p->source == SGW_POLICY_VIEWS;
   const uint8_t* produced = from_views ? out->views : out->board;         // what a step leaves for the next act
-  if (!produced) return fail(SGW_ERR_ARG, "sgw_policy_step_n: the policy's source (%s) is not among the outputs", from_views ? "views" : "board");
+  if (!produced)
+    return fail(SGW_ERR_ARG, from_views ? "%s: the policy's source (views) is not among the outputs" : "%s: the policy's source (board) is not among the outputs", who);
   const long long per_step = e->n_envs * e->spec.A, obs_step = e->n_pad * (long long)L.a.row_bytes;
   const hipStream_t st = (hipStream_t)stream;
   auto launches = [&](hipStream_t s) -> int {
     for (int t = 0; t < T; ++t) {
       int8_t* row = actions_out_dev + (long long)t * per_step;
       const uint8_t* obs = t == 0 ? obs0_dev : (write_every ? produced + (long long)(t - 1) * obs_step : produced);
-      int r = policy_launch(e, L, obs, t, row, s);
+      int r = policy_launch(e, L, obs, t, row, s, sampled, beta2);
       if (r) return r;
       KArgs a;
       r = step_args(e, row, 1, 0, 0, 0, out, accumulate, a);
@@ -1717,8 +1721,42 @@ int sgw_policy_step_n(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_de
   GraphKey<1> key; memset(&key, 0, sizeof(key));
   key.actions[0] = actions_out_dev; key.epochs[0] = e->arg_epoch; key.pol = *p; key.obs0 = obs0_dev;
   key.n = 1; key.T = T; key.write_every = write_every != 0; key.accumulate = accumulate != 0; key.has_out = 1;
+  key.sampled = sampled ? 1 : 0; key.beta2 = sampled ? beta2 : 0.0f;
   key.outs[0] = *out;
-  return e->policy_graphs.run(e->graph_owner, key, 2LL * T + 1, launches, st, "sgw_policy_step_n");
+  return e->policy_graphs.run(e->graph_owner, key, 2LL * T + 1, launches, st, who);
+}
+
+extern "C" {
+
+int sgw_sizeof_policy(void) { return (int)sizeof(sgw_policy); }
+
+int sgw_policy_act(sgw_engine* e, const sgw_policy* p, const uint8_t* obs_dev, int64_t t, int8_t* actions_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_act: null engine");
+  if (!obs_dev || !actions_dev) return fail(SGW_ERR_ARG, "sgw_policy_act: null observation or actions");
+  PolicyLaunch L;
+  const int rc = policy_plan(e, p, "sgw_policy_act", L);
+  if (rc) return rc;
+  return policy_launch(e, L, obs_dev, (long long)t, actions_dev, (hipStream_t)stream);
+}
+
+int sgw_policy_step_n(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, int T, int write_every, const sgw_out* out,
+                      int8_t* actions_out_dev, int accumulate, void* stream) {
+  return policy_step_chain(e, p, false, 0.0f, obs0_dev, T, write_every, out, actions_out_dev, accumulate, stream, "sgw_policy_step_n");
+}
+
+int sgw_policy_sample(sgw_engine* e, const sgw_policy* p, float beta2, const uint8_t* obs_dev, int64_t t, int8_t* actions_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_sample: null engine");
+  if (!obs_dev || !actions_dev) return fail(SGW_ERR_ARG, "sgw_policy_sample: null observation or actions");
+  if (!beta2_ok(beta2)) return fail(SGW_ERR_ARG, "sgw_policy_sample: beta2 must be finite and >= 0");
+  PolicyLaunch L;
+  const int rc = policy_plan(e, p, "sgw_policy_sample", L);
+  if (rc) return rc;
+  return policy_launch(e, L, obs_dev, (long long)t, actions_dev, (hipStream_t)stream, true, beta2);
+}
+
+int sgw_policy_sample_step_n(sgw_engine* e, const sgw_policy* p, float beta2, const uint8_t* obs0_dev, int T, int write_every,
+                             const sgw_out* out, int8_t* actions_out_dev, int accumulate, void* stream) {
+  return policy_step_chain(e, p, true, beta2, obs0_dev, T, write_every, out, actions_out_dev, accumulate, stream, "sgw_policy_sample_step_n");
 }
 
 }  // extern "C"
@@ -1900,30 +1938,38 @@ int sgw_policy_scores(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_de
   return SGW_OK;
 }
 
-int sgw_policy_accumulate(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, const uint8_t* obs_dev, int64_t obs_rows, int T,
-                          const int8_t* actions_dev, const double* coef_dev, int frac_bits, int64_t* acc_weights_dev,
-                          int64_t* acc_bias_dev, void* stream) {
-  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: null engine");
-  if (T < 1) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: T < 1");
-  if (!actions_dev || !coef_dev || !acc_weights_dev) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: actions, coef and acc_weights are required");
-  if (frac_bits < 0 || frac_bits > 52) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: frac_bits outside 0..52");
+}  // extern "C"
+
+// The argument checks, slices and tiles of sgw_policy_accumulate and sgw_policy_accumulate_softmax.  blocks == 0: nothing
+// to launch.
+static int accumulate_plan(sgw_engine* e, const sgw_policy* p, const char* who, const uint8_t* obs0_dev, const uint8_t* obs_dev,
+                           int64_t obs_rows, int T, const int8_t* actions_dev, const double* coef_dev, int frac_bits, int64_t* acc_weights_dev,
+                           int64_t* acc_bias_dev, AccArgs& a, long long& blocks) {
+  blocks = 0;
+  if (!e) return fail(SGW_ERR_ARG, "%s: null engine", who);
+  if (T < 1) return fail(SGW_ERR_ARG, "%s: T < 1", who);
+  if (!actions_dev || !coef_dev || !acc_weights_dev) return fail(SGW_ERR_ARG, "%s: actions, coef and acc_weights are required", who);
+  if (frac_bits < 0 || frac_bits > 52) return fail(SGW_ERR_ARG, "%s: frac_bits outside 0..52", who);
   PolicyLaunch L;
-  int rc = policy_plan(e, p, "sgw_policy_accumulate", L);
+  int rc = policy_plan(e, p, who, L);
   if (rc) return rc;
-  rc = learn_observations(e, L, "sgw_policy_accumulate", obs0_dev, obs_dev, obs_rows, T - 1);   // O[T] is not read
+  rc = learn_observations(e, L, who, obs0_dev, obs_dev, obs_rows, T - 1);   // O[T] is not read
   if (rc) return rc;
   if (((uintptr_t)coef_dev | (uintptr_t)acc_weights_dev | (uintptr_t)acc_bias_dev) & 7)
-    return fail(SGW_ERR_ARG, "sgw_policy_accumulate: coef or an accumulator is not 8-byte aligned");
+    return fail(SGW_ERR_ARG, "%s: coef or an accumulator is not 8-byte aligned", who);
   const void* inputs[] = {obs0_dev, obs_dev, actions_dev, coef_dev, p->code_of, p->weights, p->bias, p->policy_of_env, p->step_dev};
   for (const void* in : inputs)
-    if (in && (in == acc_weights_dev || in == acc_bias_dev)) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: an accumulator aliases an input");
-  if (acc_weights_dev == acc_bias_dev) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: acc_weights and acc_bias are the same array");
-  if ((long long)T * e->n_envs >= (1LL << 32)) return fail(SGW_ERR_ARG, "sgw_policy_accumulate: T * n_envs >= 2^32 (an int64 sum could wrap)");
-  AccArgs a; memset(&a, 0, sizeof(a));
+    if (in && (in == acc_weights_dev || in == acc_bias_dev)) return fail(SGW_ERR_ARG, "%s: an accumulator aliases an input", who);
+  if (acc_weights_dev == acc_bias_dev) return fail(SGW_ERR_ARG, "%s: acc_weights and acc_bias are the same array", who);
+  if ((long long)T * e->n_envs >= (1LL << 32)) return fail(SGW_ERR_ARG, "%s: T * n_envs >= 2^32 (an int64 sum could wrap)", who);
+  memset(&a, 0, sizeof(a));
+  const int A = L.a.A, G = L.a.G, NA = L.a.n_actions, P = L.a.P;
+  // rows + code_of + (q[n_actions], p) per env + bins: under 64 KiB for every E <= 64 once the rows fit, so E is halved for the rows alone
+  static_assert(LEARN_MAX_ROW_LDS + 256 + 64 * (POLICY_MAX_ACTIONS + 1) * 4 + LEARN_MAX_BIN_LDS <= 64 * 1024,
+                "the tiles of k_policy_accumulate and k_policy_accumulate_softmax fit the default dynamic LDS");
   int E = 64;
   while (E > 16 && (long long)E * L.a.row_bytes > LEARN_MAX_ROW_LDS) E >>= 1;
-  if ((long long)E * L.a.row_bytes > LEARN_MAX_ROW_LDS) return fail(SGW_ERR_UNSUPPORTED, "sgw_policy_accumulate: the observation row is too long to stage");
-  const int A = L.a.A, G = L.a.G, NA = L.a.n_actions, P = L.a.P;
+  if ((long long)E * L.a.row_bytes > LEARN_MAX_ROW_LDS) return fail(SGW_ERR_UNSUPPORTED, "%s: the observation row is too long to stage", who);
   int max_c = 1;
   for (int ag = 0; ag < A; ++ag) max_c = L.a.c_a[ag] > max_c ? L.a.c_a[ag] : max_c;
   int R = max_c;                                                            // P > 1: no bins, one slice per agent
@@ -1947,9 +1993,76 @@ int sgw_policy_accumulate(sgw_engine* e, const sgw_policy* p, const uint8_t* obs
   a.n = e->n_envs; a.obs_rows = obs_rows; a.groups = groups; a.tiles = tiles; a.scale = ldexp(1.0, frac_bits);
   a.row_bytes = L.a.row_bytes; a.envs_per_block = E; a.A = A; a.P = P; a.G = G; a.C = L.a.C; a.n_actions = NA; a.action_lo = L.a.action_lo;
   a.R = R; a.blocks_per_slice = (int)per_slice;
-  const size_t lds = ((size_t)E * a.row_bytes + 15) / 16 * 16 + 256 + (size_t)E * 12 + (P == 1 ? ((size_t)R * G * NA + NA) * 8 : 0);
+  blocks = per_slice * slices;
+  return SGW_OK;
+}
+
+extern "C" {
+
+int sgw_policy_accumulate(sgw_engine* e, const sgw_policy* p, const uint8_t* obs0_dev, const uint8_t* obs_dev, int64_t obs_rows, int T,
+                          const int8_t* actions_dev, const double* coef_dev, int frac_bits, int64_t* acc_weights_dev,
+                          int64_t* acc_bias_dev, void* stream) {
+  AccArgs a;
+  long long blocks;
+  const int rc = accumulate_plan(e, p, "sgw_policy_accumulate", obs0_dev, obs_dev, obs_rows, T, actions_dev, coef_dev, frac_bits, acc_weights_dev,
+                                 acc_bias_dev, a, blocks);
+  if (rc || blocks == 0) return rc;
+  const size_t lds = ((size_t)a.envs_per_block * a.row_bytes + 15) / 16 * 16 + 256 + (size_t)a.envs_per_block * 12 +
+                     (a.P == 1 ? ((size_t)a.R * a.G * a.n_actions + a.n_actions) * 8 : 0);
   HIP_TRY(hipSetDevice(e->device));
-  hipLaunchKernelGGL(k_policy_accumulate, dim3((unsigned)(per_slice * slices)), dim3(LEARN_THREADS), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_policy_accumulate, dim3((unsigned)blocks), dim3(LEARN_THREADS), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+int sgw_policy_accumulate_softmax(sgw_engine* e, const sgw_policy* p, float beta2, const uint8_t* obs0_dev, const uint8_t* obs_dev,
+                                  int64_t obs_rows, int T, const int8_t* actions_dev, const double* coef_dev, int frac_bits,
+                                  int64_t* acc_weights_dev, int64_t* acc_bias_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_accumulate_softmax: null engine");
+  if (!beta2_ok(beta2)) return fail(SGW_ERR_ARG, "sgw_policy_accumulate_softmax: beta2 must be finite and >= 0");
+  SoftAccArgs s; memset(&s, 0, sizeof(s));
+  long long blocks;
+  const int rc = accumulate_plan(e, p, "sgw_policy_accumulate_softmax", obs0_dev, obs_dev, obs_rows, T, actions_dev, coef_dev, frac_bits,
+                                 acc_weights_dev, acc_bias_dev, s.a, blocks);
+  if (rc || blocks == 0) return rc;
+  s.weights = p->weights; s.bias = p->bias; s.beta2 = beta2;
+  const AccArgs& a = s.a;
+  const size_t E = (size_t)a.envs_per_block, NA = (size_t)a.n_actions;
+  const size_t lds = (E * a.row_bytes + 15) / 16 * 16 + 256 + E * NA * 4 + E * 4 + (a.P == 1 ? ((size_t)a.R * a.G * NA + NA) * 8 : 0);
+  // the bytes requested == the bytes the kernel's own layout hands out
+  if ((size_t)softmax_acc_lds(a.envs_per_block, a.row_bytes, a.n_actions, a.R, a.G, a.P == 1).total != lds || lds > 64 * 1024)
+    return fail(SGW_ERR_ARG, "sgw_policy_accumulate_softmax: LDS footprint mismatch between the launcher and the kernel's layout");
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_policy_accumulate_softmax, dim3((unsigned)blocks), dim3(LEARN_THREADS), lds, (hipStream_t)stream, s);
+  HIP_TRY(hipGetLastError());
+  return SGW_OK;
+}
+
+int sgw_policy_probs(sgw_engine* e, const sgw_policy* p, float beta2, const uint8_t* obs0_dev, const uint8_t* obs_dev, int64_t obs_rows, int T,
+                     const int8_t* actions_dev, float* probs_dev, double* p_chosen_dev, void* stream) {
+  if (!e) return fail(SGW_ERR_ARG, "sgw_policy_probs: null engine");
+  if (T < 0) return fail(SGW_ERR_ARG, "sgw_policy_probs: T < 0");
+  if (!beta2_ok(beta2)) return fail(SGW_ERR_ARG, "sgw_policy_probs: beta2 must be finite and >= 0");
+  if (!probs_dev && !p_chosen_dev) return fail(SGW_ERR_ARG, "sgw_policy_probs: no output");
+  if (p_chosen_dev && T > 0 && !actions_dev) return fail(SGW_ERR_ARG, "sgw_policy_probs: p_chosen needs actions");
+  PolicyLaunch L;
+  int rc = policy_plan(e, p, "sgw_policy_probs", L);
+  if (rc) return rc;
+  rc = learn_observations(e, L, "sgw_policy_probs", obs0_dev, obs_dev, obs_rows, T);
+  if (rc) return rc;
+  if ((((uintptr_t)probs_dev) & 3) || (((uintptr_t)p_chosen_dev) & 7)) return fail(SGW_ERR_ARG, "sgw_policy_probs: a misaligned output array");
+  const long long groups = L.blocks, blocks = groups * ((long long)T + 1);
+  if (blocks > 0x7fffffffLL) return fail(SGW_ERR_ARG, "sgw_policy_probs: too many (observation, env group) blocks for one launch");
+  if (blocks == 0) return SGW_OK;
+  ProbsArgs a; memset(&a, 0, sizeof(a));
+  a.obs0 = obs0_dev; a.obs = obs_dev; a.code_of = p->code_of; a.weights = p->weights; a.bias = p->bias; a.policy_of_env = p->policy_of_env;
+  a.actions = actions_dev; a.probs = probs_dev; a.p_chosen = T > 0 ? p_chosen_dev : nullptr;
+  a.n = e->n_envs; a.obs_rows = obs_rows; a.groups = groups; a.beta2 = beta2;
+  a.T = T; a.row_bytes = L.a.row_bytes; a.envs_per_block = L.a.envs_per_block; a.A = L.a.A; a.P = L.a.P; a.G = L.a.G; a.C = L.a.C;
+  a.n_actions = L.a.n_actions; a.action_lo = L.a.action_lo;
+  for (int ag = 0; ag < SGW_MAX_AGENTS; ++ag) { a.c_a[ag] = L.a.c_a[ag]; a.off_a[ag] = L.a.off_a[ag]; }
+  HIP_TRY(hipSetDevice(e->device));
+  hipLaunchKernelGGL(k_policy_probs, dim3((unsigned)blocks), dim3(L.threads), L.lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return SGW_OK;
 }

@@ -907,8 +907,12 @@ class BatchedEngine(object):
       out = self._act_out
     else:
       _require("act", "out", out, self.device, torch.int8, self.n_envs * self.spec.A, "[N, A]")
-    N.check(self._lib.sgw_policy_act(self._h, C.byref(policy.native()), obs.data_ptr(), int(t), out.data_ptr(), self._stream()),
-            "sgw_policy_act")
+    if policy.beta2 is not None:       # a softmax policy (TablePolicy.set_temperature): the sampling launch
+      N.check(self._lib.sgw_policy_sample(self._h, C.byref(policy.native()), float(policy.beta2), obs.data_ptr(), int(t), out.data_ptr(),
+                                          self._stream()), "sgw_policy_sample")
+    else:
+      N.check(self._lib.sgw_policy_act(self._h, C.byref(policy.native()), obs.data_ptr(), int(t), out.data_ptr(), self._stream()),
+              "sgw_policy_act")
     return out.reshape(self.n_envs, self.spec.A)
 
   def policy_step_n(self, policy, T, write_every=False, accumulate=False):
@@ -945,8 +949,13 @@ class BatchedEngine(object):
       side = self._obs0_side(policy)
       side.copy_(obs0)
       obs0 = side
-    N.check(self._lib.sgw_policy_step_n(self._h, C.byref(policy.native()), obs0.data_ptr(), T, 1 if write_every else 0, C.byref(self._out),
-                                        acts.data_ptr(), 1 if accumulate else 0, self._stream()), "sgw_policy_step_n")
+    if policy.beta2 is not None:       # a softmax policy: the same chain with the sampling launch (a graph of its own)
+      N.check(self._lib.sgw_policy_sample_step_n(self._h, C.byref(policy.native()), float(policy.beta2), obs0.data_ptr(), T, 1 if write_every else 0,
+                                                 C.byref(self._out), acts.data_ptr(), 1 if accumulate else 0, self._stream()),
+              "sgw_policy_sample_step_n")
+    else:
+      N.check(self._lib.sgw_policy_step_n(self._h, C.byref(policy.native()), obs0.data_ptr(), T, 1 if write_every else 0, C.byref(self._out),
+                                          acts.data_ptr(), 1 if accumulate else 0, self._stream()), "sgw_policy_step_n")
     res = self._views()
     res["actions"] = acts
     if keep_obs0:
@@ -1021,21 +1030,65 @@ class BatchedEngine(object):
     j the action played, acc_bias[p, a, j] += q and acc_weights[p, a, c, code(o[c]), j] += q for every cell c of the observation
     the action was chosen on.  Integer sums: the same bits whatever the order, run after run.  coef: float64 [T, N, A]; obs0 / obs
     / actions as for policy_scores (None: what the last policy_rollout left).  Calls add up until policy_apply(clear=True)."""
+    self._policy_accumulate(policy, coef, T, obs0, obs, actions, frac_bits, False, "policy_accumulate")
+
+  def policy_accumulate_softmax(self, policy, coef, T, obs0, obs=None, actions=None, frac_bits=24):
+    """policy_accumulate for a SOFTMAX policy (sgw_policy_accumulate_softmax: one launch, capturable): the score-function gradient.
+    Per transition with action a*, and for EVERY action j, q_j = quantise(coef * ((j == a*) - pi_j)) is added to acc_bias[p, a, j]
+    and to acc_weights[p, a, c, code(o[c]), j] for every cell c; pi is the policy's softmax at its temperature on the observation
+    the action was chosen on (policy_probs).  Transitions with an unknown table, an action out of range or a degenerate row (a
+    NaN or infinite top score) add nothing.  The true gradient of log pi carries one more factor beta2 * ln 2 = 1 / temperature:
+    fold it into lr.  The arguments are policy_accumulate's; the policy must have a temperature (set_temperature)."""
+    if policy.beta2 is None:
+      raise N.SgwError("policy_accumulate_softmax: the policy is greedy; give it a temperature (TablePolicy.set_temperature)")
+    self._policy_accumulate(policy, coef, T, obs0, obs, actions, frac_bits, True, "policy_accumulate_softmax")
+
+  def _policy_accumulate(self, policy, coef, T, obs0, obs, actions, frac_bits, softmax, what):
     T = int(T)
     if T < 1:
-      raise ValueError("policy_accumulate: T must be >= 1")
-    self._open("policy_accumulate")
+      raise ValueError("%s: T must be >= 1" % what)
+    self._open(what)
     frac_bits = int(frac_bits)
     if policy.acc_frac_bits is not None and policy.acc_frac_bits != frac_bits:
-      raise N.SgwError("policy_accumulate: the accumulators hold sums with frac_bits=%d; apply them (clear=True) before frac_bits=%d"
-                       % (policy.acc_frac_bits, frac_bits))
+      raise N.SgwError("%s: the accumulators hold sums with frac_bits=%d; apply them (clear=True) before frac_bits=%d"
+                       % (what, policy.acc_frac_bits, frac_bits))
     n, A = self.n_envs, self.spec.A
-    _require("policy_accumulate", "coef", coef, self.device, torch.float64, T * n * A, "[%d, %d, %d]" % (T, n, A))
-    p0, p1, rows, actions = self._learn_observations(policy, T, obs0, obs, actions, "policy_accumulate", "required")
-    N.check(self._lib.sgw_policy_accumulate(self._h, C.byref(policy.native()), p0, p1, rows, T, actions.data_ptr(), coef.data_ptr(), frac_bits,
-                                            policy.acc_weights.data_ptr(), policy.acc_bias.data_ptr(), self._stream()),
-            "sgw_policy_accumulate")
+    _require(what, "coef", coef, self.device, torch.float64, T * n * A, "[%d, %d, %d]" % (T, n, A))
+    p0, p1, rows, actions = self._learn_observations(policy, T, obs0, obs, actions, what, "required")
+    if softmax:
+      N.check(self._lib.sgw_policy_accumulate_softmax(self._h, C.byref(policy.native()), float(policy.beta2), p0, p1, rows, T, actions.data_ptr(),
+                                                      coef.data_ptr(), frac_bits, policy.acc_weights.data_ptr(), policy.acc_bias.data_ptr(),
+                                                      self._stream()), "sgw_policy_accumulate_softmax")
+    else:
+      N.check(self._lib.sgw_policy_accumulate(self._h, C.byref(policy.native()), p0, p1, rows, T, actions.data_ptr(), coef.data_ptr(), frac_bits,
+                                              policy.acc_weights.data_ptr(), policy.acc_bias.data_ptr(), self._stream()),
+              "sgw_policy_accumulate")
     policy.acc_frac_bits = frac_bits
+
+  def policy_probs(self, policy, T=0, obs0=None, obs=None, actions=None):
+    """The action probabilities of a SOFTMAX TablePolicy on the T + 1 observations O[0..T] of a closed-loop call (sgw_policy_probs:
+    one launch, no synchronisation, capturable): {"probs": float32 [T+1, N, A, n_actions], "p_chosen": float64 [T, N, A] (the
+    probability of the action played, with a tape)}.  The probabilities are the softmax's alone: epsilon-exploration is not folded
+    in.  Arguments, defaults and the persistent result tensors are policy_scores'.  There is no CPU path."""
+    T = int(T)
+    if T < 0:
+      raise ValueError("policy_probs: T must be >= 0")
+    if policy.beta2 is None:
+      raise N.SgwError("policy_probs: the policy is greedy; give it a temperature (TablePolicy.set_temperature)")
+    self._open("policy_probs")
+    p0, p1, rows, actions = self._learn_observations(policy, T, obs0, obs, actions, "policy_probs", "optional" if T > 0 else None)
+    n, A = self.n_envs, self.spec.A
+    probs, chosen = self._persistent("probs", (T, policy.n_actions), lambda: (
+        torch.zeros((T + 1, n, A, policy.n_actions), dtype=torch.float32, device=self.device),
+        torch.zeros((T, n, A), dtype=torch.float64, device=self.device)))
+    want_chosen = actions is not None and T > 0
+    N.check(self._lib.sgw_policy_probs(self._h, C.byref(policy.native()), float(policy.beta2), p0, p1, rows, T,
+                                       actions.data_ptr() if want_chosen else None, probs.data_ptr(), chosen.data_ptr() if want_chosen else None,
+                                       self._stream()), "sgw_policy_probs")
+    res = {"probs": probs}
+    if want_chosen:
+      res["p_chosen"] = chosen
+    return res
 
   def policy_apply(self, policy, lr, clear=True):
     """weights += lr * acc_weights * 2^-frac_bits (and the bias alike), in place, from ONE launch (sgw_policy_apply): per element
@@ -1072,6 +1125,48 @@ class BatchedEngine(object):
     self.policy_accumulate(policy, delta, T, None, frac_bits=frac_bits)
     self.policy_apply(policy, lr, clear=True)
     traj["delta"], traj["valid"] = delta, valid
+    return traj
+
+  def pg_learn(self, policy, T, gamma, lr, lam=1.0, critic=None, critic_lr=None, bootstrap_truncated=False, frac_bits=24):
+    """One iteration of REINFORCE / actor-critic with a SOFTMAX table policy (set_temperature) over T closed-loop steps of every
+    env, all on the device and on one stream:
+      1. policy_rollout(policy, T)                                  the sampled rollout, O[0] kept
+      2. with a critic (a greedy TablePolicy on the same source): policy_scores(critic, T), then
+         td_targets(T, gamma, lam=lam, values=vmax[1:], value0=vmax[0], scalar=True); coef = advantages
+      3. without: td_targets(T, gamma, lam=lam, scalar=True); coef = returns
+      4. coef = 0 where not valid
+      5. policy_accumulate_softmax(coef), policy_apply(lr)          lr carries the factor 1 / temperature of the true gradient
+      6. with critic_lr: the critic takes q_learn's steps 4 to 6 on the same rollout and tape: delta = (advantages + vmax[:-1]) -
+         chosen, 0 where not valid; policy_accumulate(critic, delta); policy_apply(critic, critic_lr)
+    Returns the rollout's dict with "coef" float64 [T, N, A] and "valid" bool [T, N, A] added.  There is no CPU path."""
+    T = int(T)
+    if policy.beta2 is None:
+      raise N.SgwError("pg_learn: the policy is greedy; give it a temperature (TablePolicy.set_temperature)")
+    if critic is not None and (critic.beta2 is not None or critic.source != policy.source or critic is policy):
+      raise N.SgwError("pg_learn: the critic must be another, greedy TablePolicy on the policy's source")
+    if critic_lr is not None and critic is None:
+      raise ValueError("pg_learn: critic_lr without a critic")
+    traj = self.policy_rollout(policy, T)
+    n, A = self.n_envs, self.spec.A
+    zero = torch.zeros((), dtype=torch.float64, device=self.device)
+    if critic is not None:
+      sc = self.policy_scores(critic, T)
+      vmax = sc["vmax"]
+      td = self.td_targets(T, gamma, lam=lam, values=vmax[1:], value0=vmax[0], bootstrap_truncated=bootstrap_truncated, scalar=True)
+      coef = td["advantages"].reshape(T, n, A)
+    else:
+      td = self.td_targets(T, gamma, lam=lam, bootstrap_truncated=bootstrap_truncated, scalar=True)
+      coef = td["returns"].reshape(T, n, A)
+    valid = td["valid"].reshape(T, n, A)
+    coef = torch.where(valid, coef, zero)
+    if critic_lr is not None:                      # before any table moves
+      delta = torch.where(valid, (coef + vmax[:-1]) - sc["chosen"], zero)
+    self.policy_accumulate_softmax(policy, coef, T, None, frac_bits=frac_bits)
+    self.policy_apply(policy, lr, clear=True)
+    if critic_lr is not None:
+      self.policy_accumulate(critic, delta, T, None, frac_bits=frac_bits)
+      self.policy_apply(critic, critic_lr, clear=True)
+    traj["coef"], traj["valid"] = coef, valid
     return traj
 
   # -- what each action would do (csrc/sgw_whatif.hpp) ----------------------------------------

@@ -19,6 +19,7 @@ The device tensors are owned by the policy and may be written at any time; their
 are meant to hit the graph cache (assign with copy_ / fill_, not by rebinding the attributes).
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -33,6 +34,22 @@ def explore_below_of(epsilon):
   if not (0.0 <= float(epsilon) <= 1.0):
     raise ValueError("epsilon must be in [0, 1]")
   return min(2 ** 32, int(float(epsilon) * 2 ** 32))
+
+
+LOG2_E = 1.4426950408889634
+
+
+def beta2_of(tau):
+  """temperature -> beta2, the np.float32 the softmax entry points take (inverse temperature * log2(e)); None stays None."""
+  if tau is None:
+    return None
+  tau = float(tau)
+  if not tau > 0.0:
+    raise ValueError("temperature must be > 0 (math.inf: uniform), or None for the greedy policy")
+  beta2 = 0.0 if math.isinf(tau) else LOG2_E / tau
+  if beta2 > float(np.finfo(np.float32).max):
+    raise ValueError("temperature %r is too small: beta2 overflows float32" % tau)
+  return np.float32(beta2)
 
 
 def policy_cells(spec, source):
@@ -78,6 +95,7 @@ class TablePolicy(object):
     self.weights = torch.zeros((self.n_policies, spec.A, cells, self.n_codes, self.n_actions), dtype=torch.float32, device=dev)
     self.bias = torch.zeros((self.n_policies, spec.A, self.n_actions), dtype=torch.float32, device=dev)
     self.policy_of_env = None
+    self.beta2 = None          # None: greedy; else the float32 inverse temperature * log2(e) of the softmax policy (set_temperature)
     self.step = torch.zeros(1, dtype=torch.int64, device=dev)
     self._struct = None
     self._acc = None          # (acc_weights, acc_bias): the int64 gradient sums, allocated on first use
@@ -107,6 +125,20 @@ class TablePolicy(object):
   def set_epsilon(self, epsilon):
     self.explore_below = explore_below_of(epsilon)
     self._struct = None
+
+  def set_temperature(self, tau):
+    """None: the greedy policy (the first maximum).  tau > 0: a SOFTMAX policy, pi_j proportional to exp(score[j] / tau), sampled on
+    the device by act / policy_step_n / policy_rollout (include/sgw.h fixes the arithmetic): beta2 = float32(log2(e) / tau).
+    math.inf: beta2 = 0, uniform over the finite scores.  epsilon-exploration still comes first.  Returns the policy."""
+    self.beta2 = beta2_of(tau)
+    return self
+
+  @property
+  def temperature(self):
+    """tau of set_temperature as beta2 restates it (None: greedy; inf for beta2 == 0)."""
+    if self.beta2 is None:
+      return None
+    return math.inf if self.beta2 == 0 else LOG2_E / float(self.beta2)
 
   def set_policy_of_env(self, index):
     """int32 [N]: the table of every env (None: table 0 everywhere).  An index outside 0 .. P-1 makes that env's actions 0."""

@@ -529,6 +529,63 @@ int sgw_policy_accumulate(sgw_engine* e, const sgw_policy* p, const uint8_t* obs
 int sgw_policy_apply(sgw_engine* e, const sgw_policy* p, double lr, int frac_bits, int64_t* acc_weights_dev,
                      int64_t* acc_bias_dev /* or NULL */, int flags, void* stream);
 
+/* SOFTMAX table policies: sampling inside the closed loop, the probabilities of a played rollout and the policy-gradient sums, over
+ * the same score vectors, in arithmetic fixed here (csrc/sgw_softmax.hpp holds the one definition; tests/softmax_ref.py restates
+ * it in numpy and the device reproduces it bit for bit).  Per (env, agent), score[0 .. NA), best and top (= score[best]) are
+ * exactly those of sgw_policy_act.  beta2 is a float32: inverse temperature times log2(e); it must be finite and >= 0 (SGW_ERR_ARG
+ * otherwise); 0 gives a uniform policy over the finite scores.
+ *   z_j   = (score[j] - top) * beta2            one float32 subtraction, then one float32 multiplication
+ *   w_j   = E(z_j)
+ *   E(z)  : if !(z >= -125.0f) -> +0.0f         (NaN included: a NaN or -inf score is never sampled)
+ *           k = rintf(z) (ties to even);  g = z - k          (exact, g in [-0.5, 0.5])
+ *           p = 1 + g*(c1 + g*(c2 + g*(c3 + g*(c4 + g*(c5 + g*c6)))))   Horner: every * and + one float32 operation, nothing fused
+ *           E = ldexpf(p, (int)k)               (exact: never subnormal)
+ *           c1..c6 = float32((ln 2)^i / i!) = 0x1.62e430p-1, 0x1.ebfbe0p-3, 0x1.c6b08ep-5, 0x1.3b2ab6p-7, 0x1.5d87fep-10, 0x1.430912p-13
+ *   total = 0.0; for j = 0..NA-1 in order: total = total + (double)w_j        one double addition each
+ *   degenerate iff !(total > 0.0)               (exactly when top is NaN or infinite)
+ *   pi_j  = (double)w_j / total                 one double division
+ * E is within 2^-21.9 (relative) of 2^z on [-125, 0]; its smallest non-zero value is 2^-125; it is not monotone in its last bit,
+ * and nothing here depends on monotonicity.
+ * SAMPLING, with step = *step_dev + t and the global env id as for sgw_policy_act:
+ *   explore first, exactly as sgw_policy_act (the tag-2 draws, explore_below): if the agent explores, that index is the action
+ *   else if degenerate: index = best
+ *   else (x0, ..) = Philox-4x32-10(counter = (step, 3, a, env_id >> 32), key = (seed, env_id))       (tag 3: the sampler's stream)
+ *        u = ((double)x0 + 0.5) * 2^-32 ;  thr = u * total                                            one double multiplication
+ *        cum = 0.0; index = first j, scanning j = 0.. in order, with thr < (cum = cum + (double)w_j)
+ *        (always found: cum ends on total bit for bit, and thr < total)
+ *   actions[n][a] = action_lo + index; a policy index outside 0 .. P-1 writes 0 and reads no table.
+ * sgw_policy_sample is sgw_policy_act with that rule (one launch; the same arguments and checks); sgw_policy_sample_step_n is
+ * sgw_policy_step_n with the sampling launch in place of the greedy one: the same 2T + 1 launches, the same graph cache, whose
+ * key also holds beta2 and the kind of call, so a greedy and a sampled call over the same pointers never share a graph. */
+int sgw_policy_sample(sgw_engine* e, const sgw_policy* p, float beta2, const uint8_t* obs_dev, int64_t t, int8_t* actions_dev,
+                      void* stream);
+int sgw_policy_sample_step_n(sgw_engine* e, const sgw_policy* p, float beta2, const uint8_t* obs0_dev, int T, int write_every,
+                             const sgw_out* out, int8_t* actions_out_dev /* [T, N, A] */, int accumulate, void* stream);
+/* The probabilities over the T + 1 observations O[0 .. T], laid out as for sgw_policy_scores.  Outputs, at least one:
+ *   probs    float32 [T+1, N, A, n_actions] = (float)pi_j; a degenerate row is 1.0f at best and +0.0f elsewhere; a policy index
+ *            outside 0 .. P-1 gives +0.0f everywhere
+ *   p_chosen double  [T, N, A] = pi of the taped action (needs actions_dev): +0.0 for an action outside the spec's range (or an
+ *            unknown policy index), 1.0 or 0.0 on a degenerate row depending on whether the taped action is best
+ * These are the probabilities of the softmax alone: the exploration mixture of explore_below is NOT folded in (with epsilon > 0
+ * the behaviour policy is (1 - eps) * pi + eps / n_actions; that correction is the caller's).
+ * SGW_ERR_ARG: as sgw_policy_scores (T < 0, null obs0 / obs, obs_rows < N, no output, p_chosen without actions, misalignment),
+ * and a bad beta2.  One launch: no allocation, no synchronisation, capturable. */
+int sgw_policy_probs(sgw_engine* e, const sgw_policy* p, float beta2, const uint8_t* obs0_dev, const uint8_t* obs_dev, int64_t obs_rows,
+                     int T, const int8_t* actions_dev /* [T, N, A] or NULL */, float* probs_dev, double* p_chosen_dev, void* stream);
+/* The score-function (policy-gradient) sums into the int64 fixed-point accumulators of sgw_policy_accumulate.  For every transition
+ * with a known policy index, an action a* = actions[t][n][a] - action_lo inside 0 .. n_actions-1 and a row that is not degenerate,
+ * and for EVERY j (each operation one double operation):
+ *   d_j = (j == a* ? 1.0 : 0.0) - pi_j ;  x_j = coef * d_j ;  q_j = the quantisation of sgw_policy_accumulate applied to x_j
+ *   acc_bias[p][a][j] += q_j                                     (when acc_bias_dev is given)
+ *   acc_weights[p][a][c][code_of[o[c]]][j] += q_j                for every c < C_a
+ * Skipped transitions add nothing.  This is the gradient of log pi(a*) with respect to the scores, times coef; the true gradient
+ * carries one more factor beta2 * ln 2 (the scores enter the exponent as score * beta2 in base 2), which is the caller's to fold
+ * into lr.  Everything else -- in/out accumulators, T * N < 2^32, the 2048-byte row limit (SGW_ERR_UNSUPPORTED), alignment and
+ * the pointer-equality refusals, one capturable launch -- is sgw_policy_accumulate's; a bad beta2 is SGW_ERR_ARG. */
+int sgw_policy_accumulate_softmax(sgw_engine* e, const sgw_policy* p, float beta2, const uint8_t* obs0_dev, const uint8_t* obs_dev,
+                                  int64_t obs_rows, int T, const int8_t* actions_dev, const double* coef_dev, int frac_bits,
+                                  int64_t* acc_weights_dev, int64_t* acc_bias_dev /* or NULL */, void* stream);
+
 /* Per-env performance bookkeeping of SafetyEnvironment{,Mo}: _episodic_performances.append(...) at every LAST timestep
  * (safety_game.py:253-263, 301-302; safety_game_mo.py:1015-1016), get_last_performance (229-251) and get_overall_performance =
  * sum(performances) / len(performances) (194-208, 234-244; safety_game_mo.py:917-938).  perf_dev double [N, C] is the step's
