@@ -69,17 +69,22 @@ FORK_ROWS = ("island_ex_packed", "island_ex_plain", "boat_race_ex", "safe_interr
 PRE_STEPS = {"tomato_watering": 80, "tomato_crmdp": 80}
 
 
-@pytest.mark.parametrize("row_id", FORK_ROWS)
-def test_fork_equals_the_original(row_id):
-  row, spec, inp, eng = engine_of(row_id)
+FORK_SEED, FORK_AT, FORK_STEPS = 0xF0, 16, 32
+
+
+def fork_stays_equal(row, eng, pre_steps=0):
+  """A fresh engine of `row`: FORK_AT steps of its sgw_fill_actions stream (seed FORK_SEED), fork(), and both engines side by side to
+  step FORK_STEPS, across episode ends.  Closes both; returns the fork's outputs of steps FORK_AT .. FORK_STEPS - 1 as
+  {field: [steps, N, ...]}."""
+  row_id = row["id"]
   fork = None
   try:
     n = row["n"]
     LP.start(eng, row)
-    if row_id in PRE_STEPS:
-      eng.rollout(PRE_STEPS[row_id], 11)
-    acts = eng.fill_actions(32, 0xF0)
-    for t in range(16):
+    if pre_steps:
+      eng.rollout(pre_steps, 11)
+    acts = eng.fill_actions(FORK_STEPS, FORK_SEED)
+    for t in range(FORK_AT):
       o = eng.step(acts[t])
     fork = eng.fork()
     assert fork.n_envs == n and fork.env_id_base == eng.env_id_base and fork.outputs == eng.outputs
@@ -87,17 +92,26 @@ def test_fork_equals_the_original(row_id):
     for k in row["outs"]:
       assert same(fo[k], o[k]), "%s: the fork's %s differs right after fork()" % (row_id, k)
     ended = False
-    for t in range(16, 32):
+    rec = {k: [] for k in row["outs"]}
+    for t in range(FORK_AT, FORK_STEPS):
       o, fo = eng.step(acts[t]), fork.step(acts[t])
       for k in row["outs"]:
         assert same(fo[k], o[k]), "%s step %d: %s" % (row_id, t, k)
+        rec[k].append(fo[k].clone())
       ended = ended or bool((o["step_type"] == LAST).any())
     assert ended, "%s: no episode ends in the second half" % row_id
     assert same(fork.get_state()[:, :n], eng.get_state()[:, :n])
+    return {k: torch.stack(v) for k, v in rec.items()}
   finally:
     if fork is not None:
       fork.close()
     eng.close()
+
+
+@pytest.mark.parametrize("row_id", FORK_ROWS)
+def test_fork_equals_the_original(row_id):
+  row, spec, inp, eng = engine_of(row_id)
+  fork_stays_equal(row, eng, PRE_STEPS.get(row_id, 0))
 
 
 def test_fork_to_another_size_refuses_explicit_arrays():
@@ -256,18 +270,21 @@ def test_refused_calls_launch_nothing():
 
 
 # ---- 6. lookahead -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("row_id", ("island_ex_packed", "safe_interruptibility_ex", "firemaker_ex_ma"))
-def test_lookahead_is_the_step_not_taken(row_id):
-  B = 4
-  row, spec, inp, eng = engine_of(row_id)
-  third = LP.make_engine(row, spec, inp)
+LOOK_B, LOOK_AT, LOOK_SEED, LOOK_CAND_SEED = 4, 10, 0xA1, 0xB2
+
+
+def lookahead_is_the_step_not_taken(row, eng, third):
+  """Two fresh engines of `row`: LOOK_AT steps of the sgw_fill_actions stream (seed LOOK_SEED), then LOOK_B candidate action sets
+  (seed LOOK_CAND_SEED) through lookahead() against `third` restored from a snapshot; entry 2 is then taken.  Closes both; returns
+  lookahead()'s stacked result {field: [LOOK_B, N, ...]} as it was before the step."""
+  B, row_id = LOOK_B, row["id"]
   try:
     LP.start(eng, row)
     LP.start(third, row)
-    acts = eng.fill_actions(10, 0xA1)
-    for t in range(10):
+    acts = eng.fill_actions(LOOK_AT, LOOK_SEED)
+    for t in range(LOOK_AT):
       eng.step(acts[t])
-    cand = eng.fill_actions(B, 0xB2)                                    # int8 [B, N(, A)]: four different action sets
+    cand = eng.fill_actions(B, LOOK_CAND_SEED)                          # int8 [B, N(, A)]: four different action sets
     snap, b0, r0 = eng.get_state().clone(), bufs_of(eng), eng.read_returns().clone()
     res = eng.lookahead(cand)
     assert set(res) == set(row["outs"])
@@ -284,13 +301,21 @@ def test_lookahead_is_the_step_not_taken(row_id):
       assert same(v, b0[k]), "lookahead does not write the engine's %s" % k
     assert same(eng.read_returns(), r0)
     kept = {k: v[2].clone() for k, v in res.items()}
+    whole = {k: v.clone() for k, v in res.items()}
     o = eng.step(cand[2])
     for k in row["outs"]:
       assert same(o[k], kept[k]), "%s: step(actions[2]) differs from entry 2 in %s" % (row_id, k)
     assert eng.lookahead(cand)["board"].data_ptr() == res["board"].data_ptr(), "persistent result tensors"
+    return whole
   finally:
     eng.close()
     third.close()
+
+
+@pytest.mark.parametrize("row_id", ("island_ex_packed", "safe_interruptibility_ex", "firemaker_ex_ma"))
+def test_lookahead_is_the_step_not_taken(row_id):
+  row, spec, inp, eng = engine_of(row_id)
+  lookahead_is_the_step_not_taken(row, eng, LP.make_engine(row, spec, inp))
 
 
 # ---- 7. under graph capture -------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
-"""The headline's one-step kernel with level 9's default rule set compiled in (csrc/sgw_island.hpp IslandL9Default, picked by
-sgw_create: sgw_step_rules) against the shape-only kernel (SGW_GENERIC_RULES set at sgw_create) and the generic kernel
+"""The headline's one-step kernels with level 9's default rule set compiled in (csrc/sgw_island.hpp IslandL9Default, picked by
+sgw_create: sgw_step_rules) -- the forked kernel, which the default selection runs at every size used here (sgw_step_fork), and
+the one-wave kernel (SGW_NO_FORK set at sgw_create) -- against the shape-only kernel (SGW_GENERIC_RULES) and the generic kernel
 (SGW_GENERIC_STEP) on the same inputs: every output, the state and the episodic-return accumulators byte for byte.  Then
 against the C oracle, with QUIT and out-of-range actions in the tape; specs one flag or one parameter away from the compiled
 one take the shape-only kernel and still match the oracle."""
@@ -11,12 +12,14 @@ from ai_safety_gridworlds_amd import _native as N
 from ai_safety_gridworlds_amd import philox
 from ai_safety_gridworlds_amd.engine import BatchedEngine, ALL_OUTPUTS
 from ai_safety_gridworlds_amd.specs import make_spec
+from tests import headline_kernels as HK
 
 pytestmark = pytest.mark.gpu
 
 BENCH_OUTPUTS = ("board", "reward", "step_type", "term_reason", "safety", "frame")    # bench.py's headline output set
 ORACLE_FIELDS = ["board", "reward", "cumulative", "step_type", "term_reason", "safety"]
-KERNELS = (("rules", None, 1, 1), ("shape only", "SGW_GENERIC_RULES", 0, 1), ("generic", "SGW_GENERIC_STEP", 0, 0))   # name, env, step_rules, step_shape
+KERNELS = tuple((k["id"], k["env"]) + k["triple"] for k in HK.KERNELS)    # name, env at sgw_create, step_rules, step_shape, step_fork
+assert KERNELS[0] == ("fork", None, 1, 1, 1) and ("shape_only", "SGW_GENERIC_RULES", 0, 1, 0) in KERNELS and ("generic", "SGW_GENERIC_STEP", 0, 0, 0) in KERNELS
 
 
 def tape(seed, n, steps):
@@ -45,10 +48,10 @@ def _bytes(t):
 
 def _run(spec, n, outputs, env, write_every, acts, monkeypatch):
   """The call pattern of tests/test_step_shape_gpu.py: a 50-step sgw_step_n slice four times (first sighting, capture,
-  replays), two distinct 20-step slices, five single sgw_step calls; accumulate=True.  Returns (step_rules, step_shape,
-  recorded output bytes, state, returns)."""
+  replays), two distinct 20-step slices, five single sgw_step calls; accumulate=True.  Returns ((step_rules, step_shape,
+  step_fork), recorded output bytes, state, returns)."""
   eng = _engine(spec, n, outputs, env, monkeypatch)
-  rules, shape = int(N.lib().sgw_step_rules(eng._h)), int(N.lib().sgw_step_shape(eng._h))
+  triple = HK.triple_of(eng)
   rec = [{k: _bytes(v) for k, v in eng.reset().items()}]
   for a in [acts[0:50]] * 4 + [acts[50:70], acts[70:90]]:
     rec.append({k: _bytes(v) for k, v in eng.step_n(a, write_every=write_every, accumulate=True).items()})
@@ -57,7 +60,7 @@ def _run(spec, n, outputs, env, write_every, acts, monkeypatch):
   torch.cuda.synchronize()
   state, returns = _bytes(eng.get_state()), _bytes(eng.read_returns())
   eng.close()
-  return rules, shape, rec, state, returns
+  return triple, rec, state, returns
 
 
 CASES = [
@@ -69,13 +72,14 @@ CASES = [
 
 @pytest.mark.parametrize("n,outputs,write_every", CASES)
 def test_three_kernels_compute_the_same_bytes(n, outputs, write_every, monkeypatch):
+  """(Four since the forked kernel: the two with compiled rules, the shape-only one and the generic one.)"""
   spec = make_spec("island_navigation_ex")
   acts = torch.from_numpy(tape(0x5EED, n, 95)).to("cuda:0")
-  runs = [_run(spec, n, outputs, env, write_every, acts, monkeypatch) for _, env, _, _ in KERNELS]
-  for (name, _, want_rules, want_shape), (rules, shape, _, _, _) in zip(KERNELS, runs):
-    assert (rules, shape) == (want_rules, want_shape), name
-  _, _, rec0, state0, ret0 = runs[0]
-  for (name, _, _, _), (_, _, rec, state, ret) in list(zip(KERNELS, runs))[1:]:
+  runs = [_run(spec, n, outputs, k[1], write_every, acts, monkeypatch) for k in KERNELS]
+  for k, (triple, _, _, _) in zip(KERNELS, runs):
+    assert triple == k[2:], k[0]
+  _, rec0, state0, ret0 = runs[0]
+  for (name, _, _, _, _), (_, rec, state, ret) in list(zip(KERNELS, runs))[1:]:
     assert len(rec) == len(rec0)
     for i, (s, g) in enumerate(zip(rec0, rec)):
       for k in outputs:
@@ -93,6 +97,7 @@ def _against_oracle(what, kw, want_rules, want_shape):
   want = O.run_streams(O.make_config("island_navigation_ex", **kw), actions.T.copy(), fields=ORACLE_FIELDS)
   eng = BatchedEngine(spec, E, device="cuda:0", outputs=tuple(ORACLE_FIELDS))
   assert N.lib().sgw_step_rules(eng._h) == want_rules, what
+  assert N.lib().sgw_step_fork(eng._h) == want_rules, "%s: at %d envs the default selection forks wherever it compiles the rules in" % (what, E)
   if want_shape is not None:
     assert N.lib().sgw_step_shape(eng._h) == want_shape, what
   eng.reset()

@@ -128,14 +128,13 @@ def first_bad_call(c, got, rec):
       return k, bad
 
 
-@pytest.mark.parametrize("row_id", IDS)
-def test_every_row_after_every_call(row_id):
-  """(a), (b), (c)."""
+def every_call(row_id, on_engine=None):
+  """(a), (b), (c) of one row; on_engine(eng): what the caller asserts about the engine before it plays."""
   c = case(row_id)
   sched, named, idx, n, C = c["sched"], c["named"], c["idx"], c["row"]["n"], c["C"]
   eng = engine(c)
-  if row_id == "island_ex_L9_shaped":
-    assert N.lib().sgw_step_shape(eng._h) > 0, "the row must run the shaped step kernel"
+  if on_engine is not None:
+    on_engine(eng)
   watched = set(named.values()) | {named["overlap"] + 1}
   watched |= set([k for k in range(C) if sched[k][0] == "reset" and k not in watched][::4])
   rng_at = [k for k in range(C // 2, C) if sched[k][0] == "reset"][0]
@@ -156,6 +155,16 @@ def test_every_row_after_every_call(row_id):
   assert not bad, "%s: outputs %s differ from the oracle, first at (call, fields) %s" % (row_id, bad, first_bad_call(c, got, idx[:C].T))
   for k, st in rng_states.items():                                            # (c)
     assert not rng_bad(c, st, idx[k]), "%s: generator position after call %d" % (row_id, k)
+
+
+def _runs_a_shaped_kernel(eng):
+  assert N.lib().sgw_step_shape(eng._h) > 0, "the row must run the shaped step kernel"
+
+
+@pytest.mark.parametrize("row_id", IDS)
+def test_every_row_after_every_call(row_id):
+  """(a), (b), (c)."""
+  every_call(row_id, _runs_a_shaped_kernel if row_id == "island_ex_L9_shaped" else None)
 
 
 @pytest.mark.parametrize("row_id", IDS)

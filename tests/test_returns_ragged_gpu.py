@@ -117,19 +117,9 @@ def test_fractional_expectation_depends_on_the_order():
   assert r[-1] == c["last"].sum() and np.allclose(r, c["returns"], rtol=1e-12, atol=0)
 
 
-def _run(c, path, monkeypatch):
+def _play(eng, c, path):
+  """The case through one of PATHS on an engine that was just made -> (read_returns, n_pad); closes the engine."""
   import torch
-  from ai_safety_gridworlds_amd import _native as N
-  if c["generic"]:
-    monkeypatch.setenv("SGW_GENERIC_STEP", "1")
-  try:
-    eng = LP.make_engine(c["row"], c["spec"], c["inp"])
-  finally:
-    monkeypatch.delenv("SGW_GENERIC_STEP", raising=False)
-  if c["shape"] is not None:
-    assert int(N.lib().sgw_step_shape(eng._h)) == c["shape"]
-  if c["row"]["id"] == "island_fractional":
-    assert int(N.lib().sgw_state_words(eng._h)) == 22, "a reward that does not pack selects the plain f64 state"
   LP.start(eng, c["row"])
   acts = torch.from_numpy(c["acts"]).to(LP.DEV)
   if path == "step":                                         # one direct launch of the one-step kernel per call
@@ -146,6 +136,21 @@ def _run(c, path, monkeypatch):
   n_pad = eng.n_pad
   eng.close()
   return r, n_pad
+
+
+def _run(c, path, monkeypatch):
+  from ai_safety_gridworlds_amd import _native as N
+  if c["generic"]:
+    monkeypatch.setenv("SGW_GENERIC_STEP", "1")
+  try:
+    eng = LP.make_engine(c["row"], c["spec"], c["inp"])
+  finally:
+    monkeypatch.delenv("SGW_GENERIC_STEP", raising=False)
+  if c["shape"] is not None:
+    assert int(N.lib().sgw_step_shape(eng._h)) == c["shape"]
+  if c["row"]["id"] == "island_fractional":
+    assert int(N.lib().sgw_state_words(eng._h)) == 22, "a reward that does not pack selects the plain f64 state"
+  return _play(eng, c, path)
 
 
 @pytest.mark.gpu

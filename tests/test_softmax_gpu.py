@@ -113,9 +113,10 @@ def test_act_equals_the_reference(geo, beta2):
 
 
 # ---- the closed loop ------------------------------------------------------------------------------------------------------------
-def _closed_loop(geo, write_every, beta2, modes):
+def _closed_loop(geo, write_every, beta2, modes, record=None):
   """One call per entry of `modes` ("s": sampled, "g": greedy over the same buffers) on engine A, the same calls as a host loop of
-  act + step on fork B, A's tape through step_n on fork R; the tables are rewritten in place before the fourth call."""
+  act + step on fork B, A's tape through step_n on fork R; the tables are rewritten in place before the fourth call.  record: a
+  dict that receives every call's outputs ("A") and action tape ("tapeA") of engine A."""
   T = 8
   spec, eng, rng, polA, tables = _setup(geo, GEOS[geo][3], 3, 2 * len(modes) + int(write_every), beta2, epsilon=0.25)
   A, B, R = eng.fork(), eng.fork(), eng.fork()
@@ -131,6 +132,8 @@ def _closed_loop(geo, write_every, beta2, modes):
     outsB, tapeB, seen = _host_loop(B, polB, T)
     tapeA = resA.pop("actions")
     assert (tapeA == tapeB).all(), "call %d (%s): action tapes differ" % (call, mode)
+    if record is not None:
+      record.setdefault("A", []).append(resA); record.setdefault("tapeA", []).append(tapeA)
     for k in resA:
       wantB = np.stack([o[k] for o in outsB]) if write_every else outsB[-1][k]
       assert LP._same(resA[k].reshape(wantB.shape), wantB), "call %d (%s): output %r differs from the host loop" % (call, mode, k)

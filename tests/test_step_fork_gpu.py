@@ -11,7 +11,11 @@ Output subsets at N = 129, each buffer inside guard bytes (tests/output_subsets.
 alone makes the output wave run the regrowth, `cumulative` alone is the one reader of the running sums), and none at all (state and
 returns only).
 
-The selection by size: an engine of 4 x CUs x 64 envs forks, one of 4 x CUs x 64 + 64 does not and still equals SGW_NO_FORK."""
+The selection by size: an engine of 4 x CUs x 64 envs forks, one of 4 x CUs x 64 + 64 does not and still equals SGW_NO_FORK; both
+default-selected engines are compared with the oracle over 8 steps of the bench output set.
+
+The features (masked resets, QUIT, the packed state at its limit, ragged returns, the closed loop, copy / fork / lookahead, the
+facades) on this kernel and on the other three: tests/test_headline_kernels_gpu.py."""
 import numpy as np
 import pytest
 
@@ -139,23 +143,41 @@ def test_output_subsets_inside_guard_bytes(name, outputs, monkeypatch):
 
 
 def test_the_selection_by_size(monkeypatch):
-  """At most one env-wave per SIMD forks; one env-wave more keeps the one-wave kernel, which SGW_NO_FORK also selects."""
+  """At most one env-wave per SIMD forks; one env-wave more keeps the one-wave kernel, which SGW_NO_FORK also selects.  On both
+  sides of the edge the default-selected engine's 8 recorded steps of the bench output set equal the C oracle's on the same
+  Philox tape: 4 x CUs x 64 envs is the largest forked grid (its last workgroup runs nowhere else), 64 envs more the one size
+  at which the default selection launches the one-wave kernel with its real grid.  66 067 episodes end inside the 8 steps.
+  The oracle takes 0.4 s for the 65 600 envs x 8 steps of a 256-CU part (16 threads on 8 cores; 0.5 s with one thread), the
+  whole test 0.7 s on the MI355X's host."""
   import torch
   from ai_safety_gridworlds_amd import _native as N, philox
   from ai_safety_gridworlds_amd.engine import BatchedEngine
+  from oracle import oracle as O
   cus = torch.cuda.get_device_properties(0).multi_processor_count
   edge = 4 * cus * 64
-  eng = _engine(BatchedEngine, edge, None, ("step_type",), monkeypatch)
-  assert N.lib().sgw_step_fork(eng._h) == 1
-  eng.close()
   n, steps = edge + 64, 8
-  acts = torch.from_numpy(philox.actions(0xF02C, np.arange(n, dtype=np.uint64), np.arange(steps, dtype=np.uint64), 0, 5).astype(np.int8)).to("cuda:0")
+  host = philox.actions(0xF02C, np.arange(n, dtype=np.uint64), np.arange(steps, dtype=np.uint64), 0, 5).astype(np.int8)
+  want = O.run_streams(O.make_config("island_navigation_ex"), host.T.copy(), fields=list(BENCH_OUTPUTS), nthreads=16)
+  acts = torch.from_numpy(host).to("cuda:0")
+
+  def play(eng):
+    eng.reset()
+    return [{k: v.clone() for k, v in eng.step(acts[t, :eng.n_envs].contiguous()).items()} for t in range(steps)]
+
+  def against_the_oracle(rec, m, label):
+    _compare({k: torch.stack([r[k] for r in rec]) for k in BENCH_OUTPUTS}, {k: want[k][:m] for k in BENCH_OUTPUTS}, 1, m, BENCH_OUTPUTS, label)
+
+  eng = _engine(BatchedEngine, edge, None, BENCH_OUTPUTS, monkeypatch)
+  assert N.lib().sgw_step_fork(eng._h) == 1
+  against_the_oracle(play(eng), edge, "the fork at %d envs" % edge)          # (env e's tape does not depend on the batch size)
+  eng.close()
   got = []
   for env in (None, "SGW_NO_FORK"):
     eng = _engine(BatchedEngine, n, env, BENCH_OUTPUTS, monkeypatch)
     assert N.lib().sgw_step_fork(eng._h) == 0
-    eng.reset()
-    rec = [{k: v.clone() for k, v in eng.step(acts[t]).items()} for t in range(steps)]
+    rec = play(eng)
+    if env is None:
+      against_the_oracle(rec, n, "the default selection at %d envs" % n)
     got.append((rec, eng.get_state().clone()))
     eng.close()
   (rec_a, st_a), (rec_b, st_b) = got
