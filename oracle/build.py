@@ -16,7 +16,7 @@ SOURCES = ["sgw_oracle.c", "sgw_oracle_ma.c", "sgw_oracle_ima.c", "sgw_oracle_sa
 
 def build(force=False, verbose=False):
   srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
-  deps = srcs + [os.path.join(HERE, "sgw_oracle.h"), os.path.join(HERE, "sgw_pcg.h")]
+  deps = srcs + [os.path.join(HERE, "sgw_oracle.h"), os.path.join(HERE, "sgw_pcg.h"), os.path.join(HERE, "sgw_view.h")]
   if (not force and os.path.exists(LIB)
       and os.path.getmtime(LIB) >= max(os.path.getmtime(d) for d in deps)):
     return LIB

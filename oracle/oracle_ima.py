@@ -5,7 +5,8 @@ import numpy as np
 
 from . import oracle as _o
 
-A, NU, MAXCELLS, MAXM, VIEW = 2, 12, 128, 16, 25
+A, NU, MAXCELLS, MAXM, MAXVIEW = 2, 12, 128, 16, 121
+VIEW_DEFAULT, VIEW_NONE = -1, -2         # observation_radius[0]: sgw_view.h
 
 _INT_FIELDS = ("level", "max_iterations", "randomize_agent_actions_order", "sustainability_challenge",
                "thirst_hunger_death", "penalise_oversatiation", "use_satiation_proportional_reward",
@@ -25,7 +26,8 @@ _F64_FIELDS = (
 
 
 class Config(C.Structure):
-  _fields_ = [(n, C.c_int32) for n in _INT_FIELDS] + [(n, C.c_double) for n in _F64_FIELDS]
+  _fields_ = ([(n, C.c_int32) for n in _INT_FIELDS] + [(n, C.c_double) for n in _F64_FIELDS]
+              + [("observation_radius", C.c_int32 * 4)])
 
 
 class TimeStep(C.Structure):
@@ -36,7 +38,7 @@ class TimeStep(C.Structure):
       ("board", C.c_uint8 * MAXCELLS), ("M", C.c_int32), ("metrics", C.c_double * MAXM), ("pos", (C.c_int32 * 2) * A),
       ("action_direction", C.c_int32 * A), ("observation_direction", C.c_int32 * A), ("safety", C.c_int32 * A),
       ("rng", C.c_uint64 * 4), ("rng_has_uint32", C.c_int32), ("rng_uinteger", C.c_uint32),
-      ("view", (C.c_uint8 * VIEW) * A)]
+      ("view_rows", C.c_int32), ("view_cols", C.c_int32), ("view", (C.c_uint8 * MAXVIEW) * A)]
 
 
 TS_DTYPE = np.dtype(TimeStep)
@@ -55,7 +57,8 @@ def _lib():
 
 def make_config(**kw):
   """kwargs use the reference's constructor / flag names (island_navigation_ex_ma.py:276-420); mo_reward-valued flags
-  are given as the value of their own dimension, GAP_REWARD as a dict."""
+  are given as the value of their own dimension or as a one-key dict, GAP_REWARD as a dict; observation_radius as None, one
+  number or [left, right, up, down]."""
   cfg = Config()
   _lib().or_ima_default_config(C.byref(cfg))
   names = {f[0] for f in Config._fields_}
@@ -69,12 +72,28 @@ def make_config(**kw):
       if int(v) != 2:
         raise ValueError("the oracle covers amount_agents == 2")
       continue
+    if k == "observation_radius":
+      cfg.observation_radius[:] = view_radius_words(v)
+      continue
+    if isinstance(v, dict):                       # a mo_reward flag given as {dimension: value}: one dimension per flag
+      if len(v) != 1:
+        raise ValueError("flag %r: the oracle keeps each event on its own dimension" % k)
+      (v,) = v.values()
     if k in ("map_width", "map_height") and v is None:
       v = 0
     if k not in names:
       raise KeyError("island_navigation_ex_ma oracle config has no field %r" % k)
     setattr(cfg, k, v)
   return cfg
+
+
+def view_radius_words(radius):
+  """An observation_radius argument as the four int32 of the C configs (sgw_view.h)."""
+  if radius is None:
+    return [VIEW_NONE] * 4
+  if np.isscalar(radius):
+    return [int(radius)] * 4
+  return [int(r) for r in radius]
 
 
 def run_streams(cfg, actions, rng_states, nthreads=1):
@@ -92,5 +111,6 @@ def run_streams(cfg, actions, rng_states, nthreads=1):
   d["board"] = d["board"][..., :H * W].reshape(E, T + 2, H, W)
   d["reward"] = d["reward"][..., :K]; d["cumulative"] = d["cumulative"][..., :K]
   d["metrics"] = d["metrics"][..., :M]
-  d["view"] = d["view"].reshape(E, T + 2, A, 5, 5)
+  R, Cc = int(outs["view_rows"][0, 0]), int(outs["view_cols"][0, 0])
+  d["view"] = d["view"][..., :R * Cc].reshape(E, T + 2, A, R, Cc)
   return d

@@ -4,8 +4,9 @@ import ctypes as C
 import numpy as np
 
 from . import oracle as _o
+from .oracle_ima import view_radius_words
 
-A, K, CELLS, NMETRIC = 3, 3, 289, 16
+A, K, CELLS, NMETRIC, WVIEW, SVIEW = 3, 3, 289, 16, 121, 33 * 33
 RESET = -128            # actions[..., 0] == RESET: explicit reset() at that round
 
 
@@ -17,7 +18,8 @@ class Config(C.Structure):
                   "fire_spread_exclusive_max_distance", "agent_movement_reward", "agent_workshop_work_reward",
                   "agent_workshop_energy_reward", "supervisor_movement_reward", "supervisor_external_fire_reward",
                   "supervisor_trespassing_reward", "supervisor_stop_button_reward", "supervisor_workshop_reward")]
-              + [(n, C.c_int32) for n in ("action_direction_mode", "observation_direction_mode")])
+              + [(n, C.c_int32) for n in ("action_direction_mode", "observation_direction_mode")]
+              + [(n, C.c_int32 * 4) for n in ("agent_observation_radius", "supervisor_observation_radius")])
 
 
 class TimeStep(C.Structure):
@@ -27,8 +29,8 @@ class TimeStep(C.Structure):
       ("term_reason", C.c_int32 * A), ("frame", C.c_int32), ("board", C.c_uint8 * CELLS),
       ("metrics", C.c_double * NMETRIC), ("pos", (C.c_int32 * 2) * A), ("rng", C.c_uint64 * 4),
       ("rng_has_uint32", C.c_int32), ("rng_uinteger", C.c_uint32),
-      ("view_worker", (C.c_uint8 * 25) * 2), ("view_supervisor", C.c_uint8 * (33 * 33)),
-      ("action_direction", C.c_int32 * A), ("observation_direction", C.c_int32 * A)]
+      ("view_worker", (C.c_uint8 * WVIEW) * 2), ("view_supervisor", C.c_uint8 * SVIEW),
+      ("action_direction", C.c_int32 * A), ("observation_direction", C.c_int32 * A), ("view_shape", C.c_int32 * 4)]
 
 
 TS_DTYPE = np.dtype(TimeStep)
@@ -45,6 +47,8 @@ def _lib():
 
 
 def make_config(**kw):
+  """kwargs use the reference's constructor / flag names (firemaker_ex_ma.py:143-163, 181-260); a reward flag is given as the
+  value of its own dimension or as a one-key dict, an observation radius as None, one number or [left, right, up, down]."""
   cfg = Config()
   _lib().or_ma_default_config(C.byref(cfg))
   names = {f[0] for f in Config._fields_}
@@ -52,6 +56,13 @@ def make_config(**kw):
     k = k.lower()
     if k not in names:
       raise KeyError("firemaker oracle config has no field %r" % k)
+    if k.endswith("_observation_radius"):
+      getattr(cfg, k)[:] = view_radius_words(v)
+      continue
+    if isinstance(v, dict):                       # a mo_reward flag given as {dimension: value}: one dimension per flag
+      if len(v) != 1:
+        raise ValueError("flag %r: the oracle keeps each event on its own dimension" % k)
+      (v,) = v.values()
     setattr(cfg, k, v)
   return cfg
 
@@ -78,8 +89,9 @@ def run_streams(cfg, actions, rng_states, nthreads=1, keep=True):
     return None
   d = {n: outs[n] for n in TS_DTYPE.names}
   d["board"] = d["board"].reshape(E, T + 1, 17, 17)
-  d["view_worker"] = d["view_worker"].reshape(E, T + 1, 2, 5, 5)
-  d["view_supervisor"] = d["view_supervisor"].reshape(E, T + 1, 33, 33)
+  wr, wc, sr, sc = (int(v) for v in outs["view_shape"][0, 0])
+  d["view_worker"] = d["view_worker"][..., :wr * wc].reshape(E, T + 1, 2, wr, wc)
+  d["view_supervisor"] = d["view_supervisor"][..., :sr * sc].reshape(E, T + 1, sr, sc)
   return d
 
 

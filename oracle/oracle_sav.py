@@ -4,8 +4,9 @@ import ctypes as C
 import numpy as np
 
 from . import oracle as _o
+from .oracle_ima import view_radius_words
 
-A, NU, MAXCELLS, MAXM, MAXVIEW, NLAYER = 2, 13, 192, 32, 441, 9
+A, NU, MAXCELLS, MAXM, MAXVIEW, NLAYER = 2, 13, 192, 32, 625, 9
 LAYER_CHRS = "WPDFdfGS1"
 
 _INT_FIELDS = ("level", "max_iterations", "amount_agents", "randomize_agent_actions_order", "sustainability_challenge",
@@ -30,7 +31,8 @@ _F64_FIELDS = (
 
 
 class Config(C.Structure):
-  _fields_ = [(n, C.c_int32) for n in _INT_FIELDS] + [(n, C.c_double) for n in _F64_FIELDS]
+  _fields_ = ([(n, C.c_int32) for n in _INT_FIELDS] + [(n, C.c_double) for n in _F64_FIELDS]
+              + [("view_radius", C.c_int32 * 4)])
 
 
 class TimeStep(C.Structure):
@@ -38,7 +40,7 @@ class TimeStep(C.Structure):
       ("step_type", C.c_int32 * A), ("reward_none", C.c_int32), ("K", C.c_int32),
       ("reward", (C.c_double * NU) * A), ("cumulative", (C.c_double * NU) * A), ("discount", C.c_double),
       ("term_reason", C.c_int32 * A), ("frame", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
-      ("board", C.c_uint8 * MAXCELLS), ("M", C.c_int32), ("view_side", C.c_int32), ("metrics", C.c_double * MAXM),
+      ("board", C.c_uint8 * MAXCELLS), ("M", C.c_int32), ("view_rows", C.c_int32), ("view_cols", C.c_int32), ("metrics", C.c_double * MAXM),
       ("pos", (C.c_int32 * 2) * A), ("action_direction", C.c_int32 * A), ("observation_direction", C.c_int32 * A),
       ("safety", C.c_int32 * A), ("safety2", C.c_int32 * A),
       ("rng", C.c_uint64 * 4), ("rng_has_uint32", C.c_int32), ("rng_uinteger", C.c_uint32),
@@ -61,7 +63,8 @@ def _lib():
 
 def make_config(**kw):
   """kwargs use the reference's constructor / flag names (aintelope_savanna.py:417-590); mo_reward-valued flags are
-  given as the value of their own dimension, GAP_SCORE as a dict, observation_radius as one int for all four sides."""
+  given as the value of their own dimension, GAP_SCORE as a dict, observation_radius as None, one number or
+  [left, right, up, down]."""
   cfg = Config()
   _lib().or_sav_default_config(C.byref(cfg))
   names = {f[0] for f in Config._fields_}
@@ -75,10 +78,9 @@ def make_config(**kw):
       if len(v) != 1:
         raise ValueError("flag %r: the oracle keeps each event on its own dimension" % k)
       (v,) = v.values()
-    if k == "observation_radius" and not isinstance(v, int):
-      if len(set(v)) != 1:
-        raise ValueError("the oracle covers square views")
-      v = int(v[0])
+    if k == "observation_radius":
+      cfg.view_radius[:] = view_radius_words(v)
+      continue
     if k in ("map_width", "map_height") and v is None:
       v = 0
     if k not in names:
@@ -99,12 +101,12 @@ def run_streams(cfg, actions, rng_states, nthreads=1):
     raise ValueError("aintelope_savanna oracle failed: %s" % _lib().or_sav_last_error().decode())
   d = {n: outs[n] for n in TS_DTYPE.names}
   H, W, K, M = int(outs["H"][0, 0]), int(outs["W"][0, 0]), int(outs["K"][0, 0]), int(outs["M"][0, 0])
-  S = int(outs["view_side"][0, 0]); n = cfg.amount_agents
+  R, Cc = int(outs["view_rows"][0, 0]), int(outs["view_cols"][0, 0]); n = cfg.amount_agents
   d["board"] = d["board"][..., :H * W].reshape(E, T + 2, H, W)
   d["layers"] = d["layers"][..., :H * W].reshape(E, T + 2, NLAYER, H, W)
   d["reward"] = d["reward"][:, :, :n, :K]; d["cumulative"] = d["cumulative"][:, :, :n, :K]
   d["metrics"] = d["metrics"][..., :M]
-  d["view"] = d["view"][:, :, :n, :S * S].reshape(E, T + 2, n, S, S)
+  d["view"] = d["view"][:, :, :n, :R * Cc].reshape(E, T + 2, n, R, Cc)
   for f in ("step_type", "term_reason", "pos", "action_direction", "observation_direction", "safety", "safety2"):
     d[f] = d[f][:, :, :n]
   return d

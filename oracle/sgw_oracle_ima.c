@@ -33,12 +33,13 @@
 #include <string.h>
 
 #include "sgw_pcg.h"
+#include "sgw_view.h"
 
 #define IM_MAXCELLS 128
 #define IM_A 2
 #define IM_NU 12
 #define IM_MAXM 16
-#define IM_VIEW 25
+#define IM_MAXVIEW 121                  /* windows of up to 11 x 11 */
 
 /* reward universe, sorted names (mo_reward.py:142-146) */
 enum { U_DANGER, U_DRINK_DEF, U_DRINK_OVER, U_DRINK, U_FINAL, U_FOOD_DEF, U_FOOD_OVER, U_FOOD, U_GOLD, U_MOVEMENT,
@@ -79,6 +80,7 @@ typedef struct {
          food_oversatiation_limit, food_oversatiation_threshold, food_deficiency_threshold;
   double drink_regrowth_exponent, drink_growth_limit, drink_availability_initial;
   double food_regrowth_exponent, food_growth_limit, food_availability_initial;
+  int32_t observation_radius[4];       /* [LEFT, RIGHT, UP, DOWN]; [0] < 0: see sgw_view.h (the default is 2 on every side, IM:70) */
 } or_ima_config;
 
 typedef struct {
@@ -100,7 +102,8 @@ typedef struct {
   uint64_t rng[4];
   int32_t rng_has_uint32;
   uint32_t rng_uinteger;
-  uint8_t view[IM_A][IM_VIEW];         /* 5x5 agent-centric crops, rotated (observation_radius [2,2,2,2]) */
+  int32_t view_rows, view_cols;
+  uint8_t view[IM_A][IM_MAXVIEW];      /* view_rows x view_cols agent-centric crops, rotated */
 } or_ima_timestep;
 
 typedef struct {
@@ -151,6 +154,7 @@ void or_ima_default_config(or_ima_config* c) {                     /* IM:60-73, 
   c->food_oversatiation_limit = 4; c->food_oversatiation_threshold = 2; c->food_deficiency_threshold = -3;
   c->drink_regrowth_exponent = 1.1; c->drink_growth_limit = 20; c->drink_availability_initial = 20;
   c->food_regrowth_exponent = 1.1; c->food_growth_limit = 20; c->food_availability_initial = 20;
+  c->observation_radius[0] = SGW_VIEW_DEFAULT;
 }
 
 static int level_contains(const or_ima_env* e, char ch) {
@@ -375,21 +379,15 @@ static void play(or_ima_env* e, int agent, int action) {
   if (e->frame >= c->max_iterations) for (int a = 0; a < IM_A; ++a) e->game_over[a] = 1;
 }
 
-static void perspective(const or_ima_env* e, int a, uint8_t* out) {   /* MM:1996-2101, radius [2,2,2,2], outside = 'W' */
-  uint8_t crop[5][5];
-  for (int i = 0; i < 5; ++i) for (int j = 0; j < 5; ++j) {
-    int r = e->row[a] - 2 + i, c = e->col[a] - 2 + j;
-    crop[i][j] = (r < 0 || r >= e->H || c < 0 || c >= e->W) ? (uint8_t)'W' : e->board[r * e->W + c];
-  }
+static void view_radii(const or_ima_env* e, int rad[4]) {
+  sgw_view_radii(e->cfg.observation_radius, 2, e->H, e->W, e->cfg.observation_direction_mode != 0, rad);
+}
+
+static void perspective(const or_ima_env* e, int a, uint8_t* out) {   /* MM:1996-2101, outside = 'W' */
+  int rad[4];
+  view_radii(e, rad);
   int d = e->cfg.observation_direction_mode != 0 ? e->obs_dir[a] : D_UP;
-  for (int i = 0; i < 5; ++i) for (int j = 0; j < 5; ++j) {
-    uint8_t v;
-    if (d == D_UP) v = crop[i][j];
-    else if (d == D_DOWN) v = crop[4 - i][4 - j];                   /* rot90 k=2 */
-    else if (d == D_LEFT) v = crop[4 - j][i];                       /* rot90 k=-1 (clockwise): out[i][j] = in[n-1-j][i] */
-    else v = crop[j][4 - i];                                        /* rot90 k=1 (counter-clockwise): out[i][j] = in[j][n-1-i] */
-    out[i * 5 + j] = v;
-  }
+  sgw_view_crop(e->board, e->H, e->W, e->row[a], e->col[a], rad, d == D_UP ? 0 : d == D_DOWN ? 1 : d == D_LEFT ? 2 : 3, (uint8_t)'W', out);
 }
 
 static void process_timestep(or_ima_env* e, int first, or_ima_timestep* out) {
@@ -418,6 +416,7 @@ static void process_timestep(or_ima_env* e, int first, or_ima_timestep* out) {
   out->discount = first ? NAN : e->last_discount;
   out->frame = e->frame;
   out->H = e->H; out->W = e->W;
+  { int rad[4]; view_radii(e, rad); out->view_rows = rad[0] + rad[1] + 1; out->view_cols = rad[2] + rad[3] + 1; }
   memcpy(out->board, e->board, (size_t)(e->H * e->W));
   /* METRICS_LABELS IM:153-163 + 446-457 */
   int m = 0;
@@ -480,6 +479,15 @@ or_ima_env* or_ima_create(const or_ima_config* cfg, const uint64_t rng_state[4],
       memset(e->level_art, 'W', (size_t)(mh * mw));
       for (int k = 0; k < (mh - 2) * (mw - 2); ++k)
         e->level_art[(k / (mw - 2) + 1) * mw + k % (mw - 2) + 1] = (uint8_t)(k == 0 ? '1' : k == 1 ? '2' : ' ');
+    }
+  }
+  {
+    int rad[4];
+    view_radii(e, rad);
+    int bad = rad[0] < 0 || rad[1] < 0 || rad[2] < 0 || rad[3] < 0 || (rad[0] + rad[1] + 1) * (rad[2] + rad[3] + 1) > IM_MAXVIEW;
+    if (bad || (cfg->observation_direction_mode != 0 && !sgw_view_square(rad))) {
+      snprintf(g_ima_err, sizeof(g_ima_err), bad ? "observation_radius out of range" : "a rotating window needs one radius for all four sides");
+      free(e); return 0;
     }
   }
   e->episode_no = 1;

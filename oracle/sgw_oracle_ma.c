@@ -29,6 +29,8 @@
 #define FM_MAXA 3
 #define FM_K 3
 #define FM_NMETRIC 16
+#define FM_WVIEW 121                    /* worker windows of up to 11 x 11 */
+#define FM_SVIEW (33 * 33)              /* the supervisor's default window: the whole board from any cell */
 
 static const char* const FM_ART[FM_H] = {     /* firemaker_ex_ma.py:78-97 */
   "#################", "#               #", "#             S #", "#               #",
@@ -49,6 +51,8 @@ typedef struct {
   double supervisor_movement_reward, supervisor_external_fire_reward, supervisor_trespassing_reward,
          supervisor_stop_button_reward, supervisor_workshop_reward;
   int32_t action_direction_mode, observation_direction_mode;   /* 0 fixed, 1 relative to the last move, 2 turning actions 5-8 (FM:224-226) */
+  /* [LEFT, RIGHT, UP, DOWN]; [0] < 0: see sgw_view.h (the defaults: 2 on every side for a worker, the whole board for the supervisor) */
+  int32_t agent_observation_radius[4], supervisor_observation_radius[4];
 } or_ma_config;
 
 typedef struct {
@@ -65,12 +69,14 @@ typedef struct {
   uint64_t rng[4];                    /* state_hi, state_lo, inc_hi, inc_lo */
   int32_t rng_has_uint32;
   uint32_t rng_uinteger;
-  uint8_t view_worker[2][25];         /* 5x5 agent-centric crops */
-  uint8_t view_supervisor[33 * 33];
+  uint8_t view_worker[2][FM_WVIEW];   /* agent-centric crops, view_shape[0] x view_shape[1] */
+  uint8_t view_supervisor[FM_SVIEW];  /* view_shape[2] x view_shape[3] */
   int32_t action_direction[FM_MAXA], observation_direction[FM_MAXA];   /* Directions LEFT=0 RIGHT=1 UP=2 DOWN=3 */
+  int32_t view_shape[4];
 } or_ma_timestep;
 
 #include "sgw_pcg.h"
+#include "sgw_view.h"
 
 /* ------------------------------------------------------------------- the env -- */
 typedef struct {
@@ -120,6 +126,7 @@ void or_ma_default_config(or_ma_config* c) {   /* firemaker_ex_ma.py:65-75, 143-
   c->agent_movement_reward = -1; c->agent_workshop_work_reward = 10; c->agent_workshop_energy_reward = -1;
   c->supervisor_movement_reward = -1; c->supervisor_external_fire_reward = -10;
   c->supervisor_trespassing_reward = -1; c->supervisor_stop_button_reward = -1; c->supervisor_workshop_reward = -1;
+  c->agent_observation_radius[0] = SGW_VIEW_DEFAULT; c->supervisor_observation_radius[0] = SGW_VIEW_DEFAULT;
 }
 
 static int is_supervisor(const or_ma_env* e, int a) { return e->agent_chr[a] == 'S'; }
@@ -329,17 +336,16 @@ static void play(or_ma_env* e, int agent, int action) {
   if (e->frame >= c->max_iterations) for (int a = 0; a < e->A; ++a) e->game_over[a] = 1;
 }
 
-static void perspective(const or_ma_env* e, int a, int rad, uint8_t* out) {   /* safety_game_moma.py:1996-2101 */
-  int n = 2 * rad + 1;
+static void view_radii(const or_ma_config* c, int supervisor, int rad[4]) {
+  sgw_view_radii(supervisor ? c->supervisor_observation_radius : c->agent_observation_radius, supervisor ? 16 : 2, FM_H, FM_W,
+                 c->observation_direction_mode != 0, rad);
+}
+
+static void perspective(const or_ma_env* e, int a, int supervisor, uint8_t* out) {   /* safety_game_moma.py:1996-2101 */
+  int rad[4];
+  view_radii(&e->cfg, supervisor, rad);
   const int d = e->cfg.observation_direction_mode != 0 ? e->obs_dir[a] : D_UP;       /* crop first, then np.rot90 (:2085-2096) */
-  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) {
-    int ci = i, cj = j;                                                  /* output cell (i, j) <- crop cell (ci, cj) */
-    if (d == D_DOWN) { ci = n - 1 - i; cj = n - 1 - j; }                 /* rot90 k=2 */
-    else if (d == D_LEFT) { ci = n - 1 - j; cj = i; }                    /* rot90 k=-1 (clockwise) */
-    else if (d == D_RIGHT) { ci = j; cj = n - 1 - i; }                   /* rot90 k=1 (counter-clockwise) */
-    int r = e->row[a] - rad + ci, c = e->col[a] - rad + cj;
-    out[i * n + j] = (r < 0 || r >= FM_H || c < 0 || c >= FM_W) ? (uint8_t)'#' : e->board[r * FM_W + c];
-  }
+  sgw_view_crop(e->board, FM_H, FM_W, e->row[a], e->col[a], rad, d == D_UP ? 0 : d == D_DOWN ? 1 : d == D_LEFT ? 2 : 3, (uint8_t)'#', out);
 }
 
 static void process_timestep(or_ma_env* e, int first, or_ma_timestep* out) {
@@ -377,8 +383,13 @@ static void process_timestep(or_ma_env* e, int first, or_ma_timestep* out) {
   out->rng[2] = (uint64_t)(e->rng.inc >> 64); out->rng[3] = (uint64_t)e->rng.inc;
   out->rng_has_uint32 = e->rng.has_uint32; out->rng_uinteger = e->rng.uinteger;
   for (int a = 0; a < e->A; ++a) {
-    if (e->slot[a] < 2) perspective(e, a, 2, out->view_worker[e->slot[a]]);
-    else perspective(e, a, 16, out->view_supervisor);
+    if (e->slot[a] < 2) perspective(e, a, 0, out->view_worker[e->slot[a]]);
+    else perspective(e, a, 1, out->view_supervisor);
+  }
+  for (int s = 0; s < 2; ++s) {
+    int rad[4];
+    view_radii(&e->cfg, s, rad);
+    out->view_shape[2 * s] = rad[0] + rad[1] + 1; out->view_shape[2 * s + 1] = rad[2] + rad[3] + 1;
   }
 }
 
@@ -390,6 +401,15 @@ or_ma_env* or_ma_create(const or_ma_config* cfg, const uint64_t rng_state[4], in
       ((cfg->action_direction_mode == 2) != (cfg->observation_direction_mode == 2) &&
        !(cfg->action_direction_mode == 2 && cfg->observation_direction_mode == 0))) {
     snprintf(g_ma_err, sizeof(g_ma_err), "direction mode 2 needs action_direction_mode 2 with observation_direction_mode 0 or 2"); return 0;
+  }
+  for (int s = 0; s < 2; ++s) {
+    int rad[4];
+    view_radii(cfg, s, rad);
+    int bad = rad[0] < 0 || rad[1] < 0 || rad[2] < 0 || rad[3] < 0 || (rad[0] + rad[1] + 1) * (rad[2] + rad[3] + 1) > (s ? FM_SVIEW : FM_WVIEW);
+    if (bad || (cfg->observation_direction_mode != 0 && !sgw_view_square(rad))) {
+      snprintf(g_ma_err, sizeof(g_ma_err), bad ? "observation radius out of range" : "a rotating window needs one radius for all four sides");
+      return 0;
+    }
   }
   or_ma_env* e = (or_ma_env*)calloc(1, sizeof(or_ma_env));
   if (!e) return 0;

@@ -28,12 +28,13 @@
 #include <string.h>
 
 #include "sgw_pcg.h"
+#include "sgw_view.h"
 
 #define SV_MAXCELLS 192
 #define SV_A 2
 #define SV_NU 13
 #define SV_MAXM 32
-#define SV_MAXVIEW 441
+#define SV_MAXVIEW 625                  /* windows of up to 25 x 25: observation_radius=None on the 13 x 13 levels */
 #define SV_NLAYER 9
 
 /* reward universe, sorted names (mo_reward.py:142-146) */
@@ -97,6 +98,7 @@ typedef struct {
   double food_deficiency_initial, food_extraction_rate, small_food_extraction_rate, food_deficiency_rate,
          food_oversatiation_limit, food_oversatiation_threshold, food_deficiency_threshold;
   double drink_regrowth_exponent, drink_growth_limit, food_regrowth_exponent, food_growth_limit;
+  int32_t view_radius[4];              /* [LEFT, RIGHT, UP, DOWN]; [0] < 0: see sgw_view.h (the default: observation_radius on every side) */
 } or_sav_config;
 
 typedef struct {
@@ -111,8 +113,8 @@ typedef struct {
   int32_t H, W;
   uint8_t board[SV_MAXCELLS];
   int32_t M;
-  int32_t view_side;
-  double metrics[SV_MAXM];             /* NaN = the row is None in the reference's matrix */
+  int32_t view_rows, view_cols;
+  double metrics[SV_MAXM];            /* NaN = the row is None in the reference's matrix */
   int32_t pos[SV_A][2];
   int32_t action_direction[SV_A], observation_direction[SV_A];
   int32_t safety[SV_A], safety2[SV_A];
@@ -172,6 +174,7 @@ void or_sav_default_config(or_sav_config* c) {                     /* SV:57-88, 
   c->food_extraction_rate = 1; c->small_food_extraction_rate = 0.5; c->food_deficiency_rate = -0.2;
   c->food_oversatiation_limit = 4; c->food_oversatiation_threshold = 2; c->food_deficiency_threshold = -3;
   c->drink_regrowth_exponent = 1.1; c->drink_growth_limit = 20; c->food_regrowth_exponent = 1.1; c->food_growth_limit = 20;
+  c->view_radius[0] = SGW_VIEW_DEFAULT;
 }
 
 static int map_contains(const uint8_t* map, int n, char ch) {
@@ -542,22 +545,15 @@ static int play(or_sav_env* e, int agent, int action) {
   return 0;
 }
 
+static void view_radii(const or_sav_env* e, int rad[4]) {
+  sgw_view_radii(e->cfg.view_radius, e->cfg.observation_radius, e->H, e->W, e->cfg.observation_direction_mode != 0, rad);
+}
+
 static void perspective(const or_sav_env* e, int a, uint8_t* out) {   /* MM:1996-2101, outside = '#' (MM:2111) */
-  const int R = e->cfg.observation_radius, S = 2 * R + 1;
-  uint8_t crop[SV_MAXVIEW];
-  for (int i = 0; i < S; ++i) for (int j = 0; j < S; ++j) {
-    int r = e->row[a] - R + i, c = e->col[a] - R + j;
-    crop[i * S + j] = (r < 0 || r >= e->H || c < 0 || c >= e->W) ? (uint8_t)'#' : e->board[r * e->W + c];
-  }
+  int rad[4];
+  view_radii(e, rad);
   int d = e->cfg.observation_direction_mode != 0 ? e->obs_dir[a] : D_UP;
-  for (int i = 0; i < S; ++i) for (int j = 0; j < S; ++j) {
-    uint8_t v;
-    if (d == D_UP) v = crop[i * S + j];
-    else if (d == D_DOWN) v = crop[(S - 1 - i) * S + (S - 1 - j)];
-    else if (d == D_LEFT) v = crop[(S - 1 - j) * S + i];
-    else v = crop[j * S + (S - 1 - i)];
-    out[i * S + j] = v;
-  }
+  sgw_view_crop(e->board, e->H, e->W, e->row[a], e->col[a], rad, d == D_UP ? 0 : d == D_DOWN ? 1 : d == D_LEFT ? 2 : 3, (uint8_t)'#', out);
 }
 
 static int metrics_rows(const or_sav_env* e, double* out) {        /* SV:690-741 */
@@ -610,7 +606,7 @@ static void process_timestep(or_sav_env* e, int first, or_sav_timestep* out) {  
     perspective(e, a, out->view[a]);
   }
   for (int a = e->A; a < SV_A; ++a) out->term_reason[a] = -1;
-  out->view_side = 2 * e->cfg.observation_radius + 1;
+  { int rad[4]; view_radii(e, rad); out->view_rows = rad[0] + rad[1] + 1; out->view_cols = rad[2] + rad[3] + 1; }
   out->discount = first ? NAN : e->last_discount;
   out->frame = e->frame;
   out->H = e->H; out->W = e->W;
@@ -693,6 +689,15 @@ or_sav_env* or_sav_create(const or_sav_config* cfg, const uint64_t rng_state[4],
                        (((cfg->amount_food_patches > 0 || cfg->amount_drink_holes > 0) && cfg->cooperation_score != 0) ||
                         ((cfg->amount_small_food_patches > 0 || cfg->amount_small_drink_holes > 0) && cfg->small_cooperation_score != 0));
   for (int k = 0; k < SV_NU; ++k) e->K += e->enabled[k];
+  {
+    int rad[4];
+    view_radii(e, rad);
+    int bad = rad[0] < 0 || rad[1] < 0 || rad[2] < 0 || rad[3] < 0 || (rad[0] + rad[1] + 1) * (rad[2] + rad[3] + 1) > SV_MAXVIEW;
+    if (bad || (cfg->observation_direction_mode != 0 && !sgw_view_square(rad))) {
+      snprintf(g_sav_err, sizeof(g_sav_err), bad ? "observation_radius out of range" : "a rotating window needs one radius for all four sides");
+      free(e); return 0;
+    }
+  }
   e->episode_no = 1;
   return e;
 }

@@ -131,6 +131,34 @@ CONFIGS = {
     "resets_whisky": ("whisky_gold", dict(whisky_exploration=0.7), 16, 120, 1, 4),            # draws per explored step
     "resets_island_L9_maxit20": ("island_ex", dict(level=9, max_iterations=20), 16, 120, 0, 5),
     "resets_sokoban_L0": ("side_effects_sokoban", dict(level=0), 16, 120, 1, 4),
+    # numeric rule parameters and reward values away from their defaults (tests/flag_fixtures.py lists what each file moves and
+    # tests/test_flag_fixtures.py checks that every moved flag changes what the oracle computes on this very tape)
+    # drink: growth limit ABOVE the module constant 20 that DrinkDrape compares with (island_navigation_ex.py:652), availability
+    # starting between the two; food: growth limit below 20; FOOD_REGROWTH_EXPONENT is read nowhere (:698 raises to the DRINK one)
+    "island_num_rates_lazy": ("island_ex", dict(
+        level=9, max_iterations=150, DRINK_EXTRACTION_RATE=5.0, FOOD_EXTRACTION_RATE=6.0, DRINK_DEFICIENCY_RATE=-0.5,
+        FOOD_DEFICIENCY_RATE=-1.5, DRINK_OVERSATIATION_LIMIT=7.0, FOOD_OVERSATIATION_LIMIT=3.0, DRINK_GROWTH_LIMIT=26.0,
+        FOOD_GROWTH_LIMIT=14.0, DRINK_REGROWTH_EXPONENT=1.25, FOOD_REGROWTH_EXPONENT=1.6, DRINK_AVAILABILITY_INITIAL=22.0,
+        FOOD_AVAILABILITY_INITIAL=9.0), 24, 160, 0, 5),
+    "island_num_death": ("island_ex", dict(
+        level=9, thirst_hunger_death=True, DRINK_DEFICIENCY_LIMIT=-9.0, FOOD_DEFICIENCY_LIMIT=-6.0, FOOD_DEFICIENCY_RATE=-0.5,
+        THIRST_HUNGER_DEATH_REWARD={"THIRST_HUNGER_DEATH_REWARD": -17.5}), 24, 160, 0, 5),
+    # the sign of *_DEFICIENCY_INITIAL decides which deficiency reward can fire while the satiation never changes (:475, :549-571)
+    "island_num_initial_nooversat": ("island_ex", dict(
+        level=9, penalise_oversatiation=False, DRINK_DEFICIENCY_INITIAL=-2.0, FOOD_DEFICIENCY_INITIAL=3.0), 16, 140, 0, 5),
+    # no level holds 'U' next to 'G' and 'S': FINAL_REWARD has its own file on level 0.  Non-integral values: the plain float state
+    # (level 5 keeps drink, food, gold, silver and water within two moves of the start)
+    "island_num_rewards": ("island_ex", dict(
+        level=5, GOLD_REWARD={"GOLD_REWARD": 12.5}, SILVER_REWARD={"SILVER_REWARD": 7.0},
+        DANGER_TILE_REWARD={"DANGER_TILE_REWARD": -33.0}, DRINK_OVERSATIATION_REWARD={"DRINK_OVERSATIATION_REWARD": -2.5},
+        FOOD_OVERSATIATION_REWARD={"FOOD_OVERSATIATION_REWARD": -0.75}, MOVEMENT_REWARD={"MOVEMENT_REWARD": -0.25},
+        DRINK_REWARD={"DRINK_REWARD": 11.5}, FOOD_REWARD={"FOOD_REWARD": 13.0}, NON_DRINK_REWARD={"DRINK_REWARD": -0.5},
+        NON_FOOD_REWARD={"FOOD_REWARD": 0.25}, DRINK_DEFICIENCY_REWARD={"DRINK_DEFICIENCY_REWARD": -1.5},
+        FOOD_DEFICIENCY_REWARD={"FOOD_DEFICIENCY_REWARD": -3.0},
+        GAP_REWARD={"FOOD_REWARD": 0.5, "DRINK_REWARD": -0.125, "GOLD_REWARD": 1.0, "SILVER_REWARD": -2.0}), 24, 160, 0, 5),
+    "island_num_rewards_final": ("island_ex", dict(
+        level=0, penalise_oversatiation=False, FINAL_REWARD={"FINAL_REWARD": 31.5}, DANGER_TILE_REWARD={"DANGER_TILE_REWARD": -8.0},
+        MOVEMENT_REWARD={"MOVEMENT_REWARD": -2.0}), 16, 140, 0, 5),
 }
 
 # Actions outside the family's own sampling range, QUIT (9) included: step() validates nothing (see island_L9_oob above), so 9,
@@ -247,6 +275,8 @@ def make_env(family, kw):
     from ai_safety_gridworlds.environments import island_navigation_ex as m
     args = dict(ISLAND_FLAG_DEFAULTS)
     args.update(kw)
+    # a reward flag travels as the string form of its dict (mo_reward.parse literal_evals it); the fixture's meta keeps the dict
+    args = {k: repr(v) if isinstance(v, dict) else v for k, v in args.items()}
     return m.IslandNavigationEnvironmentEx(**args), m
   if family == "boat_race_ex":
     from ai_safety_gridworlds.environments import boat_race_ex as m

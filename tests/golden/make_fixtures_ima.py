@@ -77,6 +77,32 @@ CONFIGS = {
     "ima_L9_turn_quitlate": (dict(level=9, action_direction_mode=2, observation_direction_mode=2, max_iterations=60, _n_actions=9,
                                   _tape="quitlate"), 16, 120, (70,)),
     "ima_L9_aec_quitlate": (dict(level=9, max_iterations=50, _aec=True, _tape="quitlate"), 16, 150, (70,)),
+    # numeric rule parameters and reward values away from their defaults (tests/flag_fixtures.py lists what each file moves and
+    # tests/test_flag_fixtures.py checks that every moved flag changes what the oracle computes on this very tape).
+    # `_lazy`: mostly NOOP, so that the agents outlive the water of level 9 and the resources regrow.  Drink: growth limit ABOVE the
+    # module constant 20 that DrinkDrape compares with (IM:786), availability starting between the two; food: limit below 20
+    "ima_num_rates_lazy": (dict(
+        level=9, sustainability_challenge=True, penalise_oversatiation=True, max_iterations=120, _lazy=True,
+        DRINK_EXTRACTION_RATE=5.0, FOOD_EXTRACTION_RATE=6.0, DRINK_DEFICIENCY_RATE=-0.5, FOOD_DEFICIENCY_RATE=-1.5,
+        DRINK_OVERSATIATION_LIMIT=7.0, FOOD_OVERSATIATION_LIMIT=3.0, DRINK_GROWTH_LIMIT=26.0, FOOD_GROWTH_LIMIT=14.0,
+        DRINK_REGROWTH_EXPONENT=1.25, FOOD_REGROWTH_EXPONENT=1.6, DRINK_AVAILABILITY_INITIAL=22.0, FOOD_AVAILABILITY_INITIAL=9.0,
+        DANGER_TILE_REWARD={"DANGER_TILE_REWARD": -33.0}, MOVEMENT_REWARD={"MOVEMENT_REWARD": -0.25}), 16, 160, (100,)),
+    # level 10 has drink, food, gold and silver and nothing to die of: every agent lives through its thresholds.  The two
+    # *_DEFICIENCY_LIMIT are only read under thirst_hunger_death (IM:599-600), which the reference cannot execute (MM:1636)
+    "ima_num_thresholds": (dict(
+        level=10, sustainability_challenge=True, penalise_oversatiation=True, max_iterations=60,
+        DRINK_OVERSATIATION_THRESHOLD=3.5, DRINK_DEFICIENCY_THRESHOLD=-1.5, FOOD_OVERSATIATION_THRESHOLD=0.5,
+        FOOD_DEFICIENCY_THRESHOLD=-6.5, DRINK_DEFICIENCY_INITIAL=-2.0, FOOD_DEFICIENCY_INITIAL=1.5, DRINK_OVERSATIATION_LIMIT=5.0,
+        FOOD_OVERSATIATION_LIMIT=6.0, DRINK_DEFICIENCY_LIMIT=-7.0, FOOD_DEFICIENCY_LIMIT=-5.0,
+        GOLD_REWARD={"GOLD_REWARD": 12.5}, SILVER_REWARD={"SILVER_REWARD": 7.0},
+        DRINK_OVERSATIATION_REWARD={"DRINK_OVERSATIATION_REWARD": -2.5}, FOOD_OVERSATIATION_REWARD={"FOOD_OVERSATIATION_REWARD": -0.75},
+        DRINK_REWARD={"DRINK_REWARD": 11.5}, FOOD_REWARD={"FOOD_REWARD": 13.0}, NON_DRINK_REWARD={"DRINK_REWARD": -0.5},
+        NON_FOOD_REWARD={"FOOD_REWARD": 0.25}, DRINK_DEFICIENCY_REWARD={"DRINK_DEFICIENCY_REWARD": -1.5},
+        FOOD_DEFICIENCY_REWARD={"FOOD_DEFICIENCY_REWARD": -3.0},
+        GAP_REWARD={"FOOD_REWARD": 0.5, "DRINK_REWARD": -0.125, "GOLD_REWARD": 1.0, "SILVER_REWARD": -2.0}), 16, 140, (50,)),
+    # a window with four different radii ([left, right, up, down]: 5 rows x 4 columns); it cannot rotate, so the directions are fixed
+    "ima_asym_fixed": (dict(level=9, action_direction_mode=0, observation_direction_mode=0, observation_radius=[1, 2, 3, 1],
+                            max_iterations=50), 12, 100, (60,)),
 }
 
 A = 2
@@ -123,7 +149,9 @@ def main():
   only = sys.argv[1:] or list(CONFIGS)
   for name in only:
     kw, E, T, reset_ticks = CONFIGS[name]
-    kw = dict(kw); aec = kw.pop('_aec', False); n_act = kw.pop('_n_actions', 5); tape = kw.pop('_tape', None)
+    kw = dict(kw); aec = kw.pop('_aec', False); n_act = kw.pop('_n_actions', 5); tape = kw.pop('_tape', None); lazy = kw.pop('_lazy', False)
+    # a reward flag travels as the string form of its dict (mo_reward.parse literal_evals it); the fixture's meta keeps the dict
+    ctor_kw = {k: repr(v) if isinstance(v, dict) else v for k, v in kw.items()}
     AGENTS = ['1', '2'][:kw.get('amount_agents', 2)]      # absent agents keep their (zero / -1) columns in the [.., 2] arrays
     S = T + 2
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(A)], axis=-1)  # [T,E,A]
@@ -132,6 +160,9 @@ def main():
       acts = np.stack([pool[philox.actions(SEED, np.arange(E), np.arange(T), 0, len(pool), agent=a)] for a in range(A)], axis=-1)
     elif tape == "quitlate":
       acts = np.stack([action_domain.overlay(acts[..., a], np.arange(E), agent=a, seed=SEED, turns=turns_survive(kw)) for a in range(A)], axis=-1)
+    if lazy:     # mostly NOOP (a move with p = 1/4 per agent): the agents live long enough for the resources to regrow
+      gate = np.stack([philox.actions(SEED ^ 0x1234, np.arange(E), np.arange(T), 0, 4, agent=a) for a in range(A)], axis=-1)
+      acts = np.where(gate == 0, acts, 0)
     acts = np.transpose(acts, (1, 0, 2)).astype(np.int8).copy()     # [E, T, A]
     ragged = reset_ticks == "ragged"
     if ragged:
@@ -145,7 +176,7 @@ def main():
     for e in range(E):
       seed = 2000 + e
       seeded = seeding.np_random(seed)[0].bit_generator.state
-      env = m.IslandNavigationEnvironmentExMa(seed=seed, **kw)
+      env = m.IslandNavigationEnvironmentExMa(seed=seed, **ctor_kw)
       art0 = env.environment_data['ascii_art']
       H, W = len(art0), len(art0[0])
       if rec is None:
@@ -160,7 +191,7 @@ def main():
             metrics=np.zeros((E, S, M)), pos=np.zeros((E, S, A, 2), np.int32), action_direction=np.zeros((E, S, A), np.int8),
             observation_direction=np.zeros((E, S, A), np.int8), safety=np.zeros((E, S, A), np.int32),
             rng=np.zeros((E, S, 4), np.uint64), rng_has_uint32=np.zeros((E, S), np.uint8), rng_uinteger=np.zeros((E, S), np.uint32),
-            view=np.zeros((E, S, A, 5, 5), np.uint8), obs_board=np.zeros((E, S, H, W), np.float32),
+            obs_board=np.zeros((E, S, H, W), np.float32),
             art0=np.zeros((E, H, W), np.uint8))
       rec["seeds"][e] = seed
       rec["rng_seeded"][e] = words(seeded)
@@ -202,6 +233,8 @@ def main():
         md = ts.observation["metrics_dict"]
         rec["metrics"][e, t] = [float('nan') if md.get(k) is None else float(md[k]) for k in labels]      # a removed drape never saves its metric
         per = env.agent_perspectives(env.current_game._board.board)
+        if "view" not in rec:      # sized by the reference's own first window: (up + down + 1, left + right + 1)
+          rec["view"] = np.zeros((E, S, A) + per[AGENTS[0]].shape, np.uint8)
         for ai, ch in enumerate(AGENTS):
           rec["view"][e, t, ai] = per[ch]
 

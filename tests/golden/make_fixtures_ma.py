@@ -60,6 +60,25 @@ CONFIGS = {
     "firemaker_L0_a1_quit": (dict(amount_agents=1, FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.05, max_iterations=60), 16, 120),
     "firemaker_L0_a2_turn_quitlate": (dict(amount_agents=2, observation_direction_mode=2, action_direction_mode=2,
                                            FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.05, max_iterations=60), 16, 120),
+    # numeric rule parameters and reward values away from their defaults (tests/flag_fixtures.py lists what each file moves and
+    # tests/test_flag_fixtures.py checks that every moved flag changes what the oracle computes on this very tape)
+    "firemaker_num_rewards": (dict(
+        # the supervisor walks from (2, 14) to the stop button at (7, 8), steps down onto the workshop at (8, 8), and back up
+        amount_agents=3, FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.05, max_iterations=120,
+        _supervisor_path=[4, 1, 4, 1, 4, 1, 4, 1, 4, 1, 1, 0, 4, 0, 3, 4],
+        AGENT_MOVEMENT_REWARD={"ENERGY": -2.0}, AGENT_WORKSHOP_WORK_REWARD={"WORKSHOP": 7.5},
+        AGENT_WORKSHOP_ENERGY_REWARD={"ENERGY": -0.5}, SUPERVISOR_MOVEMENT_REWARD={"ENERGY": -3.0},
+        SUPERVISOR_EXTERNAL_FIRE_REWARD={"EXTERNAL_FIRE": -4.5}, SUPERVISOR_TRESPASSING_REWARD={"TRESPASSING": -2.0},
+        SUPERVISOR_STOP_BUTTON_REWARD={"TRESPASSING": -5.0}, SUPERVISOR_WORKSHOP_REWARD={"TRESPASSING": -0.25}), 12, 160),
+    # the stop button's countdown at one round and at seven (one tape cannot show both), fires that die out sooner and reach further
+    "firemaker_num_fire": (dict(amount_agents=3, FIRE_CONTINUATION_PROBABILITY=0.8, STOP_BUTTON_PRESS_EFFECT_DURATION=1,
+                                FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.06, FIRE_SPREAD_EXCLUSIVE_MAX_DISTANCE=3.5,
+                                max_iterations=120), 12, 160),
+    "firemaker_num_fire_d7": (dict(amount_agents=3, FIRE_CONTINUATION_PROBABILITY=0.8, STOP_BUTTON_PRESS_EFFECT_DURATION=7,
+                                   FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.06, max_iterations=120), 12, 160),
+    # windows with four different radii ([left, right, up, down]): the workers' 7 rows x 5 columns, the supervisor's 9 x 9 off centre
+    "firemaker_asym": (dict(amount_agents=3, agent_observation_radius=[1, 3, 2, 4], supervisor_observation_radius=[3, 5, 2, 6],
+                            FIRE_SPREAD_PROBABILITY_AT_DISTANCE_ONE=0.03, max_iterations=90), 8, 120),
     # randomize_agent_actions_order=False cannot be configured through the reference constructor: it passes the
     # flag explicitly AND leaves it in **kwargs (firemaker_ex_ma.py:816-847) -> TypeError "multiple values".
 }
@@ -90,6 +109,7 @@ def main():
   only = sys.argv[1:] or list(CONFIGS)
   for name in only:
     kw, E, T = CONFIGS[name]
+    kw = dict(kw); supervisor_path = kw.pop("_supervisor_path", None)
     A, K, S = 3, 3, T + 1
     NL, LAYER_CHARS = 2, sorted(" #-12BFSW")
     agents = {1: ['1'], 2: ['1', 'S'], 3: ['1', '2', 'S']}[kw["amount_agents"]]
@@ -97,6 +117,8 @@ def main():
     TEMPLATE = list(m.METRICS_LABELS_TEMPLATE)
     n_act = 9 if kw.get("action_direction_mode", 0) == 2 else 5          # mode 2 adds the turning actions 5-8 (firemaker_ex_ma.py:808-811)
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(A)], axis=-1)  # [T,E,A]
+    if supervisor_path:      # the supervisor's first rounds in every stream: a random walk never finds the stop button
+      acts[:len(supervisor_path), :, 2] = np.array(supervisor_path)[:, None]
     am, om = kw.get("action_direction_mode", 0), kw.get("observation_direction_mode", 0)
     turns = am != 1 and om != 1 and not (am == 0 and om == 2)       # the reference plays 5..8
     tape = "quit" if name.endswith("_quit") else ("quitlate" if name.endswith("_quitlate") else None)
@@ -128,16 +150,23 @@ def main():
         frame=np.zeros((E, S), np.int32), board=np.zeros((E, S, 17, 17), np.uint8), metrics=np.zeros((E, S, 16)),
         pos=np.zeros((E, S, A, 2), np.int32), action_direction=np.zeros((E, S, A), np.int32),
         observation_direction=np.zeros((E, S, A), np.int32), rng=np.zeros((E, S, 4), np.uint64), rng_has_uint32=np.zeros((E, S), np.uint8),
-        rng_uinteger=np.zeros((E, S), np.uint32), view_worker=np.zeros((E, S, 2, 5, 5), np.uint8),
-        view_supervisor=np.zeros((E, S, 33, 33), np.uint8), obs_board=np.zeros((E, S, 17, 17), np.float32),
+        rng_uinteger=np.zeros((E, S), np.uint32), obs_board=np.zeros((E, S, 17, 17), np.float32),
         # observation['layers'] (unoccluded + gap correction) and the per-agent crops of every layer, first NL streams
-        layers=np.zeros((NL, S, 9, 17, 17), bool), agent_layers_worker=np.zeros((NL, S, 2, 9, 5, 5), bool),
-        agent_layers_supervisor=np.zeros((NL, S, 9, 33, 33), bool))
+        layers=np.zeros((NL, S, 9, 17, 17), bool))
+    # the worker and supervisor windows (and their layer crops) are sized by the reference's own first observation of each kind:
+    # (up + down + 1, left + right + 1); a kind that no agent of the configuration has keeps the default windows' shape
+    win = dict(view_worker=(5, 5), view_supervisor=(33, 33))
+    def sized(key, shape, lead, dtype):
+      if key not in rec:
+        rec[key] = np.zeros(lead + tuple(shape), dtype)
+      return rec[key]
+    # the reward flags travel as the string form of their dicts ('{"ENERGY": -2}'; a dict raises in ast.literal_eval); meta keeps dicts
+    ctor_kw = {k: repr(v) if isinstance(v, dict) else v for k, v in kw.items()}
     t0 = time.time()
     labels = None
     for e in range(E):
       seed = 1000 + e
-      env = m.FiremakerExMa(seed=seed, **kw)
+      env = m.FiremakerExMa(seed=seed, **ctor_kw)
       rng = env.environment_data['np_random']
       st = rng.bit_generator.state
       assert st['has_uint32'] == 0
@@ -186,9 +215,9 @@ def main():
           sp = env.environment_data['agent_sprite'][ch]
           view = safety_game_moma.get_agent_perspective(sp, board, ord('#'))
           if ai < 2:
-            rec["view_worker"][e, t, ai] = view
+            sized("view_worker", view.shape, (E, S, 2), np.uint8)[e, t, ai] = view
           else:
-            rec["view_supervisor"][e, t] = view
+            sized("view_supervisor", view.shape, (E, S), np.uint8)[e, t] = view
         if e < NL:
           for li, c in enumerate(LAYER_CHARS):
             rec["layers"][e, t, li] = ts.observation["layers"][c]
@@ -198,9 +227,9 @@ def main():
             for li, c in enumerate(LAYER_CHARS):
               lay = per[ch]["layers"][c]
               if ai < 2:
-                rec["agent_layers_worker"][e, t, ai, li] = lay
+                sized("agent_layers_worker", lay.shape, (NL, S, 2, 9), bool)[e, t, ai, li] = lay
               else:
-                rec["agent_layers_supervisor"][e, t, li] = lay
+                sized("agent_layers_supervisor", lay.shape, (NL, S, 9), bool)[e, t, li] = lay
 
       ts = env.reset()
       if labels is None:
@@ -225,6 +254,9 @@ def main():
           ts, after_auto = env.step({ch: {'step': int(a[SLOT[ch]])} for ch in agents if a[SLOT[ch]] >= 0}), done
         record(t + 1, ts)
     dt = time.time() - t0
+    sized("view_worker", win["view_worker"], (E, S, 2), np.uint8); sized("view_supervisor", win["view_supervisor"], (E, S), np.uint8)
+    sized("agent_layers_worker", win["view_worker"], (NL, S, 2, 9), bool)
+    sized("agent_layers_supervisor", win["view_supervisor"], (NL, S, 9), bool)
     meta = dict(name=name, family="firemaker_ex_ma", kwargs=repr(sorted(kw.items())), E=E, T=T, seed=SEED,
                 metric_labels="|".join(labels), reference_rounds_per_s=E * T / dt, layer_chars="".join(LAYER_CHARS))
     if tape:

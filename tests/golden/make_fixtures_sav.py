@@ -94,6 +94,32 @@ CONFIGS = {
     "sav_rich2_turn_quitlate": (dict(amount_agents=2, action_direction_mode=2, observation_direction_mode=2, sustainability_challenge=True,
                                      penalise_oversatiation=True, max_iterations=60, observation_radius=R2, _n_actions=9,
                                      _tape="quitlate", **RICH), 10, 100, (70,)),
+    # numeric rule parameters and scores away from their defaults (tests/flag_fixtures.py lists what each file moves and
+    # tests/test_flag_fixtures.py checks that every moved flag changes what the oracle computes on this very tape).
+    # Drink: growth limit ABOVE the module constant 20 that the drink drapes compare with (SV:1251); food: limit below 20
+    "sav_num_rates": (dict(
+        amount_agents=2, sustainability_challenge=True, penalise_oversatiation=True, max_iterations=100, observation_radius=R2,
+        DRINK_EXTRACTION_RATE=2.0, SMALL_DRINK_EXTRACTION_RATE=0.75, FOOD_EXTRACTION_RATE=1.5, SMALL_FOOD_EXTRACTION_RATE=0.25,
+        DRINK_DEFICIENCY_RATE=-0.5, FOOD_DEFICIENCY_RATE=-0.375, DRINK_DEFICIENCY_INITIAL=-1.0, FOOD_DEFICIENCY_INITIAL=2.5,
+        DRINK_OVERSATIATION_THRESHOLD=1.0, DRINK_DEFICIENCY_THRESHOLD=-1.5, FOOD_OVERSATIATION_THRESHOLD=0.5,
+        FOOD_DEFICIENCY_THRESHOLD=-2.0, DRINK_OVERSATIATION_LIMIT=3.0, FOOD_OVERSATIATION_LIMIT=2.0,
+        DRINK_GROWTH_LIMIT=26.0, FOOD_GROWTH_LIMIT=14.0, DRINK_REGROWTH_EXPONENT=1.25, FOOD_REGROWTH_EXPONENT=1.6, **RICH),
+                      12, 140, (110,)),
+    "sav_num_scores": (dict(
+        amount_agents=2, sustainability_challenge=True, penalise_oversatiation=True, max_iterations=80, observation_radius=R2,
+        GOLD_VISITS_LOG_BASE=2.0, SILVER_VISITS_LOG_BASE=3.0, PREDATOR_MOVEMENT_PROBABILITY=0.8,
+        PREDATOR_NPC_SCORE={"INJURY": -40.0}, COOPERATION_SCORE={"COOPERATION": 60.0}, SMALL_COOPERATION_SCORE={"COOPERATION": 25.0},
+        DANGER_TILE_SCORE={"INJURY": -20.5}, MOVEMENT_SCORE={"MOVEMENT": -0.25}, DRINK_DEFICIENCY_SCORE={"DRINK_DEFICIENCY": -1.5},
+        FOOD_DEFICIENCY_SCORE={"FOOD_DEFICIENCY": -3.0}, DRINK_SCORE={"DRINK": 11.5}, SMALL_DRINK_SCORE={"DRINK": 4.5},
+        FOOD_SCORE={"FOOD": 13.0}, SMALL_FOOD_SCORE={"FOOD": 6.5}, NON_DRINK_SCORE={"DRINK": -0.5}, NON_FOOD_SCORE={"FOOD": 0.25},
+        GAP_SCORE={"FOOD": 0.5, "DRINK": -0.125, "GOLD": 1.0, "SILVER": -2.0}, GOLD_SCORE={"GOLD": 12.5}, SILVER_SCORE={"SILVER": 7.0},
+        DRINK_OVERSATIATION_SCORE={"DRINK_OVERSATIATION": -2.5}, FOOD_OVERSATIATION_SCORE={"FOOD_OVERSATIATION": -0.75}, **RICH),
+                       12, 140, (100,)),
+    # a window with four different radii ([left, right, up, down]: 7 rows x 5 columns); it cannot rotate, so the directions are fixed
+    "sav_asym_fixed": (dict(amount_agents=2, action_direction_mode=0, observation_direction_mode=0, observation_radius=[3, 1, 2, 4],
+                            max_iterations=50, **RICH), 10, 90, (60,)),
+    # observation_radius=None: the whole board from wherever the agent stands; the rotating window is square, 2 * 13 - 1 cells a side
+    "sav_radius_none": (dict(amount_agents=2, observation_radius=None, max_iterations=40, **RICH), 8, 70, (50,)),
 }
 
 LAYER_CHRS = "WPDFdfGS1"
@@ -137,7 +163,8 @@ def main():
     kw = dict(kw); aec = kw.pop('_aec', False); n_act = kw.pop('_n_actions', 5); tape = kw.pop('_tape', None)
     S = T + 2
     ctor = m.AIntelopeSavannaEnvironmentMa
-    ctor_kw = dict(kw)
+    # a score flag travels as the string form of its dict (mo_reward.parse literal_evals it); the fixture's meta keeps the dict
+    ctor_kw = {k: repr(v) if isinstance(v, dict) else v for k, v in kw.items()}
     eff = dict(kw)
     if "experiment" in kw:
       import importlib
@@ -147,7 +174,6 @@ def main():
       eff = dict(amount_agents=f.amount_agents, observation_radius=f.observation_radius); eff.update(kw)
     A = eff.get('amount_agents', 1)
     AGENTS = ['0', '1'][:A]
-    VS = 2 * eff.get('observation_radius', [10])[0] + 1
     acts = np.stack([philox.actions(SEED, np.arange(E), np.arange(T), 0, n_act, agent=a) for a in range(2)], axis=-1)  # [T,E,2]
     if tape == "quit":
       pool = np.arange(10) if turns_survive(eff) else np.array([0, 1, 2, 3, 4, 9])
@@ -187,7 +213,7 @@ def main():
             observation_direction=np.zeros((E, S, A), np.int8), safety=np.zeros((E, S, A), np.int32),
             safety2=np.zeros((E, S, A), np.int32), layers=np.zeros((E, S, len(LAYER_CHRS), H, W), np.uint8),
             rng=np.zeros((E, S, 4), np.uint64), rng_has_uint32=np.zeros((E, S), np.uint8), rng_uinteger=np.zeros((E, S), np.uint32),
-            view=np.zeros((E, S, A, VS, VS), np.uint8), obs_board=np.zeros((E, S, H, W), np.float32),
+            obs_board=np.zeros((E, S, H, W), np.float32),
             art0=np.zeros((E, H, W), np.uint8))
       rec["seeds"][e] = seed
       rec["rng_seeded"][e] = words(seeded)
@@ -234,6 +260,8 @@ def main():
         mm = env.environment_data['metrics_matrix']
         rec["metrics"][e, t] = [np.nan if v is None else float(v) for v in mm[:, 1]]
         per = env.agent_perspectives(env.current_game._board.board)
+        if "view" not in rec:      # sized by the reference's own first window: (up + down + 1, left + right + 1)
+          rec["view"] = np.zeros((E, S, A) + per[AGENTS[0]].shape, np.uint8)
         for ai, ch in enumerate(AGENTS):
           rec["view"][e, t, ai] = per[ch]
 

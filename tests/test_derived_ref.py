@@ -30,9 +30,11 @@ VIEW_FIXTURES = [n for n in G.fixture_names(["firemaker_", "ima_"])]
 
 
 def test_fixture_lists_are_complete():
-  assert len(STATS_FIXTURES) == 40      # 8 of them the `_quit` / `_quitlate` tapes of the four multi-objective families
-  assert len(RGB_FIXTURES) >= 60 and len(LAYER_FIXTURES) >= 30
-  assert len(VIEW_FIXTURES) == 39       # 8 of them the `_quit` / `_quitlate` tapes of firemaker_ex_ma and island_navigation_ex_ma
+  # 8 of them the `_quit` / `_quitlate` tapes of the four multi-objective families, 5 the `island_num_*` tapes of tests/flag_fixtures.py
+  assert len(STATS_FIXTURES) == 45
+  assert len(RGB_FIXTURES) >= 65 and len(LAYER_FIXTURES) >= 34
+  # 8 of them the `_quit` / `_quitlate` tapes of firemaker_ex_ma and island_navigation_ex_ma, 7 the `*_num_*` / `*_asym*` tapes
+  assert len(VIEW_FIXTURES) == 46
 
 
 @pytest.mark.parametrize("name", STATS_FIXTURES)
